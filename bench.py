@@ -7,13 +7,16 @@ One "step" = one complete PPO iteration of the hot path on one GPU:
     (advantage stats, forward+backward of the clipped-surrogate loss, [RCCL all-reduce of the flat gradient], clip + Adam).
 Nothing is skipped inside the timed region.  `value` = env-steps of all ranks / max-over-ranks wall time.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   N > 1 started as a plain process: this file starts N ranks itself (a child `python -m torch.distributed.run`, one rank per GPU,
   before this process makes any GPU call) and exits with the child's status; started under torch.distributed.run it is one rank.
-Prints ONE compact JSON line (< 4 KB) on rank 0: the contract keys, `roofline` (dominant kernel), `cpu_baseline` and one-number summaries of
-the other legs.  The full objects -- (N = 1) `extra_configs`, the other single-GPU BASELINE.json configs, time-boxed; `literal_batch_256`, the
-reference's literal batch_size on the headline shape; the harness leg; the per-config CPU table; the step / GAE / rollout rooflines -- go
-to `bench_extras.json` beside this file (and to gpurun_out/ when present); the line's `extras_path` names it.
+A plain run sets up, warms up, times the K iterations and prints ONE compact JSON line (< 4 KB) on rank 0: the contract keys, the
+configuration and the rollout / update split of the timed iterations.  `--dump-outputs DIR` writes what the last timed iteration computed
+(the updated policy parameters and a fixed, seeded sample of its rollout buffer) as DIR/<name>.npy before the line is printed.
+`--full` adds every other leg: `roofline` (dominant kernel), `cpu_baseline`, the step / GAE / rollout rooflines, (N > 1) `dp_timing`, and (N = 1)
+`extra_configs`, the other single-GPU BASELINE.json configs, time-boxed; `literal_batch_256`, the reference's literal batch_size on the headline
+shape; the harness leg; the reward-threshold runs.  The line then carries `roofline`, `cpu_baseline` and one-number summaries of the other legs;
+the full objects go to `bench_extras.json` beside this file, which the line's `extras_path` names.
 """
 from __future__ import annotations
 
@@ -60,11 +63,18 @@ def parse():
     ap.add_argument("--mfma-dtype", default="f32", choices=["f32", "bf16", "bf16x3"],
                     help="MFMA operand type of the hidden-layer GEMMs (bf16: hidden 128/192/256 only; BASELINE.json configs[2])")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed iterations also run the roofline, extra-config, literal-batch, harness, threshold and CPU-baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed iteration computed (policy parameters, a seeded sample of the rollout buffer) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=36.0, help="CPU-baseline budget over all five configs x {1 thread, all cores}")
-    ap.add_argument("--no-extras", action="store_true", help="skip extra_configs / literal_batch_256 (N = 1 default runs include them)")
-    ap.add_argument("--sweep", action="store_true", help="also run the env-count sweep of the step kernel (extra JSON field)")
-    return ap.parse_args()
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip extra_configs / literal_batch_256 (N = 1 --full runs include them)")
+    ap.add_argument("--sweep", action="store_true", help="with --full: also run the env-count sweep of the step kernel (extra JSON field)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def log(msg):
@@ -146,6 +156,42 @@ def time_iterations(model, steps, warmup):
     el = time.perf_counter() - t0
     model._bench_local = (el, t_roll)  # this rank's own clock (dp_timing: per-rank rollout / update split)
     return dist.allreduce_max_float(el, device=model.device), dist.allreduce_max_float(t_roll, device=model.device)
+
+
+DUMP_SAMPLE_SEED = 20240611  # the (t, env) rows of the rollout buffer that --dump-outputs writes: the same rows in every run of a shape
+DUMP_SAMPLE_ROWS = 1 << 16
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(model, path):
+    """What the last timed iteration handed back to a caller, as float32 / float64 .npy files under `path`: the trainable policy parameters
+    after its update (`policy_params`), the rollout it collected (a fixed, seeded sample of at most 65536 (t, env) rows of every plane of the
+    buffer, `sample_index` = t * n_envs + env) and the bootstrap values of its last observation.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+
+    b = model.buf
+    T, N = model.n_steps, model.n_envs
+    D = b["obs"].shape[-1]
+    A = b["actions"].shape[-1] if b["actions"].dim() == 3 else 1
+    per_row = 4 * (D + A + 7) + 8  # (obs, actions, seven scalar planes in f32, the row index in f64)
+    k = min(T * N, DUMP_SAMPLE_ROWS, DUMP_BUDGET_BYTES // per_row)
+    rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(T * N, size=k, replace=False))
+    idx = torch.from_numpy(rows).to(model.device)
+    torch.cuda.synchronize()
+    arrays = {"policy_params": model.policy.params[: model.policy.n_trainable], "sample_index": torch.from_numpy(rows.astype(np.float64)),
+              "last_values": b["last_values"][:DUMP_SAMPLE_ROWS]}
+    for name in ("obs", "actions", "log_probs", "values", "rewards", "terminated", "truncated", "advantages", "returns"):
+        plane = b[name][:T].reshape(T * N, -1) if name in ("obs", "actions") and b[name].dim() == 3 else b[name][:T].reshape(T * N)
+        arrays[name] = plane.index_select(0, idx)
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)  # (int32 actions, uint8 flags: exact in f32)
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def grad_kernel_roofline(model, task, hidden, mfma, batch, reps=24):
@@ -813,7 +859,8 @@ def compact_line(out, extras_path=None, limit=LINE_LIMIT):
     line["config"] = {**_pick(cfg, ("envs_per_gpu", "n_steps", "batch_size", "n_epochs", "hidden")),
                       "workload": str(cfg.get("workload", ""))[:260], "parallelism": str(cfg.get("parallelism", "")).split(":")[0][:40]}
     line.update(_pick(out, ("ppo_updates_per_sec", "rollout_ms", "update_ms")))
-    line["roofline"] = _roof_short(out.get("roofline"), ("samples_per_launch", "flops_per_sample_fwd_bwd"))
+    if "roofline" in out:  # (--full runs only)
+        line["roofline"] = _roof_short(out["roofline"], ("samples_per_launch", "flops_per_sample_fwd_bwd"))
     cb = out.get("cpu_baseline")
     if isinstance(cb, dict):
         line["cpu_baseline"] = ({"error": str(cb["error"])[:160]} if "error" in cb else
@@ -909,12 +956,15 @@ def main():
     batch = args.batch_size if args.batch_size > 0 else max(256, total // 32)
     env, model = build_model(args.task, N, T, args.hidden, args.mfma_dtype, batch, args.n_epochs, args.seed, dev, rank)
     log(f"rank {rank}/{world}: engine ready, N={N} T={T} batch={batch}")
-    if world > 1:
+    if world > 1 and args.full:
         model.dp_timing = {}  # HIP events around the collectives of the first minibatches / epochs of every train() call
         if model._native_comm is not None:  # (native RCCL path: the library brackets its own ncclAllReduce calls)
             model._native_comm.timing(model.dp_timing_samples)
     el, t_roll = time_iterations(model, args.steps, args.warmup)
     log(f"timed region done: {el:.3f} s for {args.steps} iterations")
+    if args.dump_outputs and rank == 0:  # before any other leg touches the model's buffers
+        shapes = dump_outputs(model, args.dump_outputs)
+        log(f"outputs of the last timed iteration written to {args.dump_outputs}: {shapes}")
     env_steps = world * total * args.steps
     updates = args.steps * args.n_epochs * ((total + batch - 1) // batch)
     train_stats = model.pop_train_stats()
@@ -936,7 +986,7 @@ def main():
         "update_ms": (el - t_roll) / args.steps * 1e3, "train_stats": {k: round(v, 6) for k, v in train_stats.items()},
     }
 
-    if world > 1:
+    if world > 1 and args.full:
         # what a multi-GPU number is made of: per-collective HIP-event durations on rank 0 and every rank's own rollout / update split
         import torch.distributed as td
 
@@ -960,7 +1010,7 @@ def main():
             "note": "durations are HIP events on rank 0's compute stream: from the end of the kernel that produced the tensor to the point where the "
                     "reduced tensor is usable (collective + both stream hand-offs); update_ms - n * median is what the GPU spent in kernels",
         }
-    if rank == 0:
+    if rank == 0 and args.full:
         roof = grad_kernel_roofline(model, args.task, args.hidden, args.mfma_dtype, batch)
         log(f"minibatch gradient kernel: median {roof['launch_us']:.1f} us (launch group of the call: {roof['launch_group_us']:.1f} us)")
         if args.mfma_dtype == "bf16" and args.hidden == 256 and args.task == "ball3d":
@@ -973,7 +1023,8 @@ def main():
     env.close()
     del model
     torch.cuda.empty_cache()
-    if rank == 0:
+    extras_path = None
+    if rank == 0 and args.full:  # every leg beyond the headline figure
         if world == 1 and not args.no_extras:
             try:
                 out["literal_batch_256"] = literal_batch_256(args, dev)

@@ -69,3 +69,28 @@ def test_extras_file(tmp_path, monkeypatch):
     for d in (tmp_path, tmp_path / "gpurun_out"):
         with open(d / "bench_extras.json") as f:
             assert json.load(f)["extra_configs"] == [1, 2, 3]
+
+
+def test_plain_run_line_has_the_contract_keys_only():
+    """A run without --full measures no roofline, CPU baseline or extra legs: its line carries the contract keys and the rollout / update
+    split, and no empty placeholders for the legs it did not run."""
+    full = _canned()
+    out = {k: full[k] for k in CONTRACT + ("ppo_updates_per_sec", "rollout_ms", "update_ms", "train_stats")}
+    line = json.loads(bench.compact_line(out, None))
+    for k in CONTRACT:
+        assert k in line, k
+    assert line["value"] == out["value"] and line["ms_per_step"] == out["ms_per_step"] and line["extras_path"] is None
+    assert not any(k in line for k in ("roofline", "cpu_baseline", "extra_configs", "other_rooflines", "dropped_to_fit"))
+
+
+def test_options():
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+        sys.argv = ["bench.py", "--steps", "2", "--full", "--dump-outputs", "out"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "out"
+    finally:
+        sys.argv = argv

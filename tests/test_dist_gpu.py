@@ -518,7 +518,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu(p2p, gpus):
     # (gpus = 8: the driver's `--gpus 8` rank program, one JSON line with n_gpus 8 and a dp_timing object -- the first real 8-GPU run must not
     #  fail on plumbing)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--n-envs", "512", "--n-steps", "64", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--n-envs", "512", "--n-steps", "64", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=860, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
