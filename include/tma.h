@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 208
+#define TMA_VERSION 209
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -356,6 +356,42 @@ int tma_debug_time_grad_kernel(int enable);
 /* Test aid: fills the LDS of every CU with `pattern` (0: quiet NaNs) so that a kernel reading LDS it never wrote shows it in its outputs. */
 int tma_debug_poison_lds(unsigned pattern, void *stream);
 int tma_debug_last_grad_kernel_us(float *us_out);
+/* Test aid: which specialisation the calling thread's last call of each policy dispatcher chose -- the forward (tma_policy_act / _act_bootstrap /
+ * _values / _bootstrap), the minibatch gradient (tma_ppo_minibatch_grad and the epoch loops built on it) and the optimizer step
+ * (tma_ppo_adam_step / _local).  Recorded on the host where each dispatcher decides, before its launches, whether or not they succeed;
+ * TMA_DISPATCH_NONE after a call that was refused before a specialisation was picked.  Any pointer may be NULL.  No GPU work. */
+enum {
+    TMA_DISPATCH_NONE = 0,
+    /* forward: H = 64 fast path; column-parallel kernels by dtype x hidden width (NTW = H / 64) x head; generic LDS kernel by waves per block */
+    TMA_DISPATCH_FWD_H64 = 1,
+    TMA_DISPATCH_FWD_F32_NTW2_DISCRETE = 2, TMA_DISPATCH_FWD_F32_NTW3_DISCRETE = 3, TMA_DISPATCH_FWD_F32_NTW4_DISCRETE = 4,
+    TMA_DISPATCH_FWD_F32_NTW2_BOX = 5, TMA_DISPATCH_FWD_F32_NTW3_BOX = 6, TMA_DISPATCH_FWD_F32_NTW4_BOX = 7,
+    TMA_DISPATCH_FWD_BF16_NTW2_DISCRETE = 8, TMA_DISPATCH_FWD_BF16_NTW3_DISCRETE = 9, TMA_DISPATCH_FWD_BF16_NTW4_DISCRETE = 10,
+    TMA_DISPATCH_FWD_BF16_NTW2_BOX = 11, TMA_DISPATCH_FWD_BF16_NTW3_BOX = 12, TMA_DISPATCH_FWD_BF16_NTW4_BOX = 13,
+    TMA_DISPATCH_FWD_GENERIC_W4 = 14, TMA_DISPATCH_FWD_GENERIC_W2 = 15, TMA_DISPATCH_FWD_GENERIC_W1 = 16,
+    /* gradient: H = 64 kernel (<= 2048 samples: one tile per wave; else the persistent eight-wave kernel); bf16; three-term bf16 split */
+    TMA_DISPATCH_GRAD_H64_SMALL = 32, TMA_DISPATCH_GRAD_H64 = 33, TMA_DISPATCH_GRAD_BF16 = 34, TMA_DISPATCH_GRAD_BF16X3 = 35,
+    /* f32 column-parallel, layer-1 k-tiles kt1 = 1 (D <= 16) / 2 (D <= 32): half (16-row) or full row groups, four or eight waves,
+     * dW2 deferred to the follow-up reduction or accumulated in the slabs */
+    TMA_DISPATCH_GRAD_F32_KT1_HALF_W4 = 36, TMA_DISPATCH_GRAD_F32_KT1_FULL_W4 = 37, TMA_DISPATCH_GRAD_F32_KT2_HALF_W4 = 38,
+    TMA_DISPATCH_GRAD_F32_KT2_FULL_W4 = 39, TMA_DISPATCH_GRAD_F32_KT1_HALF_W8_DEFER = 40, TMA_DISPATCH_GRAD_F32_KT1_HALF_W8_SLAB = 41,
+    TMA_DISPATCH_GRAD_F32_KT1_FULL_W8 = 42, TMA_DISPATCH_GRAD_F32_KT2_HALF_W8_DEFER = 43, TMA_DISPATCH_GRAD_F32_KT2_HALF_W8_SLAB = 44,
+    TMA_DISPATCH_GRAD_F32_KT2_FULL_W8 = 45,
+    /* kt1 = 7 (H = 256, 33..112 observations, <= 1024 samples): half groups, eight waves, dW2 deferred */
+    TMA_DISPATCH_GRAD_F32_SMALL7 = 46,
+    /* two passes (chain, then dW1) with 11 / 7 layer-1 k-tiles, dW1 from the cached dz1 operands or a recomputed chain; runtime width */
+    TMA_DISPATCH_GRAD_F32_KT11_CACHED = 47, TMA_DISPATCH_GRAD_F32_KT11_RECOMPUTE = 48, TMA_DISPATCH_GRAD_F32_KT107_CACHED = 49,
+    TMA_DISPATCH_GRAD_F32_KT107_RECOMPUTE = 50, TMA_DISPATCH_GRAD_F32_KT0 = 51,
+    /* generic float-atomic kernel by waves per block */
+    TMA_DISPATCH_GRAD_GENERIC_W4 = 52, TMA_DISPATCH_GRAD_GENERIC_W3 = 53, TMA_DISPATCH_GRAD_GENERIC_W2 = 54, TMA_DISPATCH_GRAD_GENERIC_W1 = 55,
+    /* optimizer: Adam + scatter into the derived copies (H = 64 fast path / column-parallel layouts); single-block kernel; multi-block kernel
+     * + tma_policy_sync; the _local forms of the two scatters, which fold the norm partials the gradient's reduction left */
+    TMA_DISPATCH_OPT_SCATTER_H64 = 64, TMA_DISPATCH_OPT_SCATTER_WIDE = 65, TMA_DISPATCH_OPT_SMALL = 66, TMA_DISPATCH_OPT_ADAM = 67,
+    TMA_DISPATCH_OPT_LOCAL_SCATTER_H64 = 68, TMA_DISPATCH_OPT_LOCAL_SCATTER_WIDE = 69,
+    /* flag on a forward or generic-gradient id: the grid is capped and the kernel loops over it */
+    TMA_DISPATCH_GRID_CAPPED = 256
+};
+int tma_debug_last_dispatch(int32_t *fwd_out, int32_t *grad_out, int32_t *opt_out);
 /* out8: sums since the last call of {policy_loss, value_sq_err, entropy, approx_kl, clipped, n_samples}, then the last
  * total grad norm and clip coefficient.  Synchronises `stream`. */
 int tma_ppo_pop_stats(void *workspace, double *out8_host, void *stream);

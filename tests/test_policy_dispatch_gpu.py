@@ -1,0 +1,491 @@
+"""Every specialisation the policy's three dispatchers can pick -- the forward (launch_fwd), the minibatch gradient (minibatch_grad_impl) and
+the optimizer step (tma_ppo_adam_step / _local) -- against an independent float64 reference (oracle/sb3_ref.py run on .double() copies of
+the exact f32 parameters and inputs), at the shapes where tile code breaks.  Each case names the branch it is meant to reach and asserts
+it through tma_debug_last_dispatch, so a threshold change cannot quietly move a case onto another kernel.
+
+Gradient comparison, per parameter segment s:  err_kernel,s <= K * err_torch32,s + F * max|g64,s|, where err_torch32 is the error of
+float32 torch CPU autograd on the same data (the calibration: what an honest f32 implementation of the same sums is off by).  Every
+gradient case also checks that the comparator REJECTS the float64 gradient of the same minibatch without its last row tile -- the
+tolerance is tight enough to see a dropped partial tile at that size.
+
+CASES is importable without a GPU: tests/test_policy_dispatch_table_cpu.py checks that every branch id of include/tma.h has a case."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import sb3_ref
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+# comparator constants, one pair for the whole file (f32 rows); bf16 forward rows are compared with the bf16-rounded emulation and get their own.
+# First MI355X run (K = 8, F = 2e-6): every gradient case used at most 0.82 of that budget (Basic, 21 x 64, 131 072 samples: the generic kernel's
+# float atomics); the forward rows at most 0.18.  With the constants below: at most 0.41, i.e. 2.4x headroom.  The dropped-tile reference
+# overshoots the same budget at least 129-fold (Box 6 x 64, 8 177 samples).  Worst err_kernel / err_torch32 over a case's segments, by
+# family: H = 64 kernels 3.1, f32 kt1 = 107 5.4, kt1 = 0 22.7, small7 26.7, kt1 = 2 31.9, kt1 = 11 127, generic 194, kt1 = 1 242 (the large
+# ones on segments where float32 autograd happens to be almost exact, so the F term carries them).
+K, F = 16.0, 4e-6
+K_BF, F_BF = 8.0, 4e-3  # (a sum that lands on a bf16 rounding boundary flips one activation by one bf16 ulp: test_bf16_gpu.py's 4e-3)
+CLIP_MARGIN = 2e-2  # |ratio - 1| kept this far from clip_range in float64 (tests/test_ppo_gpu.py's _rollout keeps 5e-3 in float32)
+
+# (entry, D, H, A, continuous, B or n, expected dispatch id: TMA_DISPATCH_ name without the prefix, "|GRID_CAPPED" where the grid is capped)
+# entries: grad (explicit indices) / grad_perm (Feistel permutation) / grad_noadv (normalize_advantage off) / grad_nodz1 (TMA_NO_DZ1_CACHE) /
+# grad_nodefer (TMA_NO_DEFER_W2, in a child process: read once per process) / grad_bf16 / grad_bf16x3 (dispatch only: their numerics are
+# test_bf16_gpu.py's and test_split3_gpu.py's) / fwd / fwd_bf16 / opt / opt_bf16 (tma_ppo_adam_step after a gradient of B samples) /
+# opt_local / opt_local_bf16 (tma_ppo_adam_step_local with last_count = B)
+_N_EDGES = (1, 15, 16, 17, 31, 32, 33)
+_FWD_SHAPES = [  # (D, H, A, cont, id) -- Discrete A = 2 / 16 and Box A = 1 / 32 among them
+    (4, 64, 5, False, "FWD_H64"), (4, 64, 16, False, "FWD_H64"),
+    (6, 128, 2, False, "FWD_F32_NTW2_DISCRETE"), (6, 192, 16, False, "FWD_F32_NTW3_DISCRETE"), (21, 256, 5, False, "FWD_F32_NTW4_DISCRETE"),
+    (8, 128, 1, True, "FWD_F32_NTW2_BOX"), (8, 192, 32, True, "FWD_F32_NTW3_BOX"), (105, 256, 8, True, "FWD_F32_NTW4_BOX"),
+    (21, 64, 3, False, "FWD_GENERIC_W1"), (6, 64, 4, True, "FWD_GENERIC_W1"),
+]
+_FWD_BF_SHAPES = [
+    (6, 128, 2, False, "FWD_BF16_NTW2_DISCRETE"), (6, 192, 16, False, "FWD_BF16_NTW3_DISCRETE"), (21, 256, 5, False, "FWD_BF16_NTW4_DISCRETE"),
+    (8, 128, 1, True, "FWD_BF16_NTW2_BOX"), (8, 192, 32, True, "FWD_BF16_NTW3_BOX"), (105, 256, 8, True, "FWD_BF16_NTW4_BOX"),
+]
+
+
+def _wide_grad_cases():
+    out = []
+    for H in (128, 192, 256):
+        w8 = H == 256
+        for cont, A in ((False, 5), (True, 3)):
+            for B in (113, 256, 1000, 1024, 1025, 33000):  # kt1 = 1: half groups up to 1024 samples, full row groups beyond
+                half = B <= 1024
+                ident = ("KT1_HALF_W8_DEFER" if half else "KT1_FULL_W8") if w8 else ("KT1_HALF_W4" if half else "KT1_FULL_W4")
+                out.append(("grad", 16, H, A, cont, B, "GRAD_F32_" + ident))
+            for D, B in ((17, 1000), (17, 2048), (32, 1024), (32, 1025)):  # kt1 = 2
+                half = B <= 1024
+                ident = ("KT2_HALF_W8_DEFER" if half else "KT2_FULL_W8") if w8 else ("KT2_HALF_W4" if half else "KT2_FULL_W4")
+                out.append(("grad", D, H, A + 1, cont, B, "GRAD_F32_" + ident))
+    return out
+
+
+CASES = (
+    # ---- gradient: H = 64 fast path (4, 64, 5, Discrete): one tile per wave up to 2048 samples, then the persistent eight-wave kernel
+    [("grad", 4, 64, 5, False, B, "GRAD_H64_SMALL") for B in (241, 255, 256, 2048)]
+    + [("grad", 4, 64, 5, False, B, "GRAD_H64") for B in (2049, 16385, 131072)]
+    + [("grad", 4, 64, 2, False, 1000, "GRAD_H64_SMALL"), ("grad", 16, 64, 16, False, 3000, "GRAD_H64"),
+       ("grad_perm", 4, 64, 5, False, 1000, "GRAD_H64_SMALL"), ("grad_noadv", 4, 64, 5, False, 300, "GRAD_H64_SMALL")]
+    # ---- gradient: generic float-atomic kernel (wpb = 4 from 512 tiles, fewer while the tile exceeds 156 KB; grid capped at 1024 blocks)
+    + [("grad", 4, 64, 5, False, B, "GRAD_GENERIC_W1") for B in (1, 2, 15, 17, 240)]
+    + [("grad", 21, 64, 3, False, 131072, "GRAD_GENERIC_W4|GRID_CAPPED"),  # Basic at the headline minibatch: grid-stride over float atomics
+       ("grad", 6, 64, 4, True, 8176, "GRAD_GENERIC_W1"), ("grad", 6, 64, 4, True, 8177, "GRAD_GENERIC_W4"),  # Box heads: 511 / 512 tiles
+       ("grad", 45, 64, 3, False, 65536, "GRAD_GENERIC_W4"),  # BrickBreak: 4096 tiles = exactly the 1024-block cap
+       ("grad", 105, 64, 8, True, 65552, "GRAD_GENERIC_W4|GRID_CAPPED"),  # Ant at 64 wide: 4097 tiles, one past the cap
+       ("grad", 500, 64, 3, False, 8200, "GRAD_GENERIC_W3"), ("grad", 800, 64, 1, True, 8200, "GRAD_GENERIC_W2"),
+       ("grad", 2000, 64, 2, False, 8200, "GRAD_GENERIC_W1"),  # (D 449..656 / 657..1072 / 1073..2384 at H = 64)
+       ("grad", 4, 320, 3, False, 300, "GRAD_GENERIC_W1"), ("grad", 4, 512, 32, True, 64, "GRAD_GENERIC_W1"),
+       ("grad", 4, 1024, 2, False, 40, "GRAD_GENERIC_W1"),
+       ("grad", 16, 128, 4, False, 112, "GRAD_GENERIC_W1"), ("grad", 16, 128, 4, False, 113, "GRAD_F32_KT1_HALF_W4"),  # 7 / 8 tiles
+       ("grad_perm", 21, 64, 3, False, 5000, "GRAD_GENERIC_W1"), ("grad_noadv", 21, 64, 3, False, 9000, "GRAD_GENERIC_W4")]
+    # ---- gradient: f32 column-parallel kernels
+    + _wide_grad_cases()
+    + [("grad", 21, 256, 3, False, 256, "GRAD_F32_KT2_HALF_W8_DEFER"),  # Basic at the reference's literal batch_size
+       ("grad", 16, 128, 16, False, 500, "GRAD_F32_KT1_HALF_W4"), ("grad", 32, 192, 32, True, 600, "GRAD_F32_KT2_HALF_W4"),
+       ("grad_perm", 16, 128, 4, True, 1000, "GRAD_F32_KT1_HALF_W4"), ("grad_noadv", 21, 256, 3, False, 2000, "GRAD_F32_KT2_FULL_W8")]
+    # small7: H = 256, 33..112 observations, <= 1024 samples (the reference's ant task at its literal batch), dW2 deferred
+    + [("grad", D, 256, A, cont, B, "GRAD_F32_SMALL7") for (D, A, cont) in ((33, 2, False), (105, 8, True), (112, 16, False))
+       for B in (256, 1000, 1024)]
+    + [("grad", 33, 256, 2, False, 113, "GRAD_F32_SMALL7"), ("grad_perm", 105, 256, 8, True, 700, "GRAD_F32_SMALL7"),
+       ("grad_noadv", 112, 256, 1, True, 500, "GRAD_F32_SMALL7")]
+    # kt1 = 107: 97..112 observations, Box head, H = 256, past the small7 range; dz1 cached or recomputed
+    + [("grad", D, 256, 8, True, B, "GRAD_F32_KT107_CACHED") for D in (97, 105, 112) for B in (1025, 33000)]
+    + [("grad_nodz1", 97, 256, 8, True, 1025, "GRAD_F32_KT107_RECOMPUTE"), ("grad_nodz1", 112, 256, 32, True, 33000, "GRAD_F32_KT107_RECOMPUTE"),
+       ("grad_perm", 105, 256, 8, True, 2000, "GRAD_F32_KT107_CACHED"), ("grad_noadv", 105, 256, 1, True, 1500, "GRAD_F32_KT107_CACHED")]
+    # kt1 = 11: 161..176 observations (Crawler's 172)
+    + [("grad", 161, 128, 4, False, 1025, "GRAD_F32_KT11_CACHED"), ("grad", 176, 192, 3, False, 2000, "GRAD_F32_KT11_CACHED"),
+       ("grad", 176, 256, 20, True, 33000, "GRAD_F32_KT11_CACHED"), ("grad", 172, 256, 2, False, 500, "GRAD_F32_KT11_CACHED"),
+       ("grad_nodz1", 161, 256, 6, True, 1500, "GRAD_F32_KT11_RECOMPUTE"), ("grad_nodz1", 176, 128, 2, False, 1025, "GRAD_F32_KT11_RECOMPUTE"),
+       ("grad_perm", 172, 256, 20, True, 2000, "GRAD_F32_KT11_CACHED"), ("grad_noadv", 172, 128, 16, False, 700, "GRAD_F32_KT11_CACHED")]
+    # runtime width (kt1 = 0)
+    + [("grad", 33, 128, 3, False, 500, "GRAD_F32_KT0"), ("grad", 96, 256, 4, True, 2000, "GRAD_F32_KT0"),
+       ("grad", 113, 256, 4, True, 1025, "GRAD_F32_KT0"), ("grad", 113, 256, 2, False, 1000, "GRAD_F32_KT0"),
+       ("grad", 177, 256, 5, False, 1000, "GRAD_F32_KT0"), ("grad", 33, 256, 2, False, 1025, "GRAD_F32_KT0"),
+       ("grad_perm", 60, 128, 4, False, 600, "GRAD_F32_KT0"), ("grad_noadv", 60, 192, 1, True, 800, "GRAD_F32_KT0")]
+    # TMA_NO_DEFER_W2: eight-wave half groups accumulate dW2 in the slabs; the Ant literal batch leaves small7 for the two-pass kernel
+    + [("grad_nodefer", 16, 256, 5, False, 1000, "GRAD_F32_KT1_HALF_W8_SLAB"), ("grad_nodefer", 21, 256, 3, False, 256, "GRAD_F32_KT2_HALF_W8_SLAB"),
+       ("grad_nodefer", 105, 256, 8, True, 256, "GRAD_F32_KT107_CACHED")]
+    + [("grad_bf16", 6, 256, 5, False, 1000, "GRAD_BF16"), ("grad_bf16x3", 6, 256, 5, False, 4096, "GRAD_BF16X3")]
+    # ---- forward: every launch_fwd leaf at the tile edges; the grid caps (wide: 4096 groups of 32 rows; generic: 8192 blocks)
+    + [("fwd", D, H, A, cont, n, ident) for (D, H, A, cont, ident) in _FWD_SHAPES for n in _N_EDGES]
+    + [("fwd_bf16", D, H, A, cont, n, ident) for (D, H, A, cont, ident) in _FWD_BF_SHAPES for n in _N_EDGES]
+    + [("fwd", 4, 64, 5, False, 131072 + 17, "FWD_H64"), ("fwd", 6, 128, 3, True, 131072 + 17, "FWD_F32_NTW2_BOX|GRID_CAPPED"),
+       ("fwd", 6, 256, 5, False, 131072, "FWD_F32_NTW4_DISCRETE"), ("fwd_bf16", 6, 128, 4, False, 131072 + 17, "FWD_BF16_NTW2_DISCRETE|GRID_CAPPED"),
+       ("fwd", 4, 64, 2, True, 20000, "FWD_GENERIC_W4"), ("fwd", 4, 64, 2, True, 8192 * 4 * 16 + 17, "FWD_GENERIC_W4|GRID_CAPPED"),
+       ("fwd", 200, 64, 3, False, 16400, "FWD_GENERIC_W2"), ("fwd", 400, 64, 3, False, 8192 * 16 + 17, "FWD_GENERIC_W1|GRID_CAPPED")]
+    # ---- optimizer: every tma_ppo_adam_step / _local leaf
+    + [("opt", 4, 64, 5, False, 256, "OPT_SCATTER_H64"), ("opt", 16, 128, 4, False, 256, "OPT_SCATTER_WIDE"),
+       ("opt", 8, 192, 3, True, 256, "OPT_SCATTER_WIDE"), ("opt", 105, 256, 8, True, 256, "OPT_SCATTER_WIDE"),
+       ("opt_bf16", 6, 256, 5, False, 1000, "OPT_SCATTER_WIDE"),
+       ("opt", 6, 64, 4, True, 256, "OPT_SMALL"), ("opt", 21, 64, 3, False, 256, "OPT_SMALL"),  # (P <= 10240: registers; beyond: a loop)
+       ("opt", 8, 320, 4, False, 256, "OPT_ADAM"),
+       ("opt_local", 4, 64, 5, False, 256, "OPT_LOCAL_SCATTER_H64"), ("opt_local", 4, 64, 5, False, 255, "OPT_SCATTER_H64"),
+       ("opt_local", 16, 128, 4, False, 128, "OPT_LOCAL_SCATTER_WIDE"), ("opt_local", 16, 128, 4, False, 127, "OPT_SCATTER_WIDE"),
+       ("opt_local", 105, 256, 8, True, 256, "OPT_LOCAL_SCATTER_WIDE"), ("opt_local", 16, 256, 5, False, 2000, "OPT_LOCAL_SCATTER_WIDE"),
+       ("opt_local", 21, 64, 3, False, 256, "OPT_SMALL"), ("opt_local_bf16", 6, 256, 5, False, 1000, "OPT_LOCAL_SCATTER_WIDE")]
+)
+
+
+def dispatch_ids():
+    """TMA_DISPATCH_<NAME> -> value, parsed from include/tma.h."""
+    text = open(os.path.join(ROOT, "include", "tma.h")).read()
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"\bTMA_DISPATCH_([A-Z0-9_]+)\s*=\s*(\d+)", text)}
+
+
+def expected_value(name):
+    ids = dispatch_ids()
+    v = 0
+    for part in name.split("|"):
+        v |= ids[part]
+    return v
+
+
+def _case_id(c):
+    entry, D, H, A, cont, B, ident = c
+    return f"{entry}-{D}x{H}x{A}{'C' if cont else 'D'}-{B}"
+
+
+def _cases(prefix):
+    return [pytest.param(*c, id=_case_id(c)) for c in CASES if c[0].split("_")[0] == prefix]
+
+
+def _last_dispatch():
+    from three_mlagents_amd import _lib
+
+    f, g, o = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    _lib.check(_lib.lib().tma_debug_last_dispatch(C.byref(f), C.byref(g), C.byref(o)))
+    return f.value, g.value, o.value
+
+
+def _name(v):
+    names = [k for k, x in dispatch_ids().items() if x == v & 0xFF and k != "GRID_CAPPED"]
+    return "|".join(names + (["GRID_CAPPED"] if v & 256 else []))
+
+
+def _policy(D, H, A, cont, dtype="f32", seed=5):
+    if dtype == "f32":
+        from test_ppo_gpu import _policy as make
+    else:
+        from test_bf16_gpu import _policies as make
+        if dtype == "bf16x3":
+            from three_mlagents_amd.ppo import HipActorCriticPolicy
+
+            pol0, sd = make(D, H, A, cont, seed)
+            pol = HipActorCriticPolicy(D, A, cont, H, torch.device("cuda", 0), seed=seed, mfma_dtype="bf16x3")
+            pol.load_state_dict(sd)
+            return pol, sd
+    return make(D, H, A, cont, seed)
+
+
+def _rows(D, A, cont, total, seed):
+    g = torch.Generator().manual_seed(seed)
+    obs = torch.randn(total, D, generator=g)
+    act = torch.randn(total, A, generator=g) * 0.7 if cont else torch.randint(0, A, (total,), generator=g, dtype=torch.int32)
+    return g, obs, act
+
+
+def _sd64(sd):
+    return {k: v.detach().double() for k, v in sd.items()}
+
+
+def _rollout(sd, D, A, cont, T, N, seed=0):
+    """(T, N, ...) rollout buffers whose old log-probabilities keep every sample CLIP_MARGIN away from the clip boundary in float64."""
+    g, flat, act = _rows(D, A, cont, T * N, seed)
+    with torch.no_grad():
+        _, lp64, _ = sb3_ref.evaluate_actions(_sd64(sd), flat.double(), act.double() if cont else act)
+    old = (lp64 + 0.25 * torch.randn(T * N, generator=g, dtype=torch.float64)).float()
+    for _ in range(10):
+        near = (((torch.exp(lp64 - old.double()) - 1.0).abs() - 0.2).abs() < CLIP_MARGIN)
+        if not near.any():
+            break
+        old = torch.where(near, old + 0.05, old)
+    assert not near.any()
+    adv, ret = torch.randn(T * N, generator=g), torch.randn(T * N, generator=g)
+    # the kernels read (T, N, ...) buffers with the flat index f = i*T + t: store row f at [t, i]
+    to_tn = lambda x: x.reshape(N, T, *x.shape[1:]).transpose(0, 1).contiguous()  # noqa: E731
+    return dict(obs=to_tn(flat), actions=to_tn(act), old_lp=to_tn(old), adv=to_tn(adv), ret=to_tn(ret)), dict(obs=flat, actions=act, old_lp=old, adv=adv, ret=ret)
+
+
+def _grads(sd, rows, idx, dtype, hp):
+    """(grads in SB3 naming, stats) of the PPO loss over rows[idx] in `dtype` (float64: the reference; float32: the calibration)."""
+    p = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
+    if len(idx) == 0:
+        return {k: torch.zeros_like(v) for k, v in p.items()}, None
+    cont = "log_std" in sd
+    x = {k: v[idx] for k, v in rows.items()}
+    acts = x["actions"].to(dtype) if cont else x["actions"]
+    loss, stats = sb3_ref.ppo_loss(p, x["obs"].to(dtype), acts, x["old_lp"].to(dtype), x["adv"].to(dtype), x["ret"].to(dtype), **hp)
+    loss.backward()
+    return {k: v.grad.detach() for k, v in p.items()}, stats
+
+
+HP = dict(clip_range=0.2, ent_coef=0.01, vf_coef=0.5, normalize_advantage=True)
+
+
+def _segment_errors(g, ref, cal):
+    """per segment: (err of g against ref, err of the calibration against ref, max |ref|)"""
+    return {k: (float((g[k].double() - ref[k]).abs().max()), float((cal[k].double() - ref[k]).abs().max()), float(ref[k].abs().max())) for k in ref}
+
+
+def _rejects(errs):
+    return any(e > K * e32 + F * m for e, e32, m in errs.values())
+
+
+def _run_child(request, env):
+    """Run this very case in a child process with `env` added (switches read once per process)."""
+    e = dict(os.environ, **env)
+    node = request.node.nodeid.split("::", 1)[1]
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", f"{os.path.join(HERE, os.path.basename(__file__))}::{node}"],
+                       cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-2000:])
+
+
+@pytest.mark.parametrize("entry,D,H,A,cont,B,ident", _cases("grad"))
+def test_gradient_branch_against_float64(entry, D, H, A, cont, B, ident, monkeypatch, request, record_property):
+    from test_ppo_gpu import _hip_grad
+
+    if entry == "grad_nodefer" and os.environ.get("TMA_NO_DEFER_W2") != "1":
+        return _run_child(request, {"TMA_NO_DEFER_W2": "1"})
+    if entry == "grad_nodz1":
+        monkeypatch.setenv("TMA_NO_DZ1_CACHE", "1")
+    dtype = {"grad_bf16": "bf16", "grad_bf16x3": "bf16x3"}.get(entry, "f32")
+    hp = dict(HP, normalize_advantage=entry != "grad_noadv")
+    start = 3
+    T = 16
+    N = (start + B + T - 1) // T + 1
+    pol, sd = _policy(D, H, A, cont, dtype)
+    bufs, rows = _rollout(sd, D, A, cont, T, N, seed=B % 7919)
+    total = T * N
+    if entry == "grad_perm":
+        from three_mlagents_amd import _lib
+
+        perm_np = np.zeros(total, dtype=np.int64)
+        _lib.check(_lib.lib().tma_ppo_permutation(77, 3, total, perm_np.ctypes.data_as(C.c_void_p)))
+        perm = torch.from_numpy(perm_np)
+        grad, st, _ = _hip_grad(pol, bufs, T, N, None, start, B, hp, perm=(77, 3))
+    else:
+        perm = torch.randperm(total, generator=torch.Generator().manual_seed(B))
+        grad, st, _ = _hip_grad(pol, bufs, T, N, perm, start, B, hp)
+    got = _last_dispatch()[1]
+    assert got == expected_value(ident), (ident, _name(got))
+    idx = perm[start:start + B]
+    g = pol.named_from_flat(grad)
+    if dtype != "f32":  # (numerics: test_bf16_gpu.py / test_split3_gpu.py)
+        assert all(torch.isfinite(v).all() for v in g.values()) and st[5] == B
+        return
+    g64, s64 = _grads(sd, rows, idx, torch.float64, hp)
+    g32, _ = _grads(sd, rows, idx, torch.float32, hp)
+    errs = _segment_errors(g, g64, g32)
+    drop = B % 16 or 16
+    gdrop, _ = _grads(sd, rows, idx[:B - drop], torch.float64, hp)
+    errs_drop = _segment_errors(gdrop, g64, g32)
+    budget = max(e / (K * e32 + F * m) if (e32 or m) else (0.0 if e == 0 else math.inf) for e, e32, m in errs.values())
+    record_property("grad_errs", repr({"budget": budget, "errs": errs, "drop": {k: v[0] for k, v in errs_drop.items()}}))
+    # statistics: sums of {policy_loss, value_sq_err, entropy, approx_kl, clipped, n} (the last two exact); no optimizer step on this workspace
+    n = st[5]
+    stats = ((st[0] / n, s64["policy_loss"], "policy_loss"), (st[1] / n, s64["value_loss"], "value_loss"),
+             (-st[2] / n, s64["entropy_loss"], "entropy_loss"), (st[3] / n, s64["approx_kl"], "approx_kl"))
+    record_property("stats_errs", repr({what: abs(got_v - ref_v) / max(1.0, abs(ref_v)) for got_v, ref_v, what in stats}))
+    assert n == B
+    assert st[4] == round(s64["clip_fraction"] * B), (st[4], s64["clip_fraction"] * B)
+    for got_v, ref_v, what in stats:
+        assert abs(got_v - ref_v) <= 2e-6 * max(1.0, abs(ref_v)), (what, got_v, ref_v)
+    assert st[6] == 0.0 and st[7] == 0.0
+    bad = {k: v for k, v in errs.items() if v[0] > K * v[1] + F * v[2]}
+    assert not bad, bad
+    assert _rejects(errs_drop), ("the comparator does not see the last row tile dropped", errs_drop)
+
+
+def _emulated_forward64(sd, obs):
+    from test_bf16_gpu import _bf
+
+    def net(prefix, head):
+        h = _bf(obs).double()
+        for i in (0, 2):
+            h = _bf(torch.tanh(h @ _bf(sd[f"mlp_extractor.{prefix}.{i}.weight"]).double().t() + sd[f"mlp_extractor.{prefix}.{i}.bias"].double()).float()).double()
+        return h @ _bf(sd[f"{head}.weight"]).double().t() + sd[f"{head}.bias"].double()
+
+    return net("policy_net", "action_net"), net("value_net", "value_net").squeeze(-1)
+
+
+def _logp(out, sd, a, cont):
+    if cont:
+        ls = sd["log_std"].to(out.dtype)
+        return (-((a.to(out.dtype) - out) ** 2) / (2 * torch.exp(2 * ls)) - ls - 0.5 * math.log(2 * math.pi)).sum(dim=1)
+    return torch.log_softmax(out, dim=1).gather(1, a.long().view(-1, 1)).squeeze(1)
+
+
+@pytest.mark.parametrize("entry,D,H,A,cont,n,ident", _cases("fwd"))
+def test_forward_branch_against_float64(entry, D, H, A, cont, n, ident, record_property):
+    from three_mlagents_amd import _lib
+
+    bf = entry == "fwd_bf16"
+    pol, sd = _policy(D, H, A, cont, "bf16" if bf else "f32")
+    g = torch.Generator().manual_seed(n)
+    obs = torch.randn(n, D, generator=g)
+    sd64 = _sd64(sd)
+    if bf:  # reference: the same rounding points as the kernel (bf16 operands) in float64; calibration: the same in float32
+        from test_bf16_gpu import _emulated_forward
+
+        out64, v64 = _emulated_forward64(sd, obs)
+        out32, v32 = _emulated_forward(sd, obs)
+        k, f = K_BF, F_BF
+    else:
+        out64, v64 = sb3_ref.forward(sd64, obs.double())
+        out32, v32 = sb3_ref.forward(sd, obs)
+        k, f = K, F
+
+    def close(got, ref, cal, what):
+        e, e32, m = float((got.double() - ref).abs().max()), float((cal.double() - ref).abs().max()), float(ref.abs().max())
+        record_property(what, repr((e, e32, m)))
+        assert e <= k * e32 + f * max(m, 1.0), (what, e, e32, m)
+
+    def check_id():
+        got = _last_dispatch()[0]
+        assert got == expected_value(ident), (ident, _name(got))
+
+    a, v, lp = pol.act(obs.cuda(), deterministic=True)
+    check_id()
+    close(v.cpu(), v64, v32, "values")
+    if cont:
+        close(a.cpu(), out64, out32, "mean")
+    else:
+        top2 = out64.topk(2, dim=1).values
+        clear = (top2[:, 0] - top2[:, 1]) > (2e-2 if bf else 1e-4)  # rows whose argmax is not a near-tie
+        assert torch.equal(a.cpu().long()[clear], out64.argmax(dim=1)[clear])
+    close(lp.cpu(), _logp(out64, sd64, a.cpu(), cont), _logp(out32, sd, a.cpu(), cont), "logp_det")
+    a, v2, lp = pol.act(obs.cuda(), rng_seed=9, rng_step=3, deterministic=False)
+    check_id()
+    close(lp.cpu(), _logp(out64, sd64, a.cpu(), cont), _logp(out32, sd, a.cpu(), cont), "logp_sampled")
+    close(pol.predict_values(obs.cuda()).cpu(), v64, v32, "predict_values")
+    check_id()
+    trunc = (torch.rand(n, generator=g) < 0.3).to(torch.uint8)
+    rew = torch.randn(n, generator=g)
+    obs_d, trunc_d, rew_d = obs.cuda(), trunc.cuda(), rew.cuda()  # (held: the launch is asynchronous)
+    _lib.check(_lib.lib().tma_policy_bootstrap(_lib.ptr(pol.params), C.byref(pol.dims), _lib.ptr(obs_d), _lib.ptr(trunc_d), n, 0.99,
+                                               _lib.ptr(rew_d), _lib.stream_ptr()))
+    check_id()
+    t = trunc.bool()
+    close(rew_d.cpu(), torch.where(t, rew.double() + 0.99 * v64, rew.double()), torch.where(t, rew + 0.99 * v32, rew), "bootstrap")
+
+
+@pytest.mark.parametrize("entry,D,H,A,cont,B,ident", _cases("opt"))
+def test_optimizer_branch_against_float64_adam(entry, D, H, A, cont, B, ident, record_property):
+    """The same kernel-produced gradient goes to the device step and to float64 torch.optim.Adam(eps=1e-5) + clip_grad_norm_: three steps
+    with the clip engaged, three without, three with grad_scale = 0.5 (tma_ppo_adam_step only); parameters and both moments compared.
+    After every run tma_policy_sync must change no bit (the step kept every derived copy consistent).
+    Also measured against IEEE float32 Adam (torch CPU, foreach=False, on the device's own clipped gradient), in units of 2^-23 (|p| + lr):
+    see the figure next to the assertion."""
+    from test_ppo_gpu import _hip_grad
+    from three_mlagents_amd import _lib
+
+    local = entry.startswith("opt_local")
+    dtype = "bf16" if entry.endswith("bf16") else "f32"
+    T = 16
+    N = (B + T - 1) // T + 1
+    runs = [(0.05, 1.0), (1e3, 1.0)] + ([] if local else [(0.05, 0.5)])
+    lr, b1, b2, eps = 3e-4, 0.9, 0.999, 1e-5
+    for max_norm, scale in runs:
+        pol, sd = _policy(D, H, A, cont, dtype)
+        P = pol.n_trainable
+        dev = pol.params.device
+        m = torch.zeros(P, device=dev)
+        v = torch.zeros(P, device=dev)
+        p64 = torch.nn.Parameter(pol.params[:P].detach().cpu().double().clone())
+        opt64 = torch.optim.Adam([p64], lr=lr, betas=(b1, b2), eps=eps)
+        p32 = torch.nn.Parameter(pol.params[:P].detach().cpu().clone())
+        opt32 = torch.optim.Adam([p32], lr=lr, betas=(b1, b2), eps=eps, foreach=False)
+        for step in range(1, 4):
+            bufs, _ = _rollout(pol.state_dict(), D, A, cont, T, N, seed=step)
+            grad, _, ws = _hip_grad(pol, bufs, T, N, torch.arange(T * N), 0, B, HP)
+            g = grad.detach().cpu().clone()
+            if local:
+                rc = _lib.lib().tma_ppo_adam_step_local(_lib.ptr(pol.params), _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v), C.byref(pol.dims), step, lr, b1, b2,
+                                                        eps, max_norm, _lib.ptr(ws), _lib.stream_ptr(), B)
+            else:
+                rc = _lib.lib().tma_ppo_adam_step(_lib.ptr(pol.params), _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v), C.byref(pol.dims), step, lr, b1, b2,
+                                                  eps, max_norm, scale, _lib.ptr(ws), _lib.stream_ptr())
+            got = _last_dispatch()[2]
+            _lib.check(rc)
+            assert got == expected_value(ident), (ident, _name(got))
+            out = (C.c_double * 8)()
+            _lib.check(_lib.lib().tma_ppo_pop_stats(_lib.ptr(ws), out, _lib.stream_ptr()))
+            assert float(grad.abs().max()) == 0.0  # re-zeroed for the next minibatch
+            # float64 reference
+            p64.grad = g.double() * scale
+            norm64 = float(torch.nn.utils.clip_grad_norm_([p64], max_norm))
+            coef64 = min(1.0, max_norm / (norm64 + 1e-6))
+            opt64.step()
+            # IEEE float32 Adam on the device's own clipped gradient (the form the scatter kernels approximate with hardware sqrt / rcp)
+            p32.grad = (g * np.float32(scale)) * np.float32(out[7])
+            opt32.step()
+            pd = pol.params[:P].detach().cpu()
+            st64 = opt64.state[p64]
+            e_p = float(((pd.double() - p64.detach()).abs() / (2.0 ** -19 * p64.detach().abs() + 4e-5 * lr)).max())
+            e_ieee = float(((pd - p32.detach()).abs() / (2.0 ** -23 * (p32.detach().abs() + lr))).max())
+            e_m = float((m.cpu().double() - st64["exp_avg"]).abs().max()) / max(float(st64["exp_avg"].abs().max()), 1e-30)
+            e_v = float((v.cpu().double() - st64["exp_avg_sq"]).abs().max()) / max(float(st64["exp_avg_sq"].abs().max()), 1e-30)
+            record_property(f"opt_{max_norm}_{scale}_{step}", repr(dict(e_p=e_p, ieee_per_lr=e_ieee, e_m=e_m, e_v=e_v, norm=(out[6], norm64), coef=(out[7], coef64))))
+            assert abs(out[6] - norm64) <= 1e-6 * norm64, (out[6], norm64)
+            assert abs(out[7] - coef64) <= 1e-6, (out[7], coef64)
+            assert (coef64 < 1.0) == (max_norm < 1.0), "clip engagement is not what the run is meant to test"
+            assert e_p <= 1.0, (step, e_p)  # |p - p64| <= 2^-19 |p64| + 4e-5 lr, element by element (observed: 0.32 of it, step 2)
+            # (the kernels form 1 - beta1 and 1 - beta2 in float32 from float32 betas: 1 - 0.999f = 0.00099998713, 1.29e-5 off 0.001 -- exp_avg_sq
+            #  carries that relative offset, exp_avg 2.4e-7; observed 1.30e-5 / 3.8e-7.  In the parameters it is <= 6.4e-6 of lr per step)
+            assert e_m <= 1e-6 and e_v <= 2.6e-5, (step, e_m, e_v)
+            # against IEEE float32 Adam, in units of 2^-23 (|p| + lr): observed <= 102 on the wide scatter (hardware sqrt / rcp) and <= 101 on the
+            # IEEE-arithmetic kernels alike -- the difference is the float32 1 - beta2 above, not the hardware square root / reciprocal
+            assert e_ieee <= 256, (step, e_ieee)
+        after = pol.params.clone()
+        _lib.check(_lib.lib().tma_policy_sync(_lib.ptr(pol.params), C.byref(pol.dims), _lib.stream_ptr()))
+        assert torch.equal(after, pol.params), "the optimizer step left a derived copy out of date"
+
+
+@pytest.mark.parametrize("D,H,A,cont", [(2500, 64, 3, False), (600, 1024, 2, True), (2100, 256, 4, False)])
+def test_accepted_but_unrunnable_shapes_are_refused_by_every_entry_point(D, H, A, cont):
+    """check_dims accepts these shapes (obs_dim <= 4096, hidden <= 1024), but one wave's LDS tile of the generic kernels does not fit:
+    every entry point must return TMA_ERR_INVALID with a message before it launches anything."""
+    from three_mlagents_amd import _lib
+    from three_mlagents_amd.ppo import HipActorCriticPolicy
+
+    L = _lib.lib()
+    pol = HipActorCriticPolicy(D, A, cont, H, torch.device("cuda", 0), seed=1)
+    n, T, N = 40, 4, 10
+    dev = pol.params.device
+    obs = torch.randn(n, D, device=dev)
+    acts = torch.zeros((n, A) if cont else (n,), dtype=torch.float32 if cont else torch.int32, device=dev)
+    vals, logp, rew = torch.zeros(n, device=dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    trunc = torch.ones(n, dtype=torch.uint8, device=dev)
+    s = _lib.stream_ptr()
+    calls = {
+        "act": lambda: L.tma_policy_act(_lib.ptr(pol.params), C.byref(pol.dims), _lib.ptr(obs), n, 1, 2, 0, 0, _lib.ptr(acts), _lib.ptr(vals), _lib.ptr(logp), s),
+        "act_bootstrap": lambda: L.tma_policy_act_bootstrap(_lib.ptr(pol.params), C.byref(pol.dims), _lib.ptr(obs), n, 1, 2, 0, _lib.ptr(acts), _lib.ptr(vals),
+                                                            _lib.ptr(logp), _lib.ptr(obs), _lib.ptr(trunc), 0.99, _lib.ptr(rew), s),
+        "values": lambda: L.tma_policy_values(_lib.ptr(pol.params), C.byref(pol.dims), _lib.ptr(obs), n, _lib.ptr(vals), s),
+        "bootstrap": lambda: L.tma_policy_bootstrap(_lib.ptr(pol.params), C.byref(pol.dims), _lib.ptr(obs), _lib.ptr(trunc), n, 0.99, _lib.ptr(rew), s),
+    }
+    for name, call in calls.items():
+        assert call() == _lib.TMA_ERR_INVALID, name
+        assert "LDS" in _lib.last_error(), (name, _lib.last_error())
+        assert _last_dispatch()[0] == 0, name
+    rv = _lib.Rollout(_lib.ptr(obs), _lib.ptr(acts), _lib.ptr(logp), _lib.ptr(vals), _lib.ptr(rew), T, N)
+    mb = _lib.Minibatch(None, 1, 0, 0, n)
+    hp = _lib.PPOHParams(0.2, 0.01, 0.5, 1)
+    grad = torch.zeros(pol.n_trainable, device=dev)
+    ws = torch.zeros(int(L.tma_ppo_workspace_bytes(C.byref(pol.dims))), dtype=torch.uint8, device=dev)
+    rc = L.tma_ppo_minibatch_grad(_lib.ptr(pol.params), C.byref(pol.dims), C.byref(rv), C.byref(mb), C.byref(hp), _lib.ptr(grad), _lib.ptr(ws), s)
+    assert rc == _lib.TMA_ERR_INVALID and "LDS" in _lib.last_error(), _lib.last_error()
+    assert _last_dispatch()[1] == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(vals).all() and float(rew.abs().max()) == 0.0  # nothing ran

@@ -1885,6 +1885,9 @@ static int enter(const tma_policy_dims *d) {
     return TMA_OK;
 }
 
+// what the calling thread's last call of each dispatcher chose (tma_debug_last_dispatch): set where the dispatcher decides, before it launches
+static thread_local int32_t g_disp_fwd = TMA_DISPATCH_NONE, g_disp_grad = TMA_DISPATCH_NONE, g_disp_opt = TMA_DISPATCH_NONE;
+
 static int fwd_smem_bytes(const PLayout &L, int wpb) {
     const int ldx = ((L.D + 3) & ~3) + 2, ld = L.H + 2;
     return wpb * (16 * (ldx + 2 * ld) + 32) * 4;
@@ -2299,11 +2302,15 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
                       int deterministic, void *actions, float *values, float *logp, const uint8_t *trunc, float gamma, float *rewards,
                       hipStream_t s) {
     const PLayout L = layout_of(d);
+    g_disp_fwd = TMA_DISPATCH_NONE;
+    const int32_t capped = ceil_div(n, 32) > 4096 ? TMA_DISPATCH_GRID_CAPPED : 0;  // (the column-parallel kernels: 4096 groups of 32 rows, then grid-stride)
     if (L.img_pi >= 0) {
+        g_disp_fwd = TMA_DISPATCH_FWD_H64;
         if constexpr (MODE == 2) return launch_fwd_h64<2>(params, L, nullptr, n, 0, 0, 0, 1, nullptr, nullptr, nullptr, obs, trunc, gamma, rewards, s);
         else return launch_fwd_h64<MODE>(params, L, obs, n, seed, step, env_offset, deterministic, actions, values, logp, nullptr, nullptr, 0.0f, nullptr, s);
     }
     if (L.bf16) {
+        g_disp_fwd = (d->continuous ? TMA_DISPATCH_FWD_BF16_NTW2_BOX : TMA_DISPATCH_FWD_BF16_NTW2_DISCRETE) + (L.H / 64 - 2) | capped;
         const int smemw = fwd_wide_bf_smem_bytes(L.D, L.H);
         int64_t groups = ceil_div(n, 32);
         if (groups > 4096) groups = 4096;
@@ -2321,6 +2328,7 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
         return TMA_OK;
     }
     if ((L.H == 128 || L.H == 192 || L.H == 256) && fwd_wide_smem_bytes(L) <= 160 * 1024) {
+        g_disp_fwd = (d->continuous ? TMA_DISPATCH_FWD_F32_NTW2_BOX : TMA_DISPATCH_FWD_F32_NTW2_DISCRETE) + (L.H / 64 - 2) | capped;
         const int smemw = fwd_wide_smem_bytes(L);
         int64_t groups = ceil_div(n, 32);
         if (groups > 4096) groups = 4096;
@@ -2341,7 +2349,10 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
     int wpb = tiles >= 1024 ? 4 : 1;  // small batches: one wave per block so every CU gets work
     while (wpb > 1 && fwd_smem_bytes(L, wpb) > 64 * 1024) wpb >>= 1;
     const int smem = fwd_smem_bytes(L, wpb);
+    // (check_dims accepts up to 4096 observations and 1024 hidden units: refuse here, before any launch, what one wave's tile cannot hold)
+    if (smem > 160 * 1024) return fail(TMA_ERR_INVALID, "policy too wide for the forward kernel's LDS-resident tile (obs_dim %d, hidden %d: needs %d bytes)", L.D, L.H, smem);
     int64_t blocks = ceil_div(tiles, wpb);
+    g_disp_fwd = (wpb == 4 ? TMA_DISPATCH_FWD_GENERIC_W4 : (wpb == 2 ? TMA_DISPATCH_FWD_GENERIC_W2 : TMA_DISPATCH_FWD_GENERIC_W1)) | (blocks > 8192 ? TMA_DISPATCH_GRID_CAPPED : 0);
     if (blocks > 8192) blocks = 8192;
     if (d->continuous) {
         auto k = policy_fwd_kernel<true, MODE>;
@@ -2405,6 +2416,7 @@ int tma_policy_sync(float *params, const tma_policy_dims *d, void *stream) {
 
 int tma_policy_act(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, uint32_t rng_seed, uint32_t rng_step,
                    uint32_t env_offset, int deterministic, void *actions_out, float *values_out, float *logp_out, void *stream) {
+    g_disp_fwd = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !obs || !actions_out || !values_out || !logp_out) return fail(TMA_ERR_INVALID, "tma_policy_act: null buffer");
@@ -2416,15 +2428,18 @@ int tma_policy_act(const float *params, const tma_policy_dims *d, const float *o
 int tma_policy_act_bootstrap(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, uint32_t rng_seed, uint32_t rng_step,
                              uint32_t env_offset, void *actions_out, float *values_out, float *logp_out, const float *prev_terminal_obs,
                              const uint8_t *prev_truncated, double gamma, float *prev_rewards_inout, void *stream) {
+    g_disp_fwd = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !obs || !actions_out || !values_out || !logp_out) return fail(TMA_ERR_INVALID, "tma_policy_act_bootstrap: null buffer");
     if (n < 1) return fail(TMA_ERR_INVALID, "tma_policy_act_bootstrap: n must be >= 1");
     const PLayout L = layout_of(d);
     const bool boot = prev_terminal_obs && prev_truncated && prev_rewards_inout;
-    if (L.img_pi >= 0)  // one launch: bootstrap of the previous step folded into this step's forward
+    if (L.img_pi >= 0) {  // one launch: bootstrap of the previous step folded into this step's forward
+        g_disp_fwd = TMA_DISPATCH_FWD_H64;
         return launch_fwd_h64<0>(params, L, obs, n, rng_seed, rng_step, env_offset, 0, actions_out, values_out, logp_out, boot ? prev_terminal_obs : nullptr,
                                  boot ? prev_truncated : nullptr, (float)gamma, boot ? prev_rewards_inout : nullptr, (hipStream_t)stream);
+    }
     if (boot) {
         rc = launch_fwd<2>(params, d, prev_terminal_obs, n, 0, 0, 0, 1, nullptr, nullptr, nullptr, prev_truncated, (float)gamma, prev_rewards_inout,
                            (hipStream_t)stream);
@@ -2434,6 +2449,7 @@ int tma_policy_act_bootstrap(const float *params, const tma_policy_dims *d, cons
 }
 
 int tma_policy_values(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *values_out, void *stream) {
+    g_disp_fwd = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !obs || !values_out) return fail(TMA_ERR_INVALID, "tma_policy_values: null buffer");
@@ -2443,6 +2459,7 @@ int tma_policy_values(const float *params, const tma_policy_dims *d, const float
 
 int tma_policy_bootstrap(const float *params, const tma_policy_dims *d, const float *terminal_obs, const uint8_t *truncated, int64_t n, double gamma,
                          float *rewards_inout, void *stream) {
+    g_disp_fwd = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !terminal_obs || !truncated || !rewards_inout) return fail(TMA_ERR_INVALID, "tma_policy_bootstrap: null buffer");
@@ -2453,6 +2470,7 @@ int tma_policy_bootstrap(const float *params, const tma_policy_dims *d, const fl
 // fold (H = 64 fast path only): the previous minibatch's optimizer step, done in the prologue of this gradient launch (AdamFold)
 static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_minibatch *mbi, const tma_ppo_hparams *hp,
                                float *grad, void *workspace, void *stream, const AdamFold *fold, int overwrite, const PeerPush *push = nullptr) {
+    g_disp_grad = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !rb || !mbi || !hp || !grad || !workspace) return fail(TMA_ERR_INVALID, "tma_ppo_minibatch_grad: null argument");
@@ -2511,6 +2529,7 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
     }
     if (h64) {
         // register-accumulating persistent kernel (tma_h64.hip) + deterministic slab reduction
+        g_disp_grad = tiles <= H64_BLOCKS ? TMA_DISPATCH_GRAD_H64_SMALL : TMA_DISPATCH_GRAD_H64;  // (tma_launch_grad_h64: one tile per wave up to 2048 samples)
         float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
         int blocks4 = 0;
         int lrc;
@@ -2526,6 +2545,7 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
     }
     if (fold || overwrite || push) return fail(TMA_ERR_INVALID, "internal: folded optimizer step outside the H = 64 fast path");
     if (L.bf16) {  // column-parallel bf16-MFMA kernel (tma_bf16.hip) + deterministic slab reduction
+        g_disp_grad = TMA_DISPATCH_GRAD_BF16;
         if ((int64_t)rb->T * rb->N * L.D >= (int64_t)1 << 31)  // (its observation gather indexes the buffer with 32-bit arithmetic)
             return fail(TMA_ERR_INVALID, "bf16 update: T * N * obs_dim = %lld exceeds 2^31", (long long)((int64_t)rb->T * rb->N * L.D));
         float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
@@ -2540,6 +2560,7 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
         return TMA_OK;
     }
     if (wide_f32 && tma_split3_eligible(L, mbi->count)) {  // mfma_dtype = 2: the same update on the bf16 MFMA, every operand as three bf16 terms
+        g_disp_grad = TMA_DISPATCH_GRAD_BF16X3;
         float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
         int n_pi = 0, n_vf = 0, lrc;
         {
@@ -2560,7 +2581,9 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
         // half groups with dW1 in registers (7 k-tiles: the eight-wave half-group kernel defers dW2, so it has them) -- that width took the
         // runtime-width kernel with dW1 accumulated in the slab: 99.5 us per 256-sample gradient launch
         static const bool no_half = getenv("TMA_NO_HALF_GROUPS") != nullptr;
-        const bool small7 = L.H == 256 && L.D > 32 && L.D <= 112 && mbi->count <= 1024 && !no_half && getenv("TMA_WIDE_NW4") == nullptr && getenv("TMA_NO_DEFER_W2") == nullptr &&
+        static const bool no_defer = getenv("TMA_NO_DEFER_W2") != nullptr;  // (small7 and defer_w2 below read this one value: small7 has no dW2 accumulators)
+        const bool nw4 = getenv("TMA_WIDE_NW4") != nullptr;
+        const bool small7 = L.H == 256 && L.D > 32 && L.D <= 112 && mbi->count <= 1024 && !no_half && !nw4 && !no_defer &&
                             (int64_t)64 * L.P + 4 * (int64_t)W2_DEFER_ROWS * L.H <= (int64_t)slab_cap(L) * L.P;  // (the deferral buffer must fit: that kernel has no dW2 accumulators)
         const bool half = (L.D <= 32 || small7) && mbi->count <= 1024 && !no_half;  // (at 2048 samples the doubled slab count costs more than the shorter groups save: 79.6 against 76.6 us per call)
         const int64_t groups = ceil_div(mbi->count, half ? 16 : 32);  // one row group per block while there are CUs to spare, then grid-stride
@@ -2581,13 +2604,13 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
             k<<<dim3((unsigned)(n_pi + n_vf)), dim3(256), smemw, s>>>(params, L, R, M, hpar, ws_adv, slabs, slots, n_pi, dz1, DZ1_CAP * L.H);
             return TMA_OK;
         };
-        const bool eight = L.H == 256 && (kt1 == 1 || kt1 == 2 || kt1 == 7) && getenv("TMA_WIDE_NW4") == nullptr;
+        const bool eight = L.H == 256 && (kt1 == 1 || kt1 == 2 || kt1 == 7) && !nw4;
         const int smem8 = grad_wide_smem_bytes(L, 8);
         // half groups on the eight-wave kernel (<= 1024 samples: <= 64 slabs in use): dW2 deferred to wide_small_reduce_kernel through a buffer behind
         // slab 64 of the workspace's slab area (TMA_NO_DEFER_W2=1: the slab path throughout)
-        static const bool no_defer = getenv("TMA_NO_DEFER_W2") != nullptr;
         const bool defer_w2 = half && eight && !no_defer && n_pi <= 64 && groups * 16 <= W2_DEFER_ROWS && (int64_t)64 * L.P + 4 * (int64_t)W2_DEFER_ROWS * L.H <= (int64_t)slab_cap(L) * L.P;
         float *const w2buf = defer_w2 ? slabs + (int64_t)64 * L.P : nullptr;
+        if (kt1 == 7 && !w2buf) return fail(TMA_ERR_INVALID, "internal: the kt1 = 7 half-group kernel needs the dW2 deferral buffer (%lld samples)", (long long)mbi->count);
         auto launch8 = [&](auto k) -> int {
             TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem8));
             k<<<dim3((unsigned)(n_pi + n_vf)), dim3(512), smem8, s>>>(params, L, R, M, hpar, ws_adv, slabs, slots, n_pi, w2buf, (int64_t)2 * W2_DEFER_ROWS * L.H);
@@ -2596,6 +2619,17 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
         // (as on the bf16 path) minibatches that fit the dz1 cache: chain pass + dW1 from the cached operands; else chain + recompute
         float *const dz1_cache = (f32_two_pass(L) && (kt1 == 11 || kt1 == 107) && mbi->count <= DZ1_CAP && !getenv("TMA_NO_DZ1_CACHE"))
             ? reinterpret_cast<float *>(ws + WS_SLABS + (int64_t)slab_cap(L) * L.P * 4 + OFFS_CAP * 4 + EPOCH_PART_BYTES + WIDE_SQ_SLOTS * 8) : nullptr;
+        if (kt1 == 7) g_disp_grad = TMA_DISPATCH_GRAD_F32_SMALL7;
+        else if (kt1 == 1 || kt1 == 2) {
+            const bool k2 = kt1 == 2;
+            if (eight) g_disp_grad = half ? (defer_w2 ? (k2 ? TMA_DISPATCH_GRAD_F32_KT2_HALF_W8_DEFER : TMA_DISPATCH_GRAD_F32_KT1_HALF_W8_DEFER)
+                                                      : (k2 ? TMA_DISPATCH_GRAD_F32_KT2_HALF_W8_SLAB : TMA_DISPATCH_GRAD_F32_KT1_HALF_W8_SLAB))
+                                          : (k2 ? TMA_DISPATCH_GRAD_F32_KT2_FULL_W8 : TMA_DISPATCH_GRAD_F32_KT1_FULL_W8);
+            else g_disp_grad = half ? (k2 ? TMA_DISPATCH_GRAD_F32_KT2_HALF_W4 : TMA_DISPATCH_GRAD_F32_KT1_HALF_W4)
+                                    : (k2 ? TMA_DISPATCH_GRAD_F32_KT2_FULL_W4 : TMA_DISPATCH_GRAD_F32_KT1_FULL_W4);
+        } else if (kt1 == 11) g_disp_grad = dz1_cache ? TMA_DISPATCH_GRAD_F32_KT11_CACHED : TMA_DISPATCH_GRAD_F32_KT11_RECOMPUTE;
+        else if (kt1 == 107) g_disp_grad = dz1_cache ? TMA_DISPATCH_GRAD_F32_KT107_CACHED : TMA_DISPATCH_GRAD_F32_KT107_RECOMPUTE;
+        else g_disp_grad = TMA_DISPATCH_GRAD_F32_KT0;
         auto pick = [&](auto ntw) -> int {
             constexpr int NTWc = decltype(ntw)::value;
             auto both = [&](auto cont) -> int {
@@ -2645,6 +2679,8 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
     const int smem = grad_smem_bytes(L, wpb);
     if (smem > 160 * 1024) return fail(TMA_ERR_INVALID, "policy too wide for the LDS-resident tile (needs %d bytes)", smem);
     int64_t blocks = ceil_div(tiles, wpb);
+    g_disp_grad = (wpb == 4 ? TMA_DISPATCH_GRAD_GENERIC_W4 : (wpb == 3 ? TMA_DISPATCH_GRAD_GENERIC_W3 : (wpb == 2 ? TMA_DISPATCH_GRAD_GENERIC_W2 : TMA_DISPATCH_GRAD_GENERIC_W1))) |
+                  (blocks > MAX_GRAD_BLOCKS / 2 ? TMA_DISPATCH_GRID_CAPPED : 0);
     if (blocks > MAX_GRAD_BLOCKS / 2) blocks = MAX_GRAD_BLOCKS / 2;
     if (d->continuous) {
         auto k = ppo_grad_kernel<true>;
@@ -3043,6 +3079,7 @@ int tma_ppo_epoch_adv_sums(void *workspace, const tma_policy_dims *d, int64_t ba
 
 int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg_sq, const tma_policy_dims *d, int64_t step, double lr, double beta1,
                       double beta2, double eps, double max_grad_norm, double grad_scale, void *workspace, void *stream) {
+    g_disp_opt = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !grad || !exp_avg || !exp_avg_sq || !workspace) return fail(TMA_ERR_INVALID, "tma_ppo_adam_step: null buffer");
@@ -3060,6 +3097,7 @@ int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg
         // layouts whose derived copies the optimizer kernel scatters itself: norm partials of the (all-reduced, scaled) gradient, then
         // ONE multi-block Adam + scatter launch -- two launches instead of three to five
         const int n_part = (int)ceil_div(L.P, 64);
+        g_disp_opt = scat_h64 ? TMA_DISPATCH_OPT_SCATTER_H64 : TMA_DISPATCH_OPT_SCATTER_WIDE;
         grad_sumsq64_kernel<<<dim3((unsigned)n_part), dim3(64), 0, s>>>(grad, L.P, (float)grad_scale, sqp);
         TMA_LAUNCH_CHECK();
         if (scat_h64)
@@ -3075,11 +3113,13 @@ int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg
         return TMA_OK;
     }
     if (L.P <= 32768) {
+        g_disp_opt = TMA_DISPATCH_OPT_SMALL;
         opt_small_kernel<<<dim3(1), dim3(1024), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, (float)grad_scale, (float)max_grad_norm, (float)step_size,
                                                         (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out);
         TMA_LAUNCH_CHECK();
         return launch_sync(params, L, s);
     }
+    g_disp_opt = TMA_DISPATCH_OPT_ADAM;
     int nb = (int)ceil_div(L.P, 1024);
     if (nb > 256) nb = 256;
     grad_sumsq_kernel<<<dim3(nb), dim3(256), 0, s>>>(grad, L.P, (float)grad_scale, partials);
@@ -3092,6 +3132,7 @@ int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg
 
 int tma_ppo_adam_step_local(float *params, float *grad, float *exp_avg, float *exp_avg_sq, const tma_policy_dims *d, int64_t step, double lr,
                             double beta1, double beta2, double eps, double max_grad_norm, void *workspace, void *stream, int64_t last_count) {
+    g_disp_opt = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !grad || !exp_avg || !exp_avg_sq || !workspace) return fail(TMA_ERR_INVALID, "tma_ppo_adam_step_local: null buffer");
@@ -3109,6 +3150,7 @@ int tma_ppo_adam_step_local(float *params, float *grad, float *exp_avg, float *e
     hipStream_t s = (hipStream_t)stream;
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
+    g_disp_opt = h64 ? TMA_DISPATCH_OPT_LOCAL_SCATTER_H64 : TMA_DISPATCH_OPT_LOCAL_SCATTER_WIDE;
     if (h64)
         adam_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
             params, grad, exp_avg, exp_avg_sq, L, sqp, (int)ceil_div(L.P, 64), (float)max_grad_norm, (float)step_size, (float)beta1, (float)beta2,
@@ -3134,6 +3176,13 @@ int tma_debug_time_grad_kernel(int enable) {
     }
     g_time_grad = enable != 0;
     g_ev_valid = false;
+    return TMA_OK;
+}
+
+int tma_debug_last_dispatch(int32_t *fwd_out, int32_t *grad_out, int32_t *opt_out) {
+    if (fwd_out) *fwd_out = g_disp_fwd;
+    if (grad_out) *grad_out = g_disp_grad;
+    if (opt_out) *opt_out = g_disp_opt;
     return TMA_OK;
 }
 
