@@ -452,7 +452,7 @@ __device__ __forceinline__ void fold_adam_into_image(const AdamFold &f, const PL
     }
 }
 
-template <bool IS_PI, int DT, bool DIRECT = false>
+template <bool IS_PI, int DT, bool DIRECT = false, int AT = 0>  // AT > 0: compile-time head width of the policy net, 0: runtime L.A
 __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params, const PLayout &L, const Rollout &rb, const Minibatch &mb,
                                                const HParams &hp, const double *__restrict__ adv_part, int n_part, float *__restrict__ slab,
                                                double *__restrict__ stat_slot, float *smem, int n_blocks_net, int block_net, const AdamFold &fold) {
@@ -463,7 +463,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const int r16 = lane & 15, g = lane >> 4;  // r16: the tile's sample this lane works for (and the A operand's row); g: lane group
     (void)0;
-    const int D = DT > 0 ? DT : L.D, A = L.A;
+    const int D = DT > 0 ? DT : L.D, A = AT > 0 ? AT : L.A;
     constexpr int KS1C = DT > 0 ? (DT + 3) / 4 : 4;  // layer-1 k-steps held in registers (runtime D: up to 16 features)
     const int KS1 = (D + 3) >> 2;
     float *wimg = smem;  // this net's weight image, staged once per block
@@ -568,7 +568,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
         const float m0 = pf_m0, m1 = pf_m1;
         const int act = pf_act;
         fetch(tile + tile_stride);
-        h64t_tile<IS_PI, KS1C>(wimg, slotA, slotB, dz3t, Xt, xb, m0, m1, act, valid, KS1, A, invB, amean, astd, hp, acc, st, tk, lane);
+        h64t_tile<IS_PI, KS1C, AT>(wimg, slotA, slotB, dz3t, Xt, xb, m0, m1, act, valid, KS1, A, invB, amean, astd, hp, acc, st, tk, lane);
     }
 #ifdef TMA_H64_TICKS
     const unsigned long long loop_t1 = __builtin_amdgcn_s_memtime();
@@ -607,7 +607,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
     }
 }
 
-template <int DT, int VER>
+template <int DT, int VER, int AT = 0>  // AT > 0 (VER 2): compile-time head width -- <4, 2, 5> is the headline shape (GridWorld: 4 observations, 5 actions)
 __global__ __launch_bounds__(512, 2) void ppo_grad_h64_kernel(const float *__restrict__ params, PLayout L, Rollout rb, Minibatch mb, HParams hp,
                                                               const double *__restrict__ adv_part, int n_part, float *__restrict__ slabs,
                                                               double *__restrict__ stat_slots, AdamFold fold) {
@@ -622,7 +622,7 @@ __global__ __launch_bounds__(512, 2) void ppo_grad_h64_kernel(const float *__res
         if (pi_block) grad_h64_body<true, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair);
         else grad_h64_body<false, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair);
     } else {
-        if (pi_block) grad_h64t_body<true, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold);
+        if (pi_block) grad_h64t_body<true, DT, false, AT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold);
         else grad_h64t_body<false, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold);
     }
 }
@@ -661,6 +661,7 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
     static const int ver = getenv("TMA_H64_V1") ? 1 : 2;  // (development switch: the round-1 LDS-round-trip tile chain)
     if (ver == 1 && foldp && foldp->grad) return TMA_ERR_INVALID;  // the round-1 chain has no optimizer prologue: refuse instead of dropping the step
     static const int stagger = getenv("TMA_H64_STAGGER") ? atoi(getenv("TMA_H64_STAGGER")) : 0;
+    static const bool runtime_a = getenv("TMA_H64_RUNTIME_A") != nullptr;  // (A/B and test switch: the runtime-head-width kernel at every shape)
     HParams hps = hpar;
     hps.debug = stagger;
     const int64_t tiles = ceil_div(M.count, 16);
@@ -688,6 +689,7 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
     };
     int rc;
     if (ver == 1) rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 1>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 1>) : launch(ppo_grad_h64_kernel<0, 1>));
+    else if (L.D == 4 && L.A == 5 && !runtime_a) rc = launch(ppo_grad_h64_kernel<4, 2, 5>);  // the headline shape: head width folded as well
     else rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 2>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 2>) : launch(ppo_grad_h64_kernel<0, 2>));
     if (rc) return rc;
     TMA_LAUNCH_CHECK();

@@ -169,10 +169,13 @@ struct TileStats {
 // Loss of one tile from the head outputs (C layout: register r of lane group g is output g + 4r of sample r16): the clipped
 // surrogate + entropy bonus for the policy net, the squared error for the value net.  Returns d loss / d head output, adds the
 // tile's statistics.  (SB3 PPO.train)
-template <bool IS_PI>
-__device__ __forceinline__ f32x4 h64t_loss(const f32x4 &o0, const f32x4 &o1, float m0, float m1, int act, bool valid, int A, float invB, float amean,
+// AT > 0: compile-time head width (the rows g + 4r >= AT of a lane can never hold an action: their exp / select work folds away; the live
+// rows see the same operations in the same order, so the bits are those of the runtime width), 0: runtime A_rt.
+template <bool IS_PI, int AT = 0>
+__device__ __forceinline__ f32x4 h64t_loss(const f32x4 &o0, const f32x4 &o1, float m0, float m1, int act, bool valid, int A_rt, float invB, float amean,
                                            float astd, const HParams &hp, TileStats &st, int lane) {
     const int g = lane >> 4;
+    const int A = AT > 0 ? AT : A_rt;
     f32x4 dz3;
     if constexpr (IS_PI) {
         float x[4], e[4], lp[4], p[4];
@@ -235,11 +238,14 @@ __device__ __forceinline__ f32x4 h64t_loss(const f32x4 &o0, const f32x4 &o1, flo
 // One tile.  Lane (g, r16) works for the tile's sample r16; xb[ks] = observation feature 4 ks + g of that sample (0 beyond D or for an
 // invalid row), m0 / m1 / act = (old log-prob, advantage, action) for the policy net, (return, -, -) for the value net.
 // wimg: this net's LDS weight image; slotA / slotB / dz3t / Xt: the wave's private [sample][feature] tiles (T_PER_WAVE floats in all).
-template <bool IS_PI, int KS1C>
+// AT > 0: compile-time head width of the policy net (as KS1C is the compile-time observation width), 0: runtime A_rt.  With the width known
+// the dW3 / dh2 chains below are straight-line code: no branch on the width, no dead MFMA path holding registers across the tile loop.
+template <bool IS_PI, int KS1C, int AT = 0>
 __device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float *slotB, float *dz3t, float *Xt, const float (&xb)[KS1C], float m0,
-                                          float m1, int act, bool valid, int KS1, int A, float invB, float amean, float astd, const HParams &hp,
+                                          float m1, int act, bool valid, int KS1, int A_rt, float invB, float amean, float astd, const HParams &hp,
                                           NetAcc &acc, TileStats &st, TileTicks &tk, int lane) {
     const int r16 = lane & 15, g = lane >> 4;
+    const int A = AT > 0 ? AT : A_rt;
     const int NOUT = IS_PI ? A : 1;
     (void)tk;
 #pragma unroll
@@ -303,7 +309,7 @@ __device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float
         }
     if constexpr (TMA_H64_PIPE) store_tile_t(slotB, h2, r16, g);
     H64_TICK(3);
-    const f32x4 dz3 = h64t_loss<IS_PI>(o0, o1, m0, m1, act, valid, A, invB, amean, astd, hp, st, lane);
+    const f32x4 dz3 = h64t_loss<IS_PI, AT>(o0, o1, m0, m1, act, valid, A, invB, amean, astd, hp, st, lane);
     H64_TICK(4);
     *reinterpret_cast<f32x4 *>(dz3t + r16 * 16 + 4 * g) = dz3;  // (column m = 4g + r of the tile <-> output a(m), undone by flush_segment)
     H64_TICK(4);

@@ -32,6 +32,11 @@ for net, o in (("pi", 0), ("vf", 16)):
     v = [out[o + i] / tiles for i in range(16)]
     print(net, "cycles per tile:", {n: round(x) for n, x in zip(names, v) if n}, "sum", round(sum(v[:10]) + v[15]))
     loop_c, loop_rt, pro, epi = (out[o + i] / reps for i in (10, 11, 12, 13))
+    # H64_TICK adds (clock at the stamp) - (clock after the PREVIOUS stamp's bookkeeping): what a stamp itself costs between its two clock
+    # reads (lane 0's read-add-write of the global counter) belongs to no phase.  The phase sum is therefore SHORTER than the loop, and a
+    # pipe-busy fraction must be taken over the loop time per tile (or from SQ counters), never over the sum.
+    per_tile = out[o + 10] / tiles
+    print("    loop per tile", round(per_tile), "cycles; the phase sum leaves out", round(per_tile - (sum(v[:10]) + v[15])), "cycles a tile spent inside the stamps")
     print("    of the epilogue,", round(out[o + 14] / reps), "cycles are the wait for the block's slowest wave")
     print("    per launch: loop", round(loop_c), "cycles =", round(loop_rt / 100, 1), "us (100 MHz counter) -> clock", round(loop_c / max(loop_rt, 1) * 0.1, 2),
           "GHz; prologue", round(pro), "cycles, epilogue", round(epi), "cycles")

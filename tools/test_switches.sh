@@ -28,3 +28,5 @@ run "TMA_WIDE_F32_ROWS=16" "tests/test_ppo_gpu.py tests/test_rollout_oracle_gpu.
 run "TMA_WIDE_F32_ROWS=8" "tests/test_ppo_gpu.py"                             # ... and in 8-env tiles beyond 2048 envs
 run "TMA_NO_CONT_F32_FUSED=1" "tests/test_ppo_gpu.py" "crawler or ant"   # the f32 Box-action rollouts step by step
 run "TMA_ROLL2=1" "tests/test_ppo_gpu.py tests/test_rollout_oracle_gpu.py" "rollout"   # the headline rollout on two waves per tile (round 5) instead of four
+# round 7
+run "TMA_H64_RUNTIME_A=1" "tests/test_ppo_gpu.py tests/test_policy_dispatch_gpu.py tests/test_rollout_oracle_gpu.py"   # the H = 64 gradient kernel with the head width read at run time at every shape (the headline shape has a compile-time instantiation)
