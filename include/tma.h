@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 209
+#define TMA_VERSION 210
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -134,6 +134,15 @@ int tma_env_pop_detached_episode_log(tma_env *env, double *ret_host, int32_t *le
 int tma_gae(const float *rewards, const float *values, const float *episode_starts, const float *last_values,
             const uint8_t *dones, double gamma, double gae_lambda, int T, int64_t N, float *adv_out, float *ret_out,
             void *stream);
+/* SB3 `train/explained_variance` (PPO.train: explained_variance(rollout_buffer.values.flatten(), rollout_buffer.returns.flatten())):
+ * out_dev[0] = 1 - Var(returns - values) / Var(returns) over the n = T * N floats of the two planes (population variances), NaN where
+ * Var(returns) == 0.  ABI 210.  Accumulated in float64 as (count, mean, M2) triples -- Welford per thread, Chan's merge over lanes, waves and
+ * blocks in a fixed order, plain stores and no floating-point atomics -- so the result is bit-identical from run to run and returns with a
+ * large mean do not cancel (SB3 takes np.var of the float32 arrays: DESIGN.md section 7).  `scratch`: TMA_EV_SCRATCH_DOUBLES doubles of device
+ * memory the two launches use between them; out_dev: one double of device memory.  Nothing is synchronised: the caller copies out_dev
+ * stream-ordered. */
+#define TMA_EV_SCRATCH_DOUBLES 1536
+int tma_explained_variance(const float *values, const float *returns, int64_t n, double *scratch, double *out_dev, void *stream);
 
 /* ---- actor-critic MLP + PPO update: replaces the SB3 objects PPO("MlpPolicy", env, **kwargs) builds at
  *      backend/mlagents/training.py:150 (policy_kwargs net_arch pi/vf = [H, H], training.py:363-365; hyper-parameters
@@ -169,6 +178,16 @@ int tma_policy_act(const float *params, const tma_policy_dims *d, const float *o
 int tma_policy_act_bootstrap(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, uint32_t rng_seed, uint32_t rng_step,
                              uint32_t env_offset, void *actions_out, float *values_out, float *logp_out, const float *prev_terminal_obs,
                              const uint8_t *prev_truncated, double gamma, float *prev_rewards_inout, void *stream);
+/* ActorCriticPolicy.evaluate_actions(obs, actions) (ABI 210): values f32[n], log_prob f32[n] and entropy f32[n] of GIVEN actions -- i32[n]
+ * (Discrete) or f32[n][act_dim] (Box, unclipped: the rollout buffer's layout).  Any output may be NULL, not all three.  The kernels are the
+ * ones tma_policy_act runs (same specialisation for a shape, same layer code and k order, same grid caps; tma_debug_last_dispatch reports
+ * the same TMA_DISPATCH_FWD_* id): `values` is bit-identical to tma_policy_act's, and so is `log_prob` where `actions` are the ones it drew.
+ * Categorical: log_softmax at the action, -sum p log p.  DiagGaussian: sum_j -d^2 / (2 sigma^2) - log sigma - log(2 pi) / 2 and
+ * sum_j 1/2 + log(2 pi) / 2 + log sigma.  A Discrete action outside [0, act_dim) is only ever compared with column indices (it never
+ * addresses memory): that row's log_prob is NaN, its value and entropy are those of any other row.  mfma_dtype 2 policies take the exact-f32
+ * kernels.  Bad dims, null params / obs / actions, n < 1 and three NULL outputs are refused (TMA_ERR_INVALID) before any HIP call. */
+int tma_policy_evaluate_actions(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
+                                float *values_out, float *logp_out, float *entropy_out, void *stream);
 /* ActorCriticPolicy.predict_values */
 int tma_policy_values(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *values_out, void *stream);
 /* collect_rollouts timeout bootstrap: rewards[i] += gamma * V(terminal_obs[i]) where truncated[i] */

@@ -14,6 +14,7 @@ SO_PATH = os.environ.get("TMA_LIB_PATH") or os.path.join(_HERE, "csrc", "libtma_
 TMA_OK, TMA_ERR_INVALID, TMA_ERR_UNKNOWN_TASK, TMA_ERR_HIP = 0, 1, 2, 3
 ACT_I32, ACT_I64, ACT_F32 = 0, 1, 2
 EP_STRIDE = 1 << 20
+EV_SCRATCH_DOUBLES = 1536  # include/tma.h TMA_EV_SCRATCH_DOUBLES
 
 _vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_double
 
@@ -75,11 +76,13 @@ SIGNATURES = {
     "tma_env_pop_detached_episode_log": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f64), _vp]),
     "tma_gae": (_i32, [_vp, _vp, _vp, _vp, _vp, _f64, _f64, _i32, _i64, _vp, _vp, _vp]),
     "tma_gae_flags": (_i32, [_vp, _vp, _vp, _vp, _vp, _f64, _f64, _i32, _i64, _vp, _vp, _vp]),
+    "tma_explained_variance": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "tma_policy_param_count": (_i32, [_pd, C.POINTER(_i64), C.POINTER(_i64)]),
     "tma_policy_param_offsets": (_i32, [_pd, C.POINTER(_i32)]),
     "tma_policy_sync": (_i32, [_vp, _pd, _vp]),
     "tma_policy_act": (_i32, [_vp, _pd, _vp, _i64, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp]),
     "tma_policy_act_bootstrap": (_i32, [_vp, _pd, _vp, _i64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
+    "tma_policy_evaluate_actions": (_i32, [_vp, _pd, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tma_policy_values": (_i32, [_vp, _pd, _vp, _i64, _vp, _vp]),
     "tma_policy_bootstrap": (_i32, [_vp, _pd, _vp, _vp, _i64, _f64, _vp, _vp]),
     "tma_ppo_workspace_bytes": (_i64, [_pd]),

@@ -280,3 +280,88 @@ extern "C" int tma_gae_flags(const float *rewards, const float *values, const ui
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// explained variance of the value function over a rollout: 1 - Var(returns - values) / Var(returns)  (SB3 PPO.train:
+// explained_variance(values.flatten(), returns.flatten()), population variances, NaN where Var(returns) == 0).
+// Float64 (count, mean, M2) triples, never sum-of-squares minus squared-sum: returns with a large mean would cancel.  A thread runs Welford's
+// update over its elements; lanes, waves and blocks are merged with Chan's formula in a FIXED order (shuffle tree, wave index, block index),
+// with plain stores and no floating-point atomics: the result is bit-identical from run to run.
+// ------------------------------------------------------------------------------------------
+namespace tma {
+
+struct Moments {
+    double n, mean, m2;
+};
+__device__ __forceinline__ void moments_add(Moments &a, double x) {
+    a.n += 1.0;
+    const double d = x - a.mean;
+    a.mean += d / a.n;
+    a.m2 += d * (x - a.mean);
+}
+__device__ __forceinline__ Moments moments_merge(const Moments &a, const Moments &b) {  // Chan et al.: a then b
+    const double n = a.n + b.n;
+    if (n == 0.0) return a;
+    const double d = b.mean - a.mean;
+    return Moments{n, a.mean + d * (b.n / n), (a.m2 + b.m2) + (d * d) * (a.n * (b.n / n))};
+}
+__device__ __forceinline__ Moments moments_wave(Moments a) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const Moments b{__shfl_down(a.n, o, 64), __shfl_down(a.mean, o, 64), __shfl_down(a.m2, o, 64)};
+        a = moments_merge(a, b);
+    }
+    return a;
+}
+
+constexpr int EV_BLOCKS = TMA_EV_SCRATCH_DOUBLES / 6;  // partial triples: [block][returns | returns - values][n, mean, M2]
+
+// pass 1: block b takes the contiguous slice [b * per, (b + 1) * per) of the flattened buffer
+__global__ __launch_bounds__(256) void ev_partial_kernel(const float *__restrict__ values, const float *__restrict__ returns, int64_t n, int64_t per,
+                                                         double *__restrict__ part) {
+    __shared__ Moments sy[4], sr[4];
+    const int64_t j0 = (int64_t)blockIdx.x * per, j1 = (j0 + per < n) ? j0 + per : n;
+    Moments my{0.0, 0.0, 0.0}, mr{0.0, 0.0, 0.0};
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) {
+        const double y = (double)returns[j];
+        moments_add(my, y);
+        moments_add(mr, y - (double)values[j]);
+    }
+    my = moments_wave(my);
+    mr = moments_wave(mr);
+    if ((threadIdx.x & 63) == 0) sy[threadIdx.x >> 6] = my, sr[threadIdx.x >> 6] = mr;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) my = moments_merge(my, sy[w]), mr = moments_merge(mr, sr[w]);
+        double *p = part + 6 * (int64_t)blockIdx.x;
+        p[0] = my.n, p[1] = my.mean, p[2] = my.m2;
+        p[3] = mr.n, p[4] = mr.mean, p[5] = mr.m2;
+    }
+}
+// pass 2: one thread folds the block triples in block-index order
+__global__ void ev_final_kernel(const double *__restrict__ part, int n_part, double *__restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    Moments my{0.0, 0.0, 0.0}, mr{0.0, 0.0, 0.0};
+    for (int b = 0; b < n_part; b++) {
+        const double *p = part + 6 * (int64_t)b;
+        my = moments_merge(my, Moments{p[0], p[1], p[2]});
+        mr = moments_merge(mr, Moments{p[3], p[4], p[5]});
+    }
+    const double var_y = my.m2 / my.n, var_r = mr.m2 / mr.n;
+    out[0] = var_y == 0.0 ? __builtin_nan("") : 1.0 - var_r / var_y;
+}
+
+}  // namespace tma
+
+extern "C" int tma_explained_variance(const float *values, const float *returns, int64_t n, double *scratch, double *out_dev, void *stream) {
+    using namespace tma;
+    if (!values || !returns || !scratch || !out_dev) return fail(TMA_ERR_INVALID, "tma_explained_variance: null buffer");
+    if (n < 1) return fail(TMA_ERR_INVALID, "tma_explained_variance: n must be >= 1 (got %lld)", (long long)n);
+    int64_t nb = ceil_div(n, 1024);
+    if (nb > EV_BLOCKS) nb = EV_BLOCKS;
+    const int64_t per = ceil_div(n, nb);
+    ev_partial_kernel<<<dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream>>>(values, returns, n, per, scratch);
+    TMA_LAUNCH_CHECK();
+    ev_final_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(scratch, (int)nb, out_dev);
+    TMA_LAUNCH_CHECK();
+    return TMA_OK;
+}

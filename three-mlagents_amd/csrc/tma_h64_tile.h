@@ -685,6 +685,40 @@ __device__ __forceinline__ float h64t_logp(const f32x4 &xs, int A, int act, int 
     for (int r = 0; r < 4; r++) lpa += (g + 4 * r == act) ? (ok[r] ? x[r] - lse : 0.0f) : 0.0f;
     return xg_sum(lpa);
 }
+// h64t_eval (evaluate_actions): log-probability of a GIVEN action and the entropy of softmax(o0 + o1).  The log-probability is h64t_act_n's
+// operations in its order (the bits tma_policy_act reports for an action it drew), the entropy h64t_loss's.  The action is only ever compared
+// with a column index: one outside [0, A) selects nothing, and its log-probability is NaN by a select.
+__device__ __forceinline__ void h64t_eval(const f32x4 &o0, const f32x4 &o1, int A, int act, float &lp_out, float &ent_out, int lane) {
+    const int g = lane >> 4;
+    float x[4], e[4];
+    bool ok[4];
+    float m = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        ok[r] = g + 4 * r < A;
+        x[r] = ok[r] ? o0[r] + o1[r] : -INFINITY;
+        m = fmaxf(m, x[r]);
+    }
+    m = xg_max(m);
+    float ssum = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        e[r] = ok[r] ? __expf(x[r] - m) : 0.0f;
+        ssum += e[r];
+    }
+    ssum = xg_sum(ssum);
+    const float lse = m + __logf(ssum), rs = __builtin_amdgcn_rcpf(ssum);
+    float lpa = 0.0f, ent = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const float lp = ok[r] ? x[r] - lse : 0.0f;
+        lpa += (g + 4 * r == act) ? lp : 0.0f;
+        ent += (e[r] * rs) * lp;
+    }
+    lpa = xg_sum(lpa);
+    lp_out = (act >= 0 && act < A) ? lpa : __builtin_nanf("");
+    ent_out = -xg_sum(ent);
+}
 __device__ __forceinline__ void h64t_act(const f32x4 &o0, const f32x4 &o1, int A, uint32_t rng_seed, uint32_t global_env, uint32_t rng_step, int det,
                                          int &act_out, float &lp_out, int lane) {
     h64t_act_n(o0, o1, A, h64t_gumbel(rng_seed, global_env, rng_step, det, lane), act_out, lp_out, lane);

@@ -113,7 +113,11 @@ __global__ void sync_transposed_kernel(float *params, PLayout L) {
 
 // ------------------------------------------------------------------------------------------
 // policy_act: obs[n][D] -> sampled (or deterministic) actions, values, log-probs.  One wave per 16 rows.
-// MODE: 0 act (actions+values+logp), 1 values only, 2 timeout bootstrap (rewards[i] += gamma * V(term_obs[i]) where trunc[i])
+// MODE: 0 act (actions+values+logp), 1 values only, 2 timeout bootstrap (rewards[i] += gamma * V(term_obs[i]) where trunc[i]),
+//       3 evaluate_actions (SB3 ActorCriticPolicy.evaluate_actions): the layers and heads of MODE 0 in the same k order, but the head epilogue READS
+//         the row's action from `actions_out` (i32[n] / f32[n][A]) instead of drawing one, and also forms the entropy; `rewards` is entropy_out.
+//         values_out / logp_out / entropy_out may each be null.  A Discrete action outside [0, A) matches no column (it never indexes memory):
+//         that row's log-prob is NaN by a select, its value and entropy are unaffected.  Same for the H = 64 and wide kernels below.
 // ------------------------------------------------------------------------------------------
 template <bool CONT, int MODE>
 __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict__ params, PLayout L, const float *__restrict__ obs, int64_t n,
@@ -166,7 +170,18 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict
                 }
             continue;
         }
-        if constexpr (MODE == 0) {
+        if constexpr (MODE == 0 || MODE == 3) {
+            constexpr bool EVAL = MODE == 3;
+            float *const entropy_out = rewards;  // (MODE 3)
+            if constexpr (EVAL) {
+                if (r16 == 0 && values_out != nullptr)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int64_t row = row0 + g * 4 + r;
+                        if (row < n) values_out[row] = vacc[0][r];
+                    }
+                if (logp_out == nullptr && entropy_out == nullptr) continue;
+            }
             const Net P = pi_net(params, L);
             dense_tanh(X, ldx, D, P.W1t, P.b1, H, h1, ld, lane);
             dense_tanh(h1, ld, H, P.W2t, P.b2, H, h2, ld, lane);
@@ -183,6 +198,16 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict
                     const float s = gsum16(e);
                     const float lse = m + logf(s);
                     const float lp = x - lse;
+                    if constexpr (EVAL) {
+                        const int act = row < n ? static_cast<const int32_t *>(actions_out)[row] : 0;
+                        const float lpa = gsum16((r16 == act) ? lp : 0.0f);  // (column compare, as MODE 0 and policy_loss_tile)
+                        const float ent = -gsum16((e / s) * (colok ? lp : 0.0f));
+                        if (r16 == r && row < n) {
+                            if (logp_out != nullptr) logp_out[row] = (act >= 0 && act < A) ? lpa : __builtin_nanf("");
+                            if (entropy_out != nullptr) entropy_out[row] = ent;
+                        }
+                        continue;
+                    }
                     int act;
                     if (deterministic) {
                         const float cand = (colok && x == m) ? (float)r16 : 99.0f;
@@ -213,13 +238,17 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict
                     const int64_t row = row0 + g * 4 + r;
                     const uint32_t gi = env_offset + (uint32_t)row;
                     float lpsum = 0.0f;
+                    [[maybe_unused]] float entsum = 0.0f;
 #pragma unroll
                     for (int j = 0; j < 2; j++) {
                         const int col = 16 * j + r16;
                         if (col < A) {
                             const float mu = acc[j][r], lsd = ls[col], sd = expf(lsd);
                             float a = mu;
-                            if (!deterministic) {
+                            if constexpr (EVAL) {
+                                if (row < n) a = static_cast<const float *>(actions_out)[row * A + col];
+                                entsum += 1.4189385332046727f + lsd;
+                            } else if (!deterministic) {
                                 const float u1 = fmaxf(uniform01(mix32(rng_seed ^ (0x68E31DA4u + (uint32_t)col * 0x9E3779B9u), gi, rng_step)), 5.9604645e-08f);
                                 const float u2 = uniform01(mix32(rng_seed ^ (0xB5297A4Du + (uint32_t)col * 0x85EBCA77u), gi, rng_step));
                                 const float z = sqrtf(-2.0f * logf(u1)) * cosf(6.2831853071795865f * u2);
@@ -227,10 +256,19 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict
                             }
                             const float d = a - mu;
                             lpsum += -(d * d) / (2.0f * (sd * sd)) - lsd - 0.9189385332046727f;
-                            if (row < n) static_cast<float *>(actions_out)[row * A + col] = a;
+                            if constexpr (!EVAL)
+                                if (row < n) static_cast<float *>(actions_out)[row * A + col] = a;
                         }
                     }
                     lpsum = gsum16(lpsum);
+                    if constexpr (EVAL) {
+                        entsum = gsum16(entsum);
+                        if (r16 == r && row < n) {
+                            if (logp_out != nullptr) logp_out[row] = lpsum;
+                            if (entropy_out != nullptr) entropy_out[row] = entsum;
+                        }
+                        continue;
+                    }
                     const float vrow = gfirst_quad(vacc[0][r]);
                     if (r16 == r && row < n) {
                         logp_out[row] = lpsum;
@@ -1902,6 +1940,7 @@ static int grad_smem_bytes(const PLayout &L, int wpb) {
 // H = 64 forward fast path: both nets' forward weight images staged in LDS once per block (float4 copies of the images
 // tma_policy_sync maintains), B operands by ds_read_b128.  MODE 0 also folds the timeout bootstrap of the PREVIOUS vector
 // step (rewards_prev[i] += gamma * V(terminal_obs_prev[i]) where truncated_prev[i]) into the same launch.
+// MODE 3 (evaluate_actions, see policy_fwd_kernel): `actions_out` is read, `boot_rewards` is entropy_out.
 // ------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(256) void policy_fwd_h64_kernel(const float *__restrict__ params, PLayout L, const float *__restrict__ obs, int64_t n,
@@ -1919,7 +1958,7 @@ __global__ __launch_bounds__(256) void policy_fwd_h64_kernel(const float *__rest
     const int D = L.D, A = L.A, KS1 = (D + 3) >> 2;
     float *vimg = smem, *pimg = smem + FWD_IMG;
     stage_fwd_image(params + L.img_vf, vimg);
-    if constexpr (MODE == 0) stage_fwd_image(params + L.img_pi, pimg);
+    if constexpr (MODE == 0 || MODE == 3) stage_fwd_image(params + L.img_pi, pimg);
     __syncthreads();
     const int64_t n_tiles = (n + 15) >> 4;
     auto features = [&](const float *src, int64_t row, bool ok, float (&xb)[4]) {  // (clamped addresses, masked values: no load sits behind a branch)
@@ -1938,7 +1977,19 @@ __global__ __launch_bounds__(256) void policy_fwd_h64_kernel(const float *__rest
             features(obs, row, ok, xb);
             f32x4 o0, o1;
             h64t_forward<4>(vimg, vimg + IMG_FWD_FLOATS, vimg + IMG_FWD_FLOATS + 64, vimg + IMG_FWD_FLOATS + 128, xb, KS1, o0, o1, lane);
-            if (ok && g == 0) values_out[row] = o0[0] + o1[0];
+            if (ok && g == 0 && (MODE != 3 || values_out != nullptr)) values_out[row] = o0[0] + o1[0];
+            if constexpr (MODE == 3) {
+                float *const entropy_out = boot_rewards;
+                if (logp_out == nullptr && entropy_out == nullptr) continue;
+                h64t_forward<4>(pimg, pimg + IMG_FWD_FLOATS, pimg + IMG_FWD_FLOATS + 64, pimg + IMG_FWD_FLOATS + 128, xb, KS1, o0, o1, lane);
+                const int act = actions_out[ok ? row : 0];
+                float lp, ent;
+                h64t_eval(o0, o1, A, act, lp, ent, lane);
+                if (ok && g == 0) {
+                    if (logp_out != nullptr) logp_out[row] = lp;
+                    if (entropy_out != nullptr) entropy_out[row] = ent;
+                }
+            }
             if constexpr (MODE == 0) {
                 h64t_forward<4>(pimg, pimg + IMG_FWD_FLOATS, pimg + IMG_FWD_FLOATS + 64, pimg + IMG_FWD_FLOATS + 128, xb, KS1, o0, o1, lane);
                 int act;
@@ -1951,7 +2002,7 @@ __global__ __launch_bounds__(256) void policy_fwd_h64_kernel(const float *__rest
             }
         }
     }
-    if constexpr (MODE != 1) {
+    if constexpr (MODE == 0 || MODE == 2) {
         if (boot_trunc != nullptr) {
             for (int64_t tile = (int64_t)blockIdx.x * wpb + wave; tile < n_tiles; tile += (int64_t)gridDim.x * wpb) {
                 const int64_t row = (tile << 4) + r16;
@@ -1976,7 +2027,7 @@ static int launch_fwd_h64(const float *params, const PLayout &L, const float *ob
                           float *boot_rewards, hipStream_t s) {
     const int64_t tiles = ceil_div(n, 16);
     const int wpb = tiles >= 512 ? 4 : (tiles >= 64 ? 2 : 1);
-    const int smem = ((MODE == 0) ? 2 : 1) * FWD_IMG * 4;
+    const int smem = ((MODE == 0 || MODE == 3) ? 2 : 1) * FWD_IMG * 4;
     int64_t blocks = ceil_div(tiles, wpb);
     if (blocks > 2048) blocks = 2048;
     auto k = policy_fwd_h64_kernel<MODE>;
@@ -2019,7 +2070,7 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
     // forward pass must reproduce these log-probabilities).
     constexpr int KS2B = H / 32, KS1R = 6;
     const int KS1b = Kp1 >> 5;
-    const bool blk_pi = MODE == 0 && (blockIdx.x & 1) == 1;
+    const bool blk_pi = (MODE == 0 || MODE == 3) && (blockIdx.x & 1) == 1;
     bf16x8 w1r[BF ? NTW : 1][BF ? KS1R : 1], w2r[BF ? NTW : 1][BF ? KS2B : 1];
     float b1r[NTW], b2r[NTW];
     if constexpr (BF) {
@@ -2154,8 +2205,15 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
     };
     // MODE 0 runs the value net and the policy net of a row group on two different blocks (even / odd blockIdx): 4096 envs are only
     // 128 row groups, so this fills all 256 CUs and halves the dependent chain of a vector step.
-    constexpr int NR = MODE == 0 ? 2 : 1;
-    const int role = MODE == 0 ? (int)(blockIdx.x & 1) : 0;
+    // MODE 3 (evaluate_actions, see policy_fwd_kernel) splits the nets the same way; `actions_out` is read, `rewards` is entropy_out, and a
+    // block whose outputs were all passed as null has nothing to do.
+    constexpr int NR = (MODE == 0 || MODE == 3) ? 2 : 1;
+    constexpr bool EVAL = MODE == 3;
+    const int role = (MODE == 0 || MODE == 3) ? (int)(blockIdx.x & 1) : 0;
+    float *const entropy_out = rewards;  // (MODE 3)
+    if constexpr (EVAL) {
+        if (role == 0 ? values_out == nullptr : (logp_out == nullptr && entropy_out == nullptr)) return;  // (block-uniform, in front of every barrier)
+    }
     for (int64_t grp = blockIdx.x / NR; grp < n_groups; grp += gridDim.x / NR) {
         const int64_t row0 = grp * M;
         two_rt = row0 + 16 < n;
@@ -2200,7 +2258,7 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
                 else dense_head<1>(h2 + mt * 16 * ld, ld, H, V.W3t, V.b3, 1, vacc, lane);
             }
         }
-        if constexpr (MODE == 1 || MODE == 0) {
+        if constexpr (MODE == 1 || MODE == 0 || MODE == 3) {
             if (role == 0 && wave < 2 && r16 == 0)
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
@@ -2218,7 +2276,7 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
                     }
                 }
         }
-        if constexpr (MODE == 0) if (role == 1) {
+        if constexpr (MODE == 0 || MODE == 3) if (role == 1) {
             const Net P = pi_net(params, L);
             hidden(P, true);
             if (wave < 2) {
@@ -2237,6 +2295,16 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
                         const float sm = gsum16(e);
                         const float lse = m + logf(sm);
                         const float lp = x - lse;
+                        if constexpr (EVAL) {
+                            const int act = row < n ? static_cast<const int32_t *>(actions_out)[row] : 0;
+                            const float lpa = gsum16((r16 == act) ? lp : 0.0f);  // (column compare, as MODE 0 and policy_loss_tile)
+                            const float ent = -gsum16((e / sm) * (colok ? lp : 0.0f));
+                            if (r16 == r && row < n) {
+                                if (logp_out != nullptr) logp_out[row] = (act >= 0 && act < A) ? lpa : __builtin_nanf("");
+                                if (entropy_out != nullptr) entropy_out[row] = ent;
+                            }
+                            continue;
+                        }
                         int act;
                         if (deterministic) {
                             float mn = (colok && x == m) ? (float)r16 : 99.0f;
@@ -2264,13 +2332,17 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
                         const int64_t row = row0 + mt * 16 + g * 4 + r;
                         const uint32_t gi = env_offset + (uint32_t)row;
                         float lpsum = 0.0f;
+                        [[maybe_unused]] float entsum = 0.0f;
 #pragma unroll
                         for (int j = 0; j < 2; j++) {
                             const int col = 16 * j + r16;
                             if (col < A) {
                                 const float mu = acc[j][r], lsd = ls[col], sd = expf(lsd);
                                 float a = mu;
-                                if (!deterministic) {
+                                if constexpr (EVAL) {
+                                    if (row < n) a = static_cast<const float *>(actions_out)[row * A + col];
+                                    entsum += 1.4189385332046727f + lsd;
+                                } else if (!deterministic) {
                                     const float u1 = fmaxf(uniform01(mix32(rng_seed ^ (0x68E31DA4u + (uint32_t)col * 0x9E3779B9u), gi, rng_step)), 5.9604645e-08f);
                                     const float u2 = uniform01(mix32(rng_seed ^ (0xB5297A4Du + (uint32_t)col * 0x85EBCA77u), gi, rng_step));
                                     // Box-Muller on the hardware units: v_log (base 2, scaled), v_sqrt, and v_cos, whose argument is in revolutions
@@ -2279,10 +2351,19 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
                                 }
                                 const float d = a - mu;
                                 lpsum += -(d * d) / (2.0f * (sd * sd)) - lsd - 0.9189385332046727f;
-                                if (row < n) static_cast<float *>(actions_out)[row * A + col] = a;
+                                if constexpr (!EVAL)
+                                    if (row < n) static_cast<float *>(actions_out)[row * A + col] = a;
                             }
                         }
                         lpsum = gsum16(lpsum);
+                        if constexpr (EVAL) {
+                            entsum = gsum16(entsum);
+                            if (r16 == r && row < n) {
+                                if (logp_out != nullptr) logp_out[row] = lpsum;
+                                if (entropy_out != nullptr) entropy_out[row] = entsum;
+                            }
+                            continue;
+                        }
                         if (r16 == r && row < n) logp_out[row] = lpsum;
                     }
                 }
@@ -2297,6 +2378,7 @@ static int fwd_wide_smem_bytes(const PLayout &L) {
     return 32 * (ldx + 2 * ld) * 4;
 }
 
+// MODE 3 (tma_policy_evaluate_actions): `actions` is the input, `rewards` carries entropy_out; eligibility, grid caps and dispatch ids are MODE 0's
 template <int MODE>
 static int launch_fwd(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, uint32_t seed, uint32_t step, uint32_t env_offset,
                       int deterministic, void *actions, float *values, float *logp, const uint8_t *trunc, float gamma, float *rewards,
@@ -2307,6 +2389,7 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
     if (L.img_pi >= 0) {
         g_disp_fwd = TMA_DISPATCH_FWD_H64;
         if constexpr (MODE == 2) return launch_fwd_h64<2>(params, L, nullptr, n, 0, 0, 0, 1, nullptr, nullptr, nullptr, obs, trunc, gamma, rewards, s);
+        else if constexpr (MODE == 3) return launch_fwd_h64<3>(params, L, obs, n, 0, 0, 0, 1, actions, values, logp, nullptr, nullptr, 0.0f, rewards, s);
         else return launch_fwd_h64<MODE>(params, L, obs, n, seed, step, env_offset, deterministic, actions, values, logp, nullptr, nullptr, 0.0f, nullptr, s);
     }
     if (L.bf16) {
@@ -2316,7 +2399,7 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
         if (groups > 4096) groups = 4096;
         auto launchw = [&](auto k) -> int {
             TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smemw));
-            k<<<dim3((unsigned)(MODE == 0 ? 2 * groups : groups)), dim3(256), smemw, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions,
+            k<<<dim3((unsigned)((MODE == 0 || MODE == 3) ? 2 * groups : groups)), dim3(256), smemw, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions,
                                                                                            values, logp, trunc, gamma, rewards);
             return TMA_OK;
         };
@@ -2334,7 +2417,7 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
         if (groups > 4096) groups = 4096;
         auto launchw = [&](auto k) -> int {
             TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smemw));
-            k<<<dim3((unsigned)(MODE == 0 ? 2 * groups : groups)), dim3(256), smemw, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions,
+            k<<<dim3((unsigned)((MODE == 0 || MODE == 3) ? 2 * groups : groups)), dim3(256), smemw, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions,
                                                                                            values, logp, trunc, gamma, rewards);
             return TMA_OK;
         };
@@ -2446,6 +2529,19 @@ int tma_policy_act_bootstrap(const float *params, const tma_policy_dims *d, cons
         if (rc) return rc;
     }
     return launch_fwd<0>(params, d, obs, n, rng_seed, rng_step, env_offset, 0, actions_out, values_out, logp_out, nullptr, 0.0f, nullptr, (hipStream_t)stream);
+}
+
+int tma_policy_evaluate_actions(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n, float *values_out,
+                                float *logp_out, float *entropy_out, void *stream) {
+    g_disp_fwd = TMA_DISPATCH_NONE;
+    int rc = check_dims(d);  // (every refusal comes back before the first HIP call: enter() is what makes the device current)
+    if (rc) return rc;
+    if (!params || !obs || !actions) return fail(TMA_ERR_INVALID, "tma_policy_evaluate_actions: null buffer");
+    if (n < 1) return fail(TMA_ERR_INVALID, "tma_policy_evaluate_actions: n must be >= 1");
+    if (!values_out && !logp_out && !entropy_out) return fail(TMA_ERR_INVALID, "tma_policy_evaluate_actions: values_out, logp_out and entropy_out are all null");
+    rc = enter(d);
+    if (rc) return rc;
+    return launch_fwd<3>(params, d, obs, n, 0, 0, 0, 1, const_cast<void *>(actions), values_out, logp_out, nullptr, 0.0f, entropy_out, (hipStream_t)stream);
 }
 
 int tma_policy_values(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *values_out, void *stream) {

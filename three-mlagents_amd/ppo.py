@@ -159,6 +159,29 @@ class HipActorCriticPolicy:
                                              _lib.ptr(actions), _lib.ptr(values), _lib.ptr(logp), _lib.stream_ptr(self.device)))
         return actions, values, logp
 
+    def forward(self, obs: torch.Tensor, deterministic: bool = False, **rng):
+        """SB3's ActorCriticPolicy.forward(obs, deterministic) -> (actions, values, log_prob): `act` under the name code written against SB3's
+        policy object calls."""
+        return self.act(obs, deterministic=deterministic, **rng)
+
+    def evaluate_actions(self, obs: torch.Tensor, actions: torch.Tensor):
+        """SB3's ActorCriticPolicy.evaluate_actions(obs, actions) -> (values, log_prob, entropy), device tensors of n rows: the values, the
+        log-probabilities of the GIVEN actions and the entropies of the action distributions (tma_policy_evaluate_actions: the kernels `act` runs,
+        so `values` carries act's bits, and `log_prob` too where `actions` are the ones it drew).  actions: int32 [n] (Discrete; an action outside
+        [0, n_actions) gives that row a NaN log_prob) or float32 [n, act_dim] (Box, unclipped) -- the rollout buffer's dtypes and layout, anything
+        else is a ValueError."""
+        obs = self._rows(obs)
+        n = obs.shape[0]
+        want_shape, want_dtype = ((n, self.act_dim), torch.float32) if self.continuous else ((n,), torch.int32)
+        if not isinstance(actions, torch.Tensor) or actions.dtype != want_dtype or tuple(actions.shape) != want_shape:
+            raise ValueError(f"actions must be a {want_dtype} tensor of shape {list(want_shape)}, got "
+                             f"{getattr(actions, 'dtype', type(actions).__name__)} {list(getattr(actions, 'shape', []))}")
+        actions = actions.to(self.device).contiguous()
+        values, logp, entropy = (torch.empty((n,), dtype=torch.float32, device=self.device) for _ in range(3))
+        _lib.check(_lib.lib().tma_policy_evaluate_actions(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), _lib.ptr(actions), n,
+                                                          _lib.ptr(values), _lib.ptr(logp), _lib.ptr(entropy), _lib.stream_ptr(self.device)))
+        return values, logp, entropy
+
     def predict_values(self, obs: torch.Tensor) -> torch.Tensor:
         obs = self._rows(obs)
         values = torch.empty((obs.shape[0],), dtype=torch.float32, device=self.device)
@@ -695,6 +718,7 @@ class PPO:
             p["ev_train"].synchronize()
             self.check_collectives()
             stats = self._fold_train_stats(p["staging"])
+            stats.update(self._read_extra_stats(p["extra"]))
             s_ret, s_len, cnt = p["ep"]
             elapsed = max(ev0.elapsed_time(p["ev_train"]) * 1e-3, 1e-9)  # device timeline: learn() start -> the end of this iteration's update
             stats.update({"time/fps": p["num_timesteps"] / elapsed, "time/iterations": p["iteration"], "time/total_timesteps": p["num_timesteps"],
@@ -713,6 +737,8 @@ class PPO:
                 cb.on_rollout_end()
                 iteration += 1
                 logging = log_interval is not None and iteration % log_interval == 0
+                if logging:  # train/explained_variance of THIS rollout: queued behind its GAE, long before the next rollout overwrites `values`
+                    self._enqueue_explained_variance()
                 if logging and pipelined:
                     eng.detach_episode_log()
                     ev_roll = torch.cuda.Event()
@@ -729,6 +755,7 @@ class PPO:
                     staging = self._stats_staging(n_logged & 1)  # (alternates per LOGGED iteration: row k's buffer is folded before row k + 2 is copied into it)
                     n_logged += 1
                     _lib.check(_lib.lib().tma_ppo_stats_enqueue(_lib.ptr(self.workspace), _lib.ptr(staging), self._stream()))
+                    extra = self._enqueue_extra_stats((n_logged - 1) & 1)
                     ev_train = torch.cuda.Event(enable_timing=True)
                     ev_train.record(torch.cuda.current_stream(self.device))
                     now = time.time() - t0
@@ -736,13 +763,15 @@ class PPO:
                     t_prev = now
                     if pending is not None:
                         finish(pending)
-                    pending = dict(ev_train=ev_train, staging=staging, ep=ep, iteration=iteration, num_timesteps=self.num_timesteps, n_updates=self._n_updates,
+                    pending = dict(ev_train=ev_train, staging=staging, extra=extra, ep=ep, iteration=iteration, num_timesteps=self.num_timesteps, n_updates=self._n_updates,
                                    window=self._episode_window(lr_, ll_, ep[0], ep[1], ep[2]))
                 elif logging:
                     s_ret, s_len, cnt = eng.pop_episode_stats()
                     log = eng.pop_episode_log() if getattr(eng, "_log_cap", 0) > 0 else None
                     win = self._episode_window(log[0] if log else None, log[1] if log else None, s_ret, s_len, cnt)
+                    extra = self._enqueue_extra_stats(0)  # (in front of the pop: its stream synchronisation covers this copy too)
                     stats = self.pop_train_stats()
+                    stats.update(self._read_extra_stats(extra))
                     fps = self.num_timesteps / max(time.time() - t0, 1e-9)
                     stats.update({"time/fps": fps, "time/iterations": iteration, "time/total_timesteps": self.num_timesteps,
                                   "rollout/ep_rew_mean": win[0], "rollout/ep_len_mean": win[1],
@@ -790,6 +819,34 @@ class PPO:
             n = int(_lib.lib().tma_ppo_stats_staging_bytes())
             bufs = self._staging_bufs = [torch.zeros(n, dtype=torch.uint8).pin_memory() for _ in range(2)]
         return bufs[which]
+
+    # -- train/explained_variance, train/std, train/learning_rate, train/clip_range (SB3 PPO.train logs them; learn() only) --------------
+    def _enqueue_explained_variance(self) -> None:
+        """Queue tma_explained_variance over the rollout's `values` / `returns` planes on the compute stream; the result stays on the device (slot 0
+        of the extras vector) until _enqueue_extra_stats copies it out behind the update."""
+        if getattr(self, "_extra_dev", None) is None:
+            self._extra_dev = torch.zeros(1 + (self.policy.act_dim if self.policy.continuous else 0), dtype=torch.float64, device=self.device)
+            self._ev_scratch = torch.zeros(_lib.EV_SCRATCH_DOUBLES, dtype=torch.float64, device=self.device)
+            self._extra_host = [torch.zeros(self._extra_dev.numel(), dtype=torch.float64).pin_memory() for _ in range(2)]
+        b = self.buf
+        _lib.check(_lib.lib().tma_explained_variance(_lib.ptr(b["values"]), _lib.ptr(b["returns"]), self.n_steps * self.n_envs,
+                                                     _lib.ptr(self._ev_scratch), _lib.ptr(self._extra_dev), self._stream()))
+
+    def _enqueue_extra_stats(self, which: int) -> torch.Tensor:
+        """Behind the update: the explained variance and (Box heads) the updated log_std slice into one of two small pinned vectors, copied
+        stream-ordered and without waiting.  Read with _read_extra_stats once the stream has passed this point."""
+        pol = self.policy
+        if pol.continuous:  # (the float32 values widen exactly)
+            self._extra_dev[1:].copy_(pol.params[pol.offsets[12]:pol.offsets[12] + pol.act_dim])
+        host = self._extra_host[which]
+        host.copy_(self._extra_dev, non_blocking=True)
+        return host
+
+    def _read_extra_stats(self, host: torch.Tensor) -> dict[str, float]:
+        out = {"train/explained_variance": float(host[0]), "train/learning_rate": self.learning_rate, "train/clip_range": self.clip_range}
+        if self.policy.continuous:  # SB3: th.exp(self.policy.log_std).mean(), float32
+            out["train/std"] = float(torch.exp(host[1:].to(torch.float32)).mean())
+        return out
 
     def _fold_train_stats(self, staging: torch.Tensor) -> dict[str, float]:
         out = (C.c_double * 8)()
