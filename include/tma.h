@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 210
+#define TMA_VERSION 211
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -443,13 +443,17 @@ typedef struct {
  * Bicycle / Glider; 256-wide policies, bf16 or f32, on the Discrete tasks with up to 32 observations and on the Box-action tasks (Crawler /
  * Ant shapes; f32: up to 4096 envs, round 6).  Every other shape runs policy forward + env step launch by launch -- the same results bit for bit
  * (tests/test_ppo_gpu.py::test_native_rollout_equals_stepwise_composition); TMA_NO_WIDE_FUSED=1 / TMA_NO_CONT_F32_FUSED=1 force that path;
- * TMA_ROLL2=1 runs the 64-wide fused chunk on two waves per 16-env tile (round 5's kernel) instead of four.
+ * the 64-wide fused chunk runs eight waves per 16-env tile where every CU gets at most one tile at a time (fewer than 16 384 envs); TMA_ROLL4=1 runs it on
+ * four (round 6's kernel), TMA_ROLL2=1 on two (round 5's) -- the same results bit for bit.
  * deterministic != 0: actions are the distribution's mode (first maximal logit / Gaussian mean) instead of samples -- what SB3's
  * evaluate_policy(deterministic=True) asks of the policy (backend/mlagents/training.py:177-184,240-247); evaluation.py runs whole evaluation
  * chunks through this entry point and reads the finished episodes from the env's episode log. */
 int tma_rollout_collect(tma_env *env, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b, int t_begin, int t_end,
                         int T, uint32_t rng_seed, uint32_t rng_step0, uint32_t env_offset, double gamma, int compute_last_values,
                         int deterministic, void *stream);
+/* Test aid (ABI 211): waves per 16-env tile of the 64-wide fused chunk kernel the calling thread's last tma_rollout_collect launched -- 8, 4
+ * (TMA_ROLL4=1, and Glider always: its env step needs a four-wave workgroup's registers), 2 (TMA_ROLL2=1), 1 (16 384 envs and more: four tiles a workgroup, one wave each); 0 before the first such launch.  No GPU work. */
+int tma_debug_last_rollout_waves(void);
 /* GAE from done flags (episode_starts[t+1] == terminated[t] | truncated[t]): same arithmetic as tma_gae */
 int tma_gae_flags(const float *rewards, const float *values, const uint8_t *terminated, const uint8_t *truncated,
                   const float *last_values, double gamma, double gae_lambda, int T, int64_t N, float *adv_out, float *ret_out,

@@ -576,6 +576,71 @@ __device__ __forceinline__ void h64t_head_r(const H64FwdRegs<KS1C> &R, const f32
         }
 }
 
+// The same forward pass with every activation formed ONCE (round 8, rollout_chunk8_h64_kernel): a wave holds ONE 16-unit tile `c` of a net --
+// its layer-1 rows, its 16 layer-2 weights (one per k-step instead of four) and the two bias quads -- forms tanh(layer 1) of that tile only,
+// leaves it in LDS lane for lane, reads all four tiles back as the B operands of its layer-2 tile (k-steps i = 0..15: h64t_forward's order),
+// and leaves tanh(layer 2) of the tile in LDS for the head (h64t_head4: h64t_head_r's two alternating chains over four tiles read from LDS).
+// Per accumulator the operations and their order are h64t_forward's: same bits.
+template <int KS1C>
+struct H64TileRegs {
+    f32x4 b1, b2;
+    float w1[KS1C], w2[16];
+};
+struct H64HeadRegs {
+    f32x4 b3o;
+    float w3[16];
+};
+template <int KS1C>
+__device__ __forceinline__ void h64t_load_tile(const float *wimg, const float *b1, const float *b2, int KS1, int c, H64TileRegs<KS1C> &R, int lane) {
+    const int r16 = lane & 15, g = lane >> 4;
+    R.b1 = *reinterpret_cast<const f32x4 *>(b1 + 16 * c + 4 * g), R.b2 = *reinterpret_cast<const f32x4 *>(b2 + 16 * c + 4 * g);
+#pragma unroll
+    for (int ks = 0; ks < KS1C; ks++) R.w1[ks] = wimg[IMG_W1 + (4 * (ks < KS1 ? ks : 0) + g) * 64 + r16 * 4 + c];
+    const float *wrow = wimg + IMG_W2F + 4 * g * 64 + r16 * 4 + c;
+#pragma unroll
+    for (int i = 0; i < 16; i++) R.w2[i] = wrow[(16 * (i >> 2) + (i & 3)) * 64];
+}
+__device__ __forceinline__ void h64t_load_head(const float *wimg, const float *b3, H64HeadRegs &R, int lane) {
+    const int r16 = lane & 15, g = lane >> 4, acol = (r16 >> 2) + 4 * (r16 & 3);
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) R.w3[4 * j + r] = wimg[IMG_W3F + (16 * j + 4 * g + r) * 16 + acol];
+    R.b3o = f32x4{b3[g], b3[g + 4], b3[g + 8], b3[g + 12]};
+}
+// tanh(layer 1) of the wave's tile
+template <int KS1C>
+__device__ __forceinline__ f32x4 h64t_l1_tile(const H64TileRegs<KS1C> &R, const float (&xb)[KS1C], int KS1) {
+    f32x4 h = R.b1;
+#pragma unroll
+    for (int ks = 0; ks < KS1C; ks++) {
+        if (ks < KS1) h = mfma16(R.w1[ks], xb[ks], h);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) h[r] = tma_tanh(h[r]);
+    return h;
+}
+// tanh(layer 2) of the wave's tile from the four activated layer-1 tiles
+template <int KS1C>
+__device__ __forceinline__ f32x4 h64t_l2_tile(const H64TileRegs<KS1C> &R, const f32x4 (&h1)[4]) {
+    f32x4 h = R.b2;
+#pragma unroll
+    for (int i = 0; i < 16; i++) h = mfma16(R.w2[i], h1[i >> 2][i & 3], h);
+#pragma unroll
+    for (int r = 0; r < 4; r++) h[r] = tma_tanh(h[r]);
+    return h;
+}
+__device__ __forceinline__ void h64t_head4(const H64HeadRegs &R, const f32x4 (&t)[4], f32x4 &o0, f32x4 &o1) {
+    o0 = R.b3o, o1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            if ((4 * j + r) & 1) o1 = mfma16(R.w3[4 * j + r], t[j][r], o1);
+            else o0 = mfma16(R.w3[4 * j + r], t[j][r], o0);
+        }
+}
+
 __device__ __forceinline__ float xg_min(float v) { return xg_reduce(v, [](float a, float b) { return fminf(a, b); }); }
 
 // Categorical action and its log-probability from the head outputs of h64t_forward (output a = g + 4 r in register r of lane group g).

@@ -9,6 +9,7 @@
 #include "tma_h64_tile.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace tma {
 #include "tma_wide_bf16.h"  // bf16 fragment helpers and image layout shared with the update / forward kernels
@@ -488,6 +489,226 @@ __global__ __launch_bounds__(256) void rollout_chunk4_h64_kernel(EnvView v, cons
                 b.rewards[(int64_t)t * N + i] = rw[q * 16 + r16] + gv;
             }
         }
+    }
+    if (wave != 0) return;
+    if (active) {
+        T::pack(v.st, N, i, s);
+        v.ep_ret[i] = er;
+        v.cur_ep[i] = ce;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sret += __shfl_down(sret, o, 64);
+        slen += __shfl_down(slen, o, 64);
+        scnt += __shfl_down(scnt, o, 64);
+    }
+    if (lane == 0 && scnt > 0.0) {
+        double *slot = v.stats + (row0 >> 8) * 3;
+        atomicAdd(slot + 0, sret);
+        atomicAdd(slot + 1, slen);
+        atomicAdd(slot + 2, scnt);
+    }
+}
+
+// Eight-wave variant (round 8): every activation of a layer is formed ONCE.  In the four-wave kernel both waves of a net compute all of layer 1
+// and all sixteen tanh(h1) elements, and a wave's layer-2 MFMAs wait for its own tanh.  Here a wave holds ONE 16-unit tile of a net (h64t_l1_tile /
+// h64t_l2_tile): the activated tiles of a layer go through LDS lane for lane, one workgroup barrier per layer.
+//   waves 0..3 (SIMDs 0..3): policy tile `wave`; wave 0 then runs the policy head, the action and the env step -- the step's chain.
+//   wave 5: value tiles 0 and 1, wave 6: value tile 2, wave 7: value tile 3 and the value head.  Wave 4 only takes part in the barriers.
+// The matrix pipe belongs to a SIMD and a dependent MFMA chain keeps it busy, so a value wave's MFMAs beside a policy wave's on the same SIMD
+// would come straight out of the policy chain (waves w and w + 4 share a SIMD).  The value net therefore runs BEHIND the policy net inside a
+// step: layer 1 with the policy's (one to four MFMAs), layer 2 behind the second barrier -- while wave 0, alone on SIMD 0 (hence no value work on
+// wave 4), runs head, action and env step -- and the head one step later from a slot by step parity, the last step's behind the loop.  Nothing
+// needs a value before the GAE.
+//   per step: layer 1 | barrier | policy layer 2 | barrier | wave 0: head, action, env step; waves 5..7: value head of step t - 1, value
+//   layer 2; wave 1: the next step's noise; wave 2: rows of step t - 1 | [timeout bootstrap of step t - 1, block-uniform] | barrier
+// Same arithmetic per element as h64t_forward: same bits as the four-wave kernel (TMA_ROLL4=1 selects that one).
+template <class T>
+__global__ __launch_bounds__(512) void rollout_chunk8_h64_kernel(EnvView v, const float *__restrict__ params, PLayout L, ChunkPtrs b, int t0, int n_steps,
+                                                                 uint32_t rng_seed, uint32_t rng_step0, float gamma, int det) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int net = wave >> 2;                                 // 0: policy, 1: value
+    const int tileA = wave < 4 ? wave : (wave == 5 ? 0 : wave - 4);  // the wave's tile of its net (wave 5: tile 1 as well; wave 4: none)
+    const bool vwave = wave >= 5;
+    const int r16 = lane & 15, g = lane >> 4;
+    constexpr int D = T::OBS, KS1 = (D + 3) >> 2;
+    const int A = L.A;
+    float *vimg = smem, *pimg = smem + FWD_IMG;
+    float *X0 = smem + 2 * FWD_IMG;                    // [2][16][CH_LDX] observation tile, by step parity
+    float *XT0 = X0 + 2 * 16 * CH_LDX;                 // [2][16][CH_LDX] terminal observations of truncated rows
+    float *rw = XT0 + 2 * 16 * CH_LDX;                 // [2][16] reward of a truncated row (before the bootstrap)
+    int *trf = reinterpret_cast<int *>(rw + 32);       // [2][16] row truncated at this parity's step
+    int *flag = trf + 32;                              // [2] any row truncated
+    float *s1 = reinterpret_cast<float *>(flag + 4);   // [2 nets][4 tiles][64 lanes][4] tanh(layer 1)
+    float *s2p = s1 + 2048;                            // [4 tiles][64][4] tanh(layer 2) of the policy net
+    float *s2v = s2p + 1024;                           // [2][4][64][4] ... of the value net, by step parity (its head runs a step later)
+    float *bs1 = s2v + 2048, *bs2 = bs1 + 1024;        // [4][64][4] each: the two layers of the bootstrap pass
+    float *gnz = bs2 + 1024;                           // [2][64 lanes][4] Gumbel noise of a step, by step parity: formed a step ahead by wave 1
+    float *lgt = gnz + 512;                            // [2][64 lanes][4] the step's logits (o0 + o1), by step parity: wave 2 forms the log-probability
+    int *acts = reinterpret_cast<int *>(lgt + 512);    // [2][16] action, [2][16] reward bits, [2][16] terminated | truncated << 1 of the step
+    int *orw = acts + 32, *ofl = orw + 32;
+    stage_fwd_image(params + L.img_vf, vimg);
+    stage_fwd_image(params + L.img_pi, pimg);
+    const int64_t N = v.N;
+    const int64_t row0 = (int64_t)blockIdx.x << 4;
+    const int64_t i = row0 + r16;
+    const bool active = g == 0 && i < N;
+    typename T::S s;
+    double er = 0.0;
+    uint32_t ce = 0;
+    if (wave == 0 && active) {
+        T::unpack(v.st, N, i, s);
+        er = v.ep_ret[i];
+        ce = v.cur_ep[i];
+    }
+    if (wave == 0) {
+        for (int e = lane; e < 2 * 16 * CH_LDX; e += 64) {
+            const int row = e / CH_LDX, c = e - row * CH_LDX;
+            X0[e] = (row < 16 && row0 + row < N && c < D) ? b.obs[((int64_t)t0 * N + row0 + row) * D + c] : 0.0f;
+            XT0[e] = 0.0f;
+        }
+        if (lane < 2) flag[lane] = 0;
+        if (lane < 32) trf[lane] = 0;
+    }
+    const uint32_t genv = v.env_offset + (uint32_t)i;
+    if (wave == 1) *reinterpret_cast<f32x4 *>(gnz + lane * 4) = h64t_gumbel(rng_seed, genv, rng_step0 + (uint32_t)t0, det, lane);
+    __syncthreads();
+    double sret = 0.0, slen = 0.0, scnt = 0.0;
+    const float *img = net == 1 ? vimg : pimg;
+    H64TileRegs<KS1> TA, TB;  // the wave's tile; wave 5: its second
+    H64HeadRegs HR;           // waves 0 and 7: the net's head
+    h64t_load_tile<KS1>(img, img + IMG_FWD_FLOATS, img + IMG_FWD_FLOATS + 64, KS1, tileA, TA, lane);
+    h64t_load_tile<KS1>(img, img + IMG_FWD_FLOATS, img + IMG_FWD_FLOATS + 64, KS1, 1, TB, lane);
+    h64t_load_head(img, img + IMG_FWD_FLOATS + 128, HR, lane);
+    float *s1n = s1 + net * 1024;
+#ifdef TMA_ROLL_TICKS
+    unsigned long long rt_last = 0;
+#endif
+    auto read_obs = [&](const float *Xp, float (&xb)[KS1]) {
+#pragma unroll
+        for (int ks = 0; ks < KS1; ks++) xb[ks] = Xp[r16 * CH_LDX + ((4 * ks + g < D) ? 4 * ks + g : 16)];  // (column 16: a zero)
+    };
+    auto read4 = [&](const float *slot, f32x4 (&h)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) h[j] = *reinterpret_cast<const f32x4 *>(slot + j * 256 + lane * 4);
+        __builtin_amdgcn_sched_barrier(0);  // all four reads in flight before the chain's first MFMA (left alone hipcc reads a tile in front of its k-steps)
+    };
+    // tanh(layer 1) of this wave's tile(s) of the observation tile at `Xp` into `dst` ([4 tiles][64][4])
+    auto layer1 = [&](const float *Xp, float *dst) {
+        float xb[KS1];
+        read_obs(Xp, xb);
+        *reinterpret_cast<f32x4 *>(dst + tileA * 256 + lane * 4) = h64t_l1_tile<KS1>(TA, xb, KS1);
+        if (wave == 5) *reinterpret_cast<f32x4 *>(dst + 256 + lane * 4) = h64t_l1_tile<KS1>(TB, xb, KS1);
+    };
+    auto layer2 = [&](const float *src, float *dst) {
+        f32x4 h1[4];
+        read4(src, h1);
+        *reinterpret_cast<f32x4 *>(dst + tileA * 256 + lane * 4) = h64t_l2_tile<KS1>(TA, h1);
+        if (wave == 5) *reinterpret_cast<f32x4 *>(dst + 256 + lane * 4) = h64t_l2_tile<KS1>(TB, h1);
+    };
+    // wave 7: the value of step tt from the value net's activated layer-2 tiles at parity `par`
+    auto value_out = [&](int tt, int par) {
+        f32x4 h2[4], o0, o1;
+        read4(s2v + par * 1024, h2);
+        h64t_head4(HR, h2, o0, o1);
+        if (active) b.values[(int64_t)tt * N + i] = o0[0] + o1[0];
+    };
+    // timeout bootstrap of step tt (parity `par`): the value net once more on the terminal observations.  EVERY wave of the block must call it
+    // (two barriers inside); the condition it is called under is block-uniform.
+    auto bootstrap = [&](int tt, int par) {
+        if (vwave) layer1(XT0 + par * 16 * CH_LDX, bs1);
+        __syncthreads();
+        if (vwave) layer2(bs1, bs2);
+        __syncthreads();
+        if (wave == 7) {
+            f32x4 h2[4], b0, b1;
+            read4(bs2, h2);
+            h64t_head4(HR, h2, b0, b1);
+            if (active && trf[par * 16 + r16]) {
+                const float gv = gamma * (b0[0] + b1[0]);
+                b.rewards[(int64_t)tt * N + i] = rw[par * 16 + r16] + gv;
+            }
+        }
+    };
+    // wave 2: log-probability and rollout-buffer rows of step tt, left in LDS at parity `par` by wave 0 a step earlier -- h64t_logp is
+    // h64t_act_n's arithmetic on the same lane layout; the next observation is the tile the step after reads
+    auto flush_rows = [&](int tt, int par) {
+        const int a_ = acts[par * 16 + r16];
+        const float lp_ = h64t_logp(*reinterpret_cast<const f32x4 *>(lgt + par * 256 + lane * 4), A, a_, lane);
+        if (active) {
+            const int64_t off = (int64_t)tt * N + i;
+            const int fl = ofl[par * 16 + r16];
+            b.actions[off] = a_;
+            b.log_probs[off] = lp_;
+            b.terminated[off] = (uint8_t)(fl & 1);
+            b.truncated[off] = (uint8_t)(fl >> 1);
+            if (!(fl >> 1)) b.rewards[off] = __int_as_float(orw[par * 16 + r16]);
+            float o[D];
+            const float *Xr = X0 + (par ^ 1) * 16 * CH_LDX + r16 * CH_LDX;
+#pragma unroll
+            for (int c = 0; c < D; c++) o[c] = Xr[c];
+            store_obs<D>(b.obs + ((int64_t)(tt + 1) * N + i) * D, o);
+        }
+    };
+#ifdef TMA_ROLL_TICKS
+    rt_last = __builtin_amdgcn_s_memtime();
+#endif
+    for (int k = 0; k < n_steps; k++) {
+        const int t = t0 + k, p = k & 1, q = p ^ 1;
+        if (wave != 4) layer1(X0 + p * 16 * CH_LDX, s1n);
+        TMA_RTICK(0);
+        __syncthreads();
+        TMA_RTICK(1);
+        if (net == 0) layer2(s1, s2p);
+        TMA_RTICK(2);
+        __syncthreads();
+        TMA_RTICK(3);
+        const bool boot = k > 0 && flag[q];  // (block-uniform: written before the previous step's last barrier)
+        if (wave == 0) {
+            // only the action is on this wave's chain: the logits go to wave 2, which forms the log-probability and writes the step's rows
+            f32x4 h2[4], o0, o1;
+            read4(s2p, h2);
+            h64t_head4(HR, h2, o0, o1);
+#ifdef TMA_ROLL_TICKS
+            asm volatile("" : "+v"(o0), "+v"(o1));
+#endif
+            TMA_RTICK(4);
+            const f32x4 xs = o0 + o1;
+            *reinterpret_cast<f32x4 *>(lgt + p * 256 + lane * 4) = xs;
+            int act = h64t_argmax(xs, A, *reinterpret_cast<const f32x4 *>(gnz + p * 256 + lane * 4), lane);
+#ifdef TMA_ROLL_TICKS
+            asm volatile("" : "+v"(act));
+#endif
+            TMA_RTICK(5);
+            bool tr_flag = false;
+            if (active) {
+                float rew32;
+                bool te_flag = false;
+                chunk_env_step<T, false>(v, b, s, er, ce, N, i, t, act, 0.0f, X0 + q * 16 * CH_LDX + r16 * CH_LDX, XT0 + p * 16 * CH_LDX + r16 * CH_LDX, rew32,
+                                         tr_flag, false, sret, slen, scnt, &te_flag);  // truncated rows: the value net writes reward + bootstrap after the barrier
+                if (tr_flag) rw[p * 16 + r16] = rew32;
+                trf[p * 16 + r16] = tr_flag ? 1 : 0;
+                acts[p * 16 + r16] = act, orw[p * 16 + r16] = __float_as_int(rew32), ofl[p * 16 + r16] = (te_flag ? 1 : 0) | (tr_flag ? 2 : 0);
+            }
+            const bool any = __ballot(tr_flag) != 0ull;
+            if (lane == 0) flag[p] = any ? 1 : 0;
+            TMA_RTICK(6);
+        }
+        // the next step's noise and the previous step's rows on policy waves that idle from the second barrier to the end of the step
+        if (wave == 1) *reinterpret_cast<f32x4 *>(gnz + q * 256 + lane * 4) = h64t_gumbel(rng_seed, genv, rng_step0 + (uint32_t)(t + 1), det, lane);
+        if (wave == 2 && k > 0) flush_rows(t - 1, q);
+        if (wave == 7 && k > 0) value_out(t - 1, q);
+        if (vwave) layer2(s1 + 1024, s2v + p * 1024);
+        if (boot) bootstrap(t - 1, q);
+        __syncthreads();
+        TMA_RTICK(7);
+    }
+    if (n_steps > 0) {  // behind the loop: rows and value of the chunk's last step, its bootstrap
+        const int q = (n_steps - 1) & 1, t = t0 + n_steps - 1;
+        if (wave == 2) flush_rows(t, q);
+        if (wave == 7) value_out(t, q);
+        if (flag[q]) bootstrap(t, q);
     }
     if (wave != 0) return;
     if (active) {
@@ -2110,6 +2331,15 @@ static int launch_chunk_wide(tma_env *env, const float *params, const PLayout &L
     }
 }
 
+// waves per 16-env tile of the calling thread's last 64-wide fused chunk launch (tma_debug_last_rollout_waves)
+static thread_local int g_roll_waves = 0;
+
+// a task whose env step needs more registers than a wave of an eight-wave workgroup has (256) stays on the four-wave kernel: T::ROLL8 = false
+template <class T, class = void>
+struct roll8_task : std::true_type {};
+template <class T>
+struct roll8_task<T, std::enable_if_t<!T::ROLL8>> : std::false_type {};
+
 template <class T>
 static int launch_chunk(tma_env *env, const float *params, const PLayout &L, const ChunkPtrs &b, int t0, int n, uint32_t rng_seed, uint32_t rng_step0,
                         float gamma, int det, hipStream_t s) {
@@ -2117,7 +2347,20 @@ static int launch_chunk(tma_env *env, const float *params, const PLayout &L, con
     const int wpb = tiles >= 1024 ? 4 : 1;  // BASELINE shape (256 tiles): one wave per block so all 256 CUs take part
     const int smem = (2 * FWD_IMG + wpb * 2 * 16 * CH_LDX) * 4;
     static const bool roll2 = getenv("TMA_ROLL2") != nullptr;  // A/B switch: the two-wave kernel
-    if (wpb == 1 && !roll2) {  // one tile per CU: each net on two waves (round 6)
+    static const bool roll4 = getenv("TMA_ROLL4") != nullptr;  // A/B switch: the four-wave kernel
+    g_roll_waves = wpb != 1 ? 1 : (roll2 ? 2 : (roll4 ? 4 : 8));
+    if constexpr (!roll8_task<T>::value) {
+        if (g_roll_waves == 8) g_roll_waves = 4;
+    } else if (wpb == 1 && !roll2 && !roll4) {  // one tile per CU: one tile of a net per wave, every activation formed once (round 8)
+        const int smem8 = (2 * FWD_IMG + 4 * 16 * CH_LDX + 32 + 32 + 4 + 2048 + 1024 + 2048 + 1024 + 1024 + 512 + 512 + 96) * 4;
+        static_assert((2 * FWD_IMG + 4 * 16 * CH_LDX + 32 + 32 + 4 + 2048 + 1024 + 2048 + 1024 + 1024 + 512 + 512 + 96) * 4 <= 160 * 1024, "LDS of a CU");
+        auto k8 = rollout_chunk8_h64_kernel<T>;
+        if (smem8 > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, smem8));
+        k8<<<dim3((unsigned)tiles), dim3(512), smem8, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
+        TMA_LAUNCH_CHECK();
+        return TMA_OK;
+    }
+    if (wpb == 1 && !roll2) {  // each net on two waves (round 6)
         const int smem4 = (2 * FWD_IMG + 4 * 16 * CH_LDX + 32 + 32 + 4 + 1024 + 512 + 512 + 512 + 96) * 4;
         auto k4 = rollout_chunk4_h64_kernel<T>;
         if (smem4 > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k4), hipFuncAttributeMaxDynamicSharedMemorySize, smem4));
@@ -2394,6 +2637,8 @@ extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_
     }
     return TMA_OK;
 }
+
+extern "C" int tma_debug_last_rollout_waves(void) { return tma::g_roll_waves; }
 
 #ifdef TMA_ROLL_TICKS
 // diagnostic build only: read (reset != 0: clear) the per-phase cycle sums of the f32 wide rollout kernel

@@ -938,6 +938,7 @@ struct BrickBreakTask {
 struct GliderTask {
     static constexpr int ID = TMA_TASK_GLIDER, OBS = 16, NACT = 5, ADIM = 1, MAXSTEPS = 4000, SW = 26, RW = 7, SDIM = 14;
     static constexpr bool USES_MT = true, NATIVE_TRUNC_RULE = false, FUSED_ROLLOUT = true;
+    static constexpr bool ROLL8 = false;  // 64-wide fused rollout on four waves: this env step spills registers at the 256 a wave of eight has (tma_rollout.hip)
     struct S {
         double pos[3], vel[3], rot[3], av[3];
         int wp, steps;

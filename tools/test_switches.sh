@@ -30,3 +30,5 @@ run "TMA_NO_CONT_F32_FUSED=1" "tests/test_ppo_gpu.py" "crawler or ant"   # the f
 run "TMA_ROLL2=1" "tests/test_ppo_gpu.py tests/test_rollout_oracle_gpu.py" "rollout"   # the headline rollout on two waves per tile (round 5) instead of four
 # round 7
 run "TMA_H64_RUNTIME_A=1" "tests/test_ppo_gpu.py tests/test_policy_dispatch_gpu.py tests/test_rollout_oracle_gpu.py"   # the H = 64 gradient kernel with the head width read at run time at every shape (the headline shape has a compile-time instantiation)
+# round 8
+run "TMA_ROLL4=1" "tests/test_ppo_gpu.py tests/test_rollout_oracle_gpu.py tests/test_env_gpu.py tests/test_bench_gpu.py"   # the headline rollout on four waves per tile (round 6) instead of eight
