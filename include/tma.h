@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 211
+#define TMA_VERSION 212
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -289,10 +289,20 @@ int tma_ppo_train_epoch_local(float *params, const tma_policy_dims *d, const tma
  * epoch kernel takes the shape (batch_size 256: H = 64 fast-path layouts, and the reference's default 256 x 256 f32 policy with a Discrete head
  * and <= 32 observations) and n_epochs * T * N sample offsets fit the workspace cache (2^22), ALL the epochs run as ONE launch -- the
  * reference's own 1- and 8-env schedules are 4 and 32 optimizer steps per epoch, where a launch per epoch is mostly launch; otherwise (and
- * when such a launch cannot place its workgroups) exactly tma_ppo_train_epoch_local per epoch.  Same results either way. */
+ * when such a launch cannot place its workgroups) exactly tma_ppo_train_epoch_local per epoch.  Same results either way.
+ * ABI 212, H = 64 fast-path policies at minibatches of more than 2 048 rows (the eight-wave gradient kernel): the epochs of the call are ONE
+ * chain of gradient launches.  There is no tma_ppo_epoch_prepare launch: one adv_partial_kernel launch over the call's first minibatch, then
+ * gradient launch k leaves the sample offsets and advantage partials of minibatch k + 1 -- at an epoch's end: of minibatch 0 of the next
+ * epoch -- where tma_ppo_epoch_prepare would have (its value-net workgroups do it once their own work is stored; a tail minibatch of
+ * <= 2 048 rows, before and behind it, gets a launch over that minibatch alone).  Every epoch ends in the ordinary optimizer launch.
+ * Bit-identical to the per-epoch sequence, which TMA_NO_PREP_FOLD=1 in the environment (read per call) selects. */
 int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch0, int n_epochs,
                                int64_t batch_size, const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step,
                                double lr, double beta1, double beta2, double eps, double max_grad_norm, void *workspace, void *stream);
+/* Test aid (ABI 212): advantage pre-passes of the calling thread's last tma_ppo_train_epoch_local / tma_ppo_train_epochs_local call -- how many
+ * rode on a gradient launch (*folded_out) and how many were launches of their own (*standalone_out: a tma_ppo_epoch_prepare launch over
+ * a whole epoch counts as one).  No GPU work. */
+int tma_debug_last_prep_fold(int *folded_out, int *standalone_out);
 /* One epoch of PPO.train on ONE RANK of a data-parallel job (env shards per GPU, one gradient all-reduce per
  * minibatch; the reference itself is one process, backend/mlagents/training.py:71-89,150): for every minibatch of batch_size local rows --
  * tma_ppo_minibatch_grad, then `allreduce(ctx, grad, n_trainable)` (the caller's collective: SUM over the ranks, in place, enqueued on

@@ -94,6 +94,7 @@ SIGNATURES = {
     "tma_debug_last_grad_kernel_us": (_i32, [C.POINTER(C.c_float)]),
     "tma_debug_last_dispatch": (_i32, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "tma_debug_last_rollout_waves": (_i32, []),
+    "tma_debug_last_prep_fold": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
     "tma_ppo_epoch_prepare": (_i32, [C.POINTER(Rollout), C.POINTER(Minibatch), _i64, _pd, _vp, _vp]),
     "tma_ppo_epoch_adv_sums": (_i32, [_vp, _pd, _i64, _i64, _vp, _i32, _vp]),
     "tma_ppo_adam_step": (_i32, [_vp, _vp, _vp, _vp, _pd, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp]),

@@ -9,6 +9,10 @@
 
 namespace tma {
 
+#ifdef TMA_H64_TICKS
+static __device__ unsigned long long g_h64_tail_ticks;  // diagnostic build: the value blocks' tail phase (tma_debug_h64_tail_ticks)
+#endif
+
 // ------------------------------------------------------------------------------------------
 // H = 64 specialisation (BASELINE configs[1]): persistent waves keep the WHOLE parameter gradient of both nets in MFMA
 // accumulators (210 VGPRs) while they walk their share of the 16-sample tiles -- dW += X^T.dZ is accumulated through the
@@ -455,7 +459,8 @@ __device__ __forceinline__ void fold_adam_into_image(const AdamFold &f, const PL
 template <bool IS_PI, int DT, bool DIRECT = false, int AT = 0>  // AT > 0: compile-time head width of the policy net, 0: runtime L.A
 __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params, const PLayout &L, const Rollout &rb, const Minibatch &mb,
                                                const HParams &hp, const double *__restrict__ adv_part, int n_part, float *__restrict__ slab,
-                                               double *__restrict__ stat_slot, float *smem, int n_blocks_net, int block_net, const AdamFold &fold) {
+                                               double *__restrict__ stat_slot, float *smem, int n_blocks_net, int block_net, const AdamFold &fold,
+                                               const PrepNext &next) {
 #ifdef TMA_H64_TICKS
     const unsigned long long kern_t0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -605,12 +610,31 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
         const int q = IS_PI ? (threadIdx.x == 0 ? 0 : threadIdx.x + 1) : (threadIdx.x == 0 ? 1 : -1);
         if (q >= 0) stat_slot[q] += s;
     }
+    // ---- tail phase, value blocks of the eight-wave kernel only: the advantage pre-pass of the NEXT minibatch (PrepNext).  This block's
+    // slab stores are issued and its statistics written; the policy blocks of the launch -- its pole -- are still in their loop.  Threads
+    // 0..255 of value block b run partial blocks b, b + n_blocks_net, ... exactly as adv_partial_kernel's blocks would.
+    if constexpr (!IS_PI && !DIRECT) {
+        if (next.count > 0) {  // (uniform)
+            __shared__ double prep_s1[4], prep_s2[4];
+            const Minibatch nm{nullptr, next.perm_seed, next.perm_epoch, next.start, next.count, next.total, nullptr, next.count, nullptr, 0};
+            int nb = (int)((next.count + 1023) / 1024);
+            if (nb > ADV_BLOCKS) nb = ADV_BLOCKS;
+            for (int pb = block_net; pb < nb; pb += n_blocks_net) {
+                adv_partial_block(next.adv, nm, next.T, next.N, nb, pb, (int)threadIdx.x, next.partials_out, next.offs_out, next.want_sums != 0, prep_s1,
+                                  prep_s2);
+                __syncthreads();  // (prep_s1 / prep_s2 serve the next round)
+            }
+#ifdef TMA_H64_TICKS
+            if (tick_on && lane == 0) g_h64_tail_ticks += __builtin_amdgcn_s_memtime() - loop_t1;  // loop end -> end of the tail phase (slot 13 + the phase)
+#endif
+        }
+    }
 }
 
 template <int DT, int VER, int AT = 0>  // AT > 0 (VER 2): compile-time head width -- <4, 2, 5> is the headline shape (GridWorld: 4 observations, 5 actions)
 __global__ __launch_bounds__(512, 2) void ppo_grad_h64_kernel(const float *__restrict__ params, PLayout L, Rollout rb, Minibatch mb, HParams hp,
                                                               const double *__restrict__ adv_part, int n_part, float *__restrict__ slabs,
-                                                              double *__restrict__ stat_slots, AdamFold fold) {
+                                                              double *__restrict__ stat_slots, AdamFold fold, PrepNext next) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // policy blocks first, value blocks behind them: with 128 pairs the two blocks of pair p (same tiles, same sample records) are workgroups p and
     // 128 + p -- dispatched round-robin over the 8 XCDs they land on the SAME XCD, so the second reader of a record finds its line in that L2
@@ -622,8 +646,8 @@ __global__ __launch_bounds__(512, 2) void ppo_grad_h64_kernel(const float *__res
         if (pi_block) grad_h64_body<true, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair);
         else grad_h64_body<false, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair);
     } else {
-        if (pi_block) grad_h64t_body<true, DT, false, AT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold);
-        else grad_h64t_body<false, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold);
+        if (pi_block) grad_h64t_body<true, DT, false, AT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
+        else grad_h64t_body<false, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
     }
 }
 
@@ -636,8 +660,8 @@ __global__ __launch_bounds__(256, 1) void ppo_grad_h64_small_kernel(const float 
     const int pair = blockIdx.x >> 1, n_pairs = gridDim.x >> 1;
     float *slab = slabs + (int64_t)pair * L.P;
     double *slot = stat_slots + (int64_t)pair * 8;
-    if ((blockIdx.x & 1) == 0) grad_h64t_body<true, DT, true>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold);
-    else grad_h64t_body<false, DT, true>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold);
+    if ((blockIdx.x & 1) == 0) grad_h64t_body<true, DT, true>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, PrepNext{});
+    else grad_h64t_body<false, DT, true>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, PrepNext{});
 }
 
 }  // namespace tma
@@ -652,14 +676,23 @@ static int grad_h64_smem_bytes(const PLayout &L, int wpb, int ver) {
     return tile > flush ? tile : flush;
 }
 
+static int grad_h64_version() {
+    static const int ver = getenv("TMA_H64_V1") ? 1 : 2;  // (development switch: the round-1 LDS-round-trip tile chain)
+    return ver;
+}
+bool tma_grad_h64_carries_prep(int64_t count) { return grad_h64_version() == 2 && ceil_div(count, 16) > H64_BLOCKS; }
+
 // H = 64 persistent gradient kernel over one minibatch (>= 256 samples): 2 x n_pairs blocks of 8 waves, block pair p writes slab p.
 // Returns the number of slabs written through *n_slabs_out (the caller runs slab_reduce_kernel over them).
 int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R, const Minibatch &M, const HParams &hpar, const double *adv_part,
-                        int n_part, float *slabs, double *slots, int *n_slabs_out, hipStream_t s, const AdamFold *foldp) {
+                        int n_part, float *slabs, double *slots, int *n_slabs_out, hipStream_t s, const AdamFold *foldp, const PrepNext *nextp) {
     AdamFold fold{};
     if (foldp) fold = *foldp;
-    static const int ver = getenv("TMA_H64_V1") ? 1 : 2;  // (development switch: the round-1 LDS-round-trip tile chain)
+    PrepNext next{};
+    if (nextp) next = *nextp;
+    const int ver = grad_h64_version();
     if (ver == 1 && foldp && foldp->grad) return TMA_ERR_INVALID;  // the round-1 chain has no optimizer prologue: refuse instead of dropping the step
+    if (next.count > 0 && !tma_grad_h64_carries_prep(M.count)) return TMA_ERR_INVALID;  // only the eight-wave kernel has the tail phase: refuse instead of dropping the pre-pass
     static const int stagger = getenv("TMA_H64_STAGGER") ? atoi(getenv("TMA_H64_STAGGER")) : 0;
     static const bool runtime_a = getenv("TMA_H64_RUNTIME_A") != nullptr;  // (A/B and test switch: the runtime-head-width kernel at every shape)
     HParams hps = hpar;
@@ -684,7 +717,7 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
     if (blocks4 > H64_BLOCKS) blocks4 = H64_BLOCKS;
     auto launch = [&](auto k) -> int {
         if (smem4 > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem4));
-        k<<<dim3((unsigned)(2 * blocks4)), dim3(64 * wpb4), smem4, s>>>(params, L, R, M, hps, adv_part, n_part, slabs, slots, fold);
+        k<<<dim3((unsigned)(2 * blocks4)), dim3(64 * wpb4), smem4, s>>>(params, L, R, M, hps, adv_part, n_part, slabs, slots, fold, next);
         return TMA_OK;
     };
     int rc;
@@ -698,6 +731,16 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
 }
 
 #ifdef TMA_H64_TICKS
+// value block 0, wave 0: cycles from the end of its tile loop to the end of the tail phase, summed over the launches that carried one
+extern "C" int tma_debug_h64_tail_ticks(unsigned long long *out, int reset) {
+    TMA_HIP(hipDeviceSynchronize());
+    if (out) TMA_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_h64_tail_ticks), sizeof(unsigned long long)));
+    if (reset) {
+        unsigned long long z = 0;
+        TMA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_h64_tail_ticks), &z, sizeof(z)));
+    }
+    return TMA_OK;
+}
 extern "C" int tma_debug_h64_ticks(unsigned long long *out32, int reset) {
     TMA_HIP(hipDeviceSynchronize());
     if (out32) TMA_HIP(hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_h64_ticks), sizeof(unsigned long long) * 32));

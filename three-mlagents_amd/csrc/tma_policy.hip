@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict
 // minibatch advantage statistics (mean, unbiased std) -- one block; SB3 PPO.train normalize_advantage
 // ------------------------------------------------------------------------------------------
 // pass 1: up to ADV_BLOCKS blocks, each sums a contiguous slice of the (permuted) minibatch -> (sum, sum of squares) partials
-constexpr int ADV_BLOCKS = 128;
+// (adv_partial_block, tma_ppo_types.h: the body this kernel shares with the tail phase of the H = 64 gradient kernel)
 // gridDim.y > 1 (tma_ppo_epoch_prepare): blockIdx.y = minibatch k of an epoch split into chunks of `batch` rows; partials and
 // offsets of minibatch k land at partials + 2 * k * gridDim.x and offs_out + k * batch.
 __global__ __launch_bounds__(256) void adv_partial_kernel(const float *__restrict__ adv, Minibatch mb, int T, int64_t N, double *partials,
@@ -300,26 +300,7 @@ __global__ __launch_bounds__(256) void adv_partial_kernel(const float *__restric
     int nb = (int)((mb.count + 1023) / 1024);  // partial blocks this minibatch uses: the same split as a stand-alone launch
     if (nb > (int)gridDim.x) nb = gridDim.x;
     if ((int)blockIdx.x >= nb) return;
-    const int64_t per = (mb.count + nb - 1) / nb;
-    const int64_t j0 = (int64_t)blockIdx.x * per, j1 = (j0 + per < mb.count) ? j0 + per : mb.count;
-    double a = 0.0, b = 0.0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) {
-        const int64_t off = sample_offset(mb, mb.start + j, T, N);
-        if (offs_out) offs_out[j] = (int32_t)off;
-        const double x = (double)adv[off];
-        a += x;
-        b += x * x;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_down(a, o, 64);
-        b += __shfl_down(b, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) s1[threadIdx.x >> 6] = a, s2[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = (s1[0] + s1[1]) + (s1[2] + s1[3]);
-        partials[2 * blockIdx.x + 1] = (s2[0] + s2[1]) + (s2[2] + s2[3]);
-    }
+    adv_partial_block(adv, mb, T, N, nb, (int)blockIdx.x, (int)threadIdx.x, partials, offs_out, true, s1, s2);
 }
 // pass 2: one wave folds the partials in a fixed order -> mean, unbiased std (SB3: advantages.std() + 1e-8)
 __global__ void adv_final_kernel(const double *partials, int n_part, int64_t count, float *ws_adv) {
@@ -2565,7 +2546,8 @@ int tma_policy_bootstrap(const float *params, const tma_policy_dims *d, const fl
 
 // fold (H = 64 fast path only): the previous minibatch's optimizer step, done in the prologue of this gradient launch (AdamFold)
 static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_minibatch *mbi, const tma_ppo_hparams *hp,
-                               float *grad, void *workspace, void *stream, const AdamFold *fold, int overwrite, const PeerPush *push = nullptr) {
+                               float *grad, void *workspace, void *stream, const AdamFold *fold, int overwrite, const PeerPush *push = nullptr,
+                               const PrepNext *next = nullptr /* the next minibatch's pre-pass, carried by this launch (eight-wave H = 64 kernel only) */) {
     g_disp_grad = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
@@ -2631,7 +2613,7 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
         int lrc;
         {
             GradTimer timer(s);
-            lrc = tma_launch_grad_h64(params, L, R, M, hpar, adv_part, nbk, slabs, slots, &blocks4, s, fold);
+            lrc = tma_launch_grad_h64(params, L, R, M, hpar, adv_part, nbk, slabs, slots, &blocks4, s, fold, next);
         }
         if (lrc) return lrc;
         slab_reduce_kernel<<<dim3((unsigned)ceil_div(L.P, 64)), dim3(256), 0, s>>>(slabs, (int)blocks4, L.P, grad, -1, 0, 0, sq_partials(ws, L), overwrite,
@@ -2639,7 +2621,7 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
         TMA_LAUNCH_CHECK();
         return TMA_OK;
     }
-    if (fold || overwrite || push) return fail(TMA_ERR_INVALID, "internal: folded optimizer step outside the H = 64 fast path");
+    if (fold || overwrite || push || next) return fail(TMA_ERR_INVALID, "internal: folded optimizer step outside the H = 64 fast path");
     if (L.bf16) {  // column-parallel bf16-MFMA kernel (tma_bf16.hip) + deterministic slab reduction
         g_disp_grad = TMA_DISPATCH_GRAD_BF16;
         if ((int64_t)rb->T * rb->N * L.D >= (int64_t)1 << 31)  // (its observation gather indexes the buffer with 32-bit arithmetic)
@@ -2891,6 +2873,111 @@ static int persistent_epochs(float *params, const tma_policy_dims *d, const tma_
     return TMA_OK;
 }
 
+// advantage pre-passes of the calling thread's last tma_ppo_train_epoch(s)_local call: carried by a gradient launch / launches of their own
+// (tma_debug_last_prep_fold)
+static thread_local int g_prep_folded = 0, g_prep_standalone = 0;
+
+// H = 64 fast path of the single-GPU epoch loop: every minibatch on the LDS-image kernel (>= 256 rows) and more than one of them
+static bool h64_fold_eligible(const PLayout &L, int64_t total, int64_t batch_size) {
+    const bool no_fold = getenv("TMA_NO_ADAM_FOLD") != nullptr;  // test / measurement switch: one optimizer launch per minibatch (read per call)
+    const int64_t tail = total % batch_size;
+    return L.img_pi >= 0 && total <= OFFS_CAP && batch_size >= 256 && (tail == 0 || tail >= 256) && total > batch_size && !no_fold;
+}
+
+// `n_epochs` epochs of the H = 64 fast path (h64_fold_eligible).
+// AdamFold: the optimizer step of minibatch k runs in the prologue of gradient launch k + 1 (every workgroup redoes it for its net and
+// builds its weight image from the results), so a minibatch costs two launches (gradient, slab reduction) instead of three; the state
+// ping-pongs between (params, exp_avg, exp_avg_sq) and the workspace copy, and the last step is the ordinary optimizer launch, which leaves
+// everything (derived copies and images included) in the caller's buffers.  Same arithmetic on the same inputs as the unfolded sequence.
+// PrepNext (minibatches of more than 2 048 rows: the eight-wave kernel): no tma_ppo_epoch_prepare launch in front of an epoch -- gradient
+// launch k carries the pre-pass of minibatch k + 1 (the epoch's last one: of minibatch 0 of the next epoch) in the idle tail of its value
+// blocks; launch k reads region k of the offsets / partials and writes region k + 1 (n_mb >= 2: never the same), the kernel boundary
+// hands over.  The call's first minibatch, and any minibatch whose predecessor or which itself runs on the small kernel (a tail of <= 2 048
+// rows), get adv_partial_kernel over that minibatch alone.  Every epoch still ends in the ordinary optimizer launch: folding that step
+// into the next epoch's first gradient launch as well was built and did not show in the headline.
+// TMA_NO_PREP_FOLD=1 (read per call): one prepare launch per epoch, the sequence before.  Bit-identical.
+static int h64_fold_epochs(float *params, const tma_policy_dims *d, const tma_rollout *rb, const PLayout &L, uint32_t perm_seed, uint32_t perm_epoch0, int n_epochs,
+                           int64_t batch_size, const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr,
+                           double beta1, double beta2, double eps, double max_grad_norm, void *workspace, void *stream) {
+    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->advantages || !rb->returns) return fail(TMA_ERR_INVALID, "rollout view has a null buffer");
+    const int64_t total = (int64_t)rb->T * rb->N, n_mb = ceil_div(total, batch_size);
+    char *ws = static_cast<char *>(workspace);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t Pp = ((int64_t)L.P + 3) & ~(int64_t)3;
+    float *alt = reinterpret_cast<float *>(ws + fold_state_offset(L));
+    float *bufs[2][3] = {{params, exp_avg, exp_avg_sq}, {alt, alt + Pp, alt + 2 * Pp}};
+    int cur = 0;
+    const double *sqp = sq_partials(ws, L);
+    const bool chain = getenv("TMA_NO_PREP_FOLD") == nullptr && tma_grad_h64_carries_prep(batch_size);
+    const int64_t offs_base = WS_SLABS + (int64_t)slab_cap(L) * L.P * 4;  // the regions tma_ppo_epoch_prepare fills
+    int32_t *offs_all = reinterpret_cast<int32_t *>(ws + offs_base);
+    double *part_all = reinterpret_cast<double *>(ws + offs_base + OFFS_CAP * 4);
+    int stride = (int)ceil_div(batch_size, 1024);
+    if (stride > ADV_BLOCKS) stride = ADV_BLOCKS;
+    auto prep_of = [&](int e, int64_t k) {  // minibatch k of epoch e and where its offsets and partials belong
+        const int64_t start = k * batch_size, count = start + batch_size <= total ? batch_size : total - start;
+        return PrepNext{rb->advantages, offs_all + start, part_all + 2 * k * stride, perm_seed, perm_epoch0 + (uint32_t)e, start, count, total, rb->N, rb->T,
+                        hp->normalize_advantage ? 1 : 0};
+    };
+    bool ready = false;  // the coming minibatch's pre-pass rides on the gradient launch before it
+    int64_t step = first_step;
+    int rc;
+    for (int e = 0; e < n_epochs; e++) {
+        if (!chain) {
+            const tma_minibatch ep{nullptr, perm_seed, perm_epoch0 + (uint32_t)e, 0, total, 0, 0};
+            rc = tma_ppo_epoch_prepare(rb, &ep, batch_size, d, workspace, stream);
+            if (rc) return rc;
+            g_prep_standalone++;
+        }
+        for (int64_t k = 0; k < n_mb; k++, step++) {
+            const PrepNext me = prep_of(e, k);
+            if (chain && !ready) {  // nobody carried it: the pre-pass over this minibatch alone
+                const Minibatch M{nullptr, me.perm_seed, me.perm_epoch, me.start, me.count, total, nullptr, me.count, nullptr, 0};
+                int nbk = (int)ceil_div(me.count, 1024);
+                if (nbk > ADV_BLOCKS) nbk = ADV_BLOCKS;
+                adv_partial_kernel<<<dim3(nbk), dim3(256), 0, s>>>(rb->advantages, M, rb->T, rb->N, me.partials_out, me.offs_out);
+                TMA_LAUNCH_CHECK();
+                g_prep_standalone++;
+            }
+            ready = false;
+            PrepNext nx{};
+            if (chain && (k + 1 < n_mb || e + 1 < n_epochs)) {
+                nx = k + 1 < n_mb ? prep_of(e, k + 1) : prep_of(e + 1, 0);
+                ready = tma_grad_h64_carries_prep(me.count) && tma_grad_h64_carries_prep(nx.count);  // both sides on the eight-wave kernel
+                if (ready) g_prep_folded++;
+            }
+            const tma_minibatch mb{nullptr, perm_seed, me.perm_epoch, me.start, me.count, batch_size, 0};
+            AdamFold f{};
+            if (k > 0) {  // the step of the previous minibatch (index step - 1)
+                const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
+                f = AdamFold{grad, sqp, (int)ceil_div(L.P, 64), bufs[cur][0], bufs[cur][1], bufs[cur][2], bufs[cur ^ 1][0], bufs[cur ^ 1][1],
+                             bufs[cur ^ 1][2], (float)max_grad_norm, (float)(lr / bc1), (float)beta1, (float)beta2, (float)sqrt(bc2), (float)eps,
+                             reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f};
+            }
+            rc = minibatch_grad_impl(params, d, rb, &mb, hp, grad, workspace, stream, k > 0 ? &f : nullptr, k > 0 ? 1 : 0, nullptr, ready ? &nx : nullptr);
+            if (rc) return rc;
+            if (k > 0) cur ^= 1;
+        }
+        const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
+        adam_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
+            params, grad, exp_avg, exp_avg_sq, L, sqp, (int)ceil_div(L.P, 64), (float)max_grad_norm, (float)(lr / bc1), (float)beta1, (float)beta2,
+            (float)sqrt(bc2), (float)eps, reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f, bufs[cur][0], bufs[cur][1], bufs[cur][2]);
+        TMA_LAUNCH_CHECK();
+        cur = 0;  // (the optimizer launch left the state in the caller's buffers)
+    }
+    return TMA_OK;
+}
+
+int tma_debug_last_prep_fold(int *folded_out, int *standalone_out) {
+    if (folded_out) *folded_out = g_prep_folded;
+    if (standalone_out) *standalone_out = g_prep_standalone;
+    return TMA_OK;
+}
+
+static int train_epoch_local_impl(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch, int64_t batch_size,
+                                  const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                  double beta2, double eps, double max_grad_norm, void *workspace, void *stream);
+
 int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch0, int n_epochs,
                                int64_t batch_size, const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr,
                                double beta1, double beta2, double eps, double max_grad_norm, void *workspace, void *stream) {
@@ -2901,6 +2988,7 @@ int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tm
         return fail(TMA_ERR_INVALID, "tma_ppo_train_epochs_local: T, N, batch_size, first_step and n_epochs must be >= 1");
     const int64_t total = (int64_t)rb->T * rb->N, n_mb = ceil_div(total, batch_size);
     const PLayout L = layout_of(d);
+    g_prep_folded = g_prep_standalone = 0;
     int e = 0;
     // as many epochs per persistent launch as the offsets cache holds (all of them for the reference's own 1- and 8-env schedules: 4 or 32
     // optimizer steps an epoch, where a launch per epoch was mostly launch)
@@ -2914,8 +3002,13 @@ int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tm
         if (!ran) break;
         e += n;
     }
+    // H = 64 fast path at minibatches the eight-wave gradient kernel takes (never a persistent-kernel shape: those are batch_size 256): the
+    // remaining epochs as ONE chain of gradient launches, each carrying the next minibatch's pre-pass -- across the epoch boundaries too
+    if (e < n_epochs && h64_fold_eligible(L, total, batch_size) && tma_grad_h64_carries_prep(batch_size))
+        return h64_fold_epochs(params, d, rb, L, perm_seed, perm_epoch0 + (uint32_t)e, n_epochs - e, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step + e * n_mb, lr,
+                               beta1, beta2, eps, max_grad_norm, workspace, stream);
     for (; e < n_epochs; e++) {  // not eligible (or handed back): epoch by epoch (which tries the single-epoch persistent launch first, then the launches)
-        rc = tma_ppo_train_epoch_local(params, d, rb, perm_seed, perm_epoch0 + (uint32_t)e, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step + e * n_mb, lr,
+        rc = train_epoch_local_impl(params, d, rb, perm_seed, perm_epoch0 + (uint32_t)e, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step + e * n_mb, lr,
                                        beta1, beta2, eps, max_grad_norm, workspace, stream);
         if (rc) return rc;
     }
@@ -2925,6 +3018,14 @@ int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tm
 int tma_ppo_train_epoch_local(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch, int64_t batch_size,
                               const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr, double beta1,
                               double beta2, double eps, double max_grad_norm, void *workspace, void *stream) {
+    g_prep_folded = g_prep_standalone = 0;
+    return train_epoch_local_impl(params, d, rb, perm_seed, perm_epoch, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step, lr, beta1, beta2, eps, max_grad_norm,
+                                  workspace, stream);
+}
+
+static int train_epoch_local_impl(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch, int64_t batch_size,
+                                  const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                  double beta2, double eps, double max_grad_norm, void *workspace, void *stream) {
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !rb || !hp || !grad || !exp_avg || !exp_avg_sq || !workspace) return fail(TMA_ERR_INVALID, "tma_ppo_train_epoch_local: null argument");
@@ -2940,47 +3041,15 @@ int tma_ppo_train_epoch_local(float *params, const tma_policy_dims *d, const tma
                                workspace, stream, &ran);
         if (rc) return rc;
         if (ran) return TMA_OK;
+        if (h64_fold_eligible(L, total, batch_size))  // H = 64 fast path: optimizer steps (and, from 2 049 rows a minibatch, pre-passes) inside the gradient launches
+            return h64_fold_epochs(params, d, rb, L, perm_seed, perm_epoch, 1, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step, lr, beta1, beta2, eps,
+                                   max_grad_norm, workspace, stream);
         const tma_minibatch ep{nullptr, perm_seed, perm_epoch, 0, total, 0, 0};
         rc = tma_ppo_epoch_prepare(rb, &ep, batch_size, d, workspace, stream);
         if (rc) return rc;
+        g_prep_standalone++;
     }
     int64_t step = first_step;
-    const bool no_fold = getenv("TMA_NO_ADAM_FOLD") != nullptr;  // test / measurement switch: one optimizer launch per minibatch (read per epoch)
-    const int64_t tail = total % batch_size;
-    if (L.img_pi >= 0 && prepared && (tail == 0 || tail >= 256) && total > batch_size && !no_fold) {
-        // H = 64 fast path, every minibatch on the LDS-image kernel: the optimizer step of minibatch k runs in the prologue of gradient
-        // launch k + 1 (AdamFold: every workgroup redoes it for its net and builds its weight image from the results), so a minibatch
-        // costs two launches (gradient, slab reduction) instead of three; the state ping-pongs between (params, exp_avg, exp_avg_sq) and
-        // the workspace copy, and the epoch's last step is the ordinary optimizer launch, which leaves everything (derived copies and
-        // images included) in the caller's buffers.  Same arithmetic on the same inputs as the unfolded sequence: bit-identical.
-        char *ws = static_cast<char *>(workspace);
-        hipStream_t s = (hipStream_t)stream;
-        const int64_t Pp = ((int64_t)L.P + 3) & ~(int64_t)3;
-        float *alt = reinterpret_cast<float *>(ws + fold_state_offset(L));
-        float *bufs[2][3] = {{params, exp_avg, exp_avg_sq}, {alt, alt + Pp, alt + 2 * Pp}};
-        int cur = 0;
-        const double *sqp = sq_partials(ws, L);
-        for (int64_t start = 0; start < total; start += batch_size, step++) {
-            const int64_t count = start + batch_size <= total ? batch_size : total - start;
-            const tma_minibatch mb{nullptr, perm_seed, perm_epoch, start, count, batch_size, 0};
-            AdamFold f{};
-            if (start > 0) {  // the step of the previous minibatch (index step - 1)
-                const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
-                f = AdamFold{grad, sqp, (int)ceil_div(L.P, 64), bufs[cur][0], bufs[cur][1], bufs[cur][2], bufs[cur ^ 1][0], bufs[cur ^ 1][1],
-                             bufs[cur ^ 1][2], (float)max_grad_norm, (float)(lr / bc1), (float)beta1, (float)beta2, (float)sqrt(bc2), (float)eps,
-                             reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f};
-            }
-            rc = minibatch_grad_impl(params, d, rb, &mb, hp, grad, workspace, stream, start > 0 ? &f : nullptr, start > 0 ? 1 : 0);
-            if (rc) return rc;
-            if (start > 0) cur ^= 1;
-        }
-        const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
-        adam_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
-            params, grad, exp_avg, exp_avg_sq, L, sqp, (int)ceil_div(L.P, 64), (float)max_grad_norm, (float)(lr / bc1), (float)beta1, (float)beta2,
-            (float)sqrt(bc2), (float)eps, reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f, bufs[cur][0], bufs[cur][1], bufs[cur][2]);
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
-    }
     for (int64_t start = 0; start < total; start += batch_size, step++) {
         const int64_t count = start + batch_size <= total ? batch_size : total - start;
         const tma_minibatch mb{nullptr, perm_seed, perm_epoch, start, count, prepared ? batch_size : 0, 0};

@@ -53,6 +53,77 @@ __device__ __forceinline__ int64_t sample_offset(const Minibatch &mb, int64_t j,
     return t * N + i;
 }
 
+// ---- advantage pre-pass: sample offsets + (sum, sum of squares) partials of one minibatch ----
+constexpr int ADV_BLOCKS = 128;  // partial blocks per minibatch at the most (1 024 rows each up to 131 072 rows, longer slices beyond)
+// Partial block `pb` of the `nb` a minibatch is split into: rows [pb * per, (pb + 1) * per) of it, thread tid < 256 takes rows j0 + tid,
+// + 256, ... in that order into ONE f64 (sum, sum of squares) pair; one shuffle tree per wave, the four waves' pairs as (0 + 1) + (2 + 3).
+// The ONE body of adv_partial_kernel (tma_policy.hip) and of the tail phase of the H = 64 gradient kernel's value blocks (tma_h64.hip),
+// so the two cannot drift apart.  Four rows of a thread go through together -- four permutation evaluations, then four gathers in one
+// memory round trip -- and are added in row order.  Every thread of the workgroup calls it (it holds a barrier); s1 / s2: 4 doubles of
+// LDS each.  want_sums == false: offsets only (nothing reads the partials when advantages are not normalised), no barrier.
+__device__ __forceinline__ void adv_partial_block(const float *__restrict__ adv, const Minibatch &mb, int T, int64_t N, int nb, int pb, int tid,
+                                                  double *__restrict__ partials, int32_t *__restrict__ offs_out, bool want_sums, double *s1,
+                                                  double *s2) {
+    const int64_t per = (mb.count + nb - 1) / nb;
+    const int64_t j0 = (int64_t)pb * per, j1 = (j0 + per < mb.count) ? j0 + per : mb.count;
+    if (tid < 256) {
+        double a = 0.0, b = 0.0;
+        for (int64_t j = j0 + tid; j < j1; j += 4 * 256) {
+            int64_t off[4];
+            float x[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int64_t jq = j + 256 * q;
+                off[q] = 0;
+                if (jq < j1) {
+                    off[q] = sample_offset(mb, mb.start + jq, T, N);
+                    if (offs_out) offs_out[jq] = (int32_t)off[q];
+                }
+            }
+            if (want_sums) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) x[q] = adv[off[q]];  // (rows past the slice read element 0 and are not added)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    if (j + 256 * q < j1) {
+                        const double xd = (double)x[q];
+                        a += xd;
+                        b += xd * xd;
+                    }
+                }
+            }
+        }
+        if (want_sums) {
+            for (int o = 32; o > 0; o >>= 1) {
+                a += __shfl_down(a, o, 64);
+                b += __shfl_down(b, o, 64);
+            }
+            if ((tid & 63) == 0) s1[tid >> 6] = a, s2[tid >> 6] = b;
+        }
+    }
+    if (!want_sums) return;
+    __syncthreads();
+    if (tid == 0) {
+        partials[2 * pb] = (s1[0] + s1[1]) + (s1[2] + s1[3]);
+        partials[2 * pb + 1] = (s2[0] + s2[1]) + (s2[2] + s2[3]);
+    }
+}
+
+// The pre-pass of the NEXT minibatch, carried by an eight-wave H = 64 gradient launch (tma_ppo_train_epochs_local): value block b runs
+// partial blocks b, b + n_pairs, ... of it after its own slab stores and statistics -- the value net's blocks finish ahead of the policy
+// net's, so the launch does not grow -- and the next launch finds its offsets and partials where tma_ppo_epoch_prepare would have left
+// them.  The kernel boundary is the hand-over; the regions written are never the ones the carrying launch reads.
+struct PrepNext {
+    const float *adv;             // the advantages plane [T][N]
+    int32_t *offs_out;            // offs_out[j] = buffer offset of row j of that minibatch
+    double *partials_out;         // its (sum, sum of squares) partials: min(ceil(count / 1024), ADV_BLOCKS) pairs; untouched without want_sums
+    uint32_t perm_seed, perm_epoch;
+    int64_t start, count, total;  // rows [start, start + count) of the (perm_seed, perm_epoch) permutation; count == 0: nothing to do
+    int64_t N;
+    int T;
+    int want_sums;                // normalize_advantage; 0: offsets only
+};
+
 struct Rollout {
     const float *obs;
     const void *actions;
@@ -189,7 +260,9 @@ __device__ __forceinline__ void policy_loss_tile(const f32x4 (&acc)[CONT ? 2 : 1
 // tma_h64.hip: the H = 64 persistent gradient kernel (internal, not part of the C ABI)
 int tma_launch_grad_h64(const float *params, const tma::PLayout &L, const tma::Rollout &R, const tma::Minibatch &M, const tma::HParams &hpar,
                         const double *adv_part, int n_part, float *slabs, double *slots, int *n_slabs_out, hipStream_t s,
-                        const tma::AdamFold *fold = nullptr);
+                        const tma::AdamFold *fold = nullptr, const tma::PrepNext *next = nullptr);
+// true: a minibatch of `count` rows runs on the eight-wave kernel, whose value blocks can carry a PrepNext (and whose launch may be handed one)
+bool tma_grad_h64_carries_prep(int64_t count);
 
 // tma_h64p.hip: one whole epoch at batch_size = 256 as a single persistent launch (H = 64 fast-path layouts)
 bool tma_epoch_h64p_eligible(const tma::PLayout &L, int64_t batch_size, int64_t total);

@@ -40,3 +40,33 @@ for net, o in (("pi", 0), ("vf", 16)):
     print("    of the epilogue,", round(out[o + 14] / reps), "cycles are the wait for the block's slowest wave")
     print("    per launch: loop", round(loop_c), "cycles =", round(loop_rt / 100, 1), "us (100 MHz counter) -> clock", round(loop_c / max(loop_rt, 1) * 0.1, 2),
           "GHz; prologue", round(pro), "cycles, epilogue", round(epi), "cycles")
+
+# ---- the value blocks' tail phase (the next minibatch's advantage pre-pass, carried by the launch): two epochs of two minibatches of B rows
+# through tma_ppo_train_epochs_local -- four gradient launches a call, three of them carrying a pre-pass
+if hasattr(L, "tma_debug_h64_tail_ticks"):
+    env.close()
+    env = make_vector_env("gridworld", n_envs=4096, seed=1)
+    m = PPO("MlpPolicy", env, n_steps=max(1, 2 * B // 4096), batch_size=B, n_epochs=2, seed=1, policy_kwargs={"net_arch": [64, 64]})
+    m.collect_rollouts()
+    L.tma_debug_h64_tail_ticks.argtypes = [C.c_void_p, C.c_int]
+    tail = C.c_ulonglong(0)
+    for switch in (None, "1"):
+        os.environ.pop("TMA_NO_PREP_FOLD", None)
+        if switch:
+            os.environ["TMA_NO_PREP_FOLD"] = switch
+        m.train()
+        L.tma_debug_h64_ticks(None, 1)
+        L.tma_debug_h64_tail_ticks(None, 1)
+        for _ in range(reps):
+            m.train()
+        L.tma_debug_h64_ticks(out, 0)
+        L.tma_debug_h64_tail_ticks(C.byref(tail), 0)
+        n, carrying = reps * 4, reps * 3
+        print("train(), pre-passes", "in launches of their own (TMA_NO_PREP_FOLD=1)" if switch else "carried by the gradient launches", "-- cycles per launch:")
+        for net, o in (("pi", 0), ("vf", 16)):
+            pro, loop_c, epi = (out[o + i] / n for i in (12, 10, 13))
+            print("   ", net, "prologue", round(pro), "loop", round(loop_c), "epilogue", round(epi), "sum", round(pro + loop_c + epi))
+        if not switch:
+            print("    vf: end of the loop -> end of the tail phase", round(tail.value / carrying), "cycles per carrying launch: the phase itself",
+                  round(tail.value / carrying - out[16 + 13] / n))
+    os.environ.pop("TMA_NO_PREP_FOLD", None)

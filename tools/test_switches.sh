@@ -32,3 +32,5 @@ run "TMA_ROLL2=1" "tests/test_ppo_gpu.py tests/test_rollout_oracle_gpu.py" "roll
 run "TMA_H64_RUNTIME_A=1" "tests/test_ppo_gpu.py tests/test_policy_dispatch_gpu.py tests/test_rollout_oracle_gpu.py"   # the H = 64 gradient kernel with the head width read at run time at every shape (the headline shape has a compile-time instantiation)
 # round 8
 run "TMA_ROLL4=1" "tests/test_ppo_gpu.py tests/test_rollout_oracle_gpu.py tests/test_env_gpu.py tests/test_bench_gpu.py"   # the headline rollout on four waves per tile (round 6) instead of eight
+# round 9
+run "TMA_NO_PREP_FOLD=1" "tests/test_ppo_gpu.py tests/test_h64_head_width_gpu.py tests/test_policy_dispatch_gpu.py tests/test_bench_gpu.py"   # H = 64 fast path: one prepare launch per epoch (tests/test_prep_fold_gpu.py sets the switch itself)
