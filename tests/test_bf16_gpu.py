@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import sb3_ref
-from test_ppo_gpu import HP, _flatten_env_major, _hip_grad, _ref_grad_flat, _rollout
+from test_ppo_gpu import HP, _flatten_env_major, _hip_grad, _nontrivial_heads, _ref_grad_flat, _rollout
 
 pytestmark = pytest.mark.gpu
 
@@ -26,15 +26,7 @@ def _policies(D, H, A, cont, seed=5):
     from three_mlagents_amd.ppo import HipActorCriticPolicy
 
     pol = HipActorCriticPolicy(D, A, cont, H, torch.device("cuda", 0), seed=seed, mfma_dtype="bf16")
-    sd = pol.state_dict()
-    g = torch.Generator().manual_seed(seed)
-    if cont:
-        sd["log_std"] = torch.linspace(-0.7, 0.3, A)
-    sd["action_net.weight"] = sd["action_net.weight"] * 40 + 0.05 * torch.randn(sd["action_net.weight"].shape, generator=g)
-    sd["action_net.bias"] = 0.1 * torch.randn(sd["action_net.bias"].shape, generator=g)
-    for k in list(sd):
-        if k.endswith("bias") and k != "action_net.bias":
-            sd[k] = 0.05 * torch.randn(sd[k].shape, generator=g)
+    sd = _nontrivial_heads(pol.state_dict(), A, cont, seed)
     pol.load_state_dict(sd)
     return pol, sd
 

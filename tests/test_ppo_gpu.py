@@ -14,20 +14,24 @@ pytestmark = pytest.mark.gpu
 CONFIGS = [(4, 64, 5, False), (6, 256, 5, False), (21, 64, 3, False), (172, 256, 20, True), (4, 128, 5, False)]
 
 
-def _policy(D, H, A, cont, seed=5):
-    from three_mlagents_amd.ppo import HipActorCriticPolicy
-
-    pol = HipActorCriticPolicy(D, A, cont, H, torch.device("cuda", 0), seed=seed)
-    sd = pol.state_dict()
+def _nontrivial_heads(sd, A, cont, seed):
+    """the test policies' state dict from the initial one: make the heads non-trivial (gain 0.01 init gives almost uniform logits)"""
     if cont:
         sd["log_std"] = torch.linspace(-0.7, 0.3, A)
-    # make the heads non-trivial (gain 0.01 init gives almost uniform logits)
     g = torch.Generator().manual_seed(seed)
     sd["action_net.weight"] = sd["action_net.weight"] * 40 + 0.05 * torch.randn(sd["action_net.weight"].shape, generator=g)
     sd["action_net.bias"] = 0.1 * torch.randn(sd["action_net.bias"].shape, generator=g)
     for k in list(sd):
         if k.endswith("bias") and k != "action_net.bias":
             sd[k] = 0.05 * torch.randn(sd[k].shape, generator=g)
+    return sd
+
+
+def _policy(D, H, A, cont, seed=5):
+    from three_mlagents_amd.ppo import HipActorCriticPolicy
+
+    pol = HipActorCriticPolicy(D, A, cont, H, torch.device("cuda", 0), seed=seed)
+    sd = _nontrivial_heads(pol.state_dict(), A, cont, seed)
     pol.load_state_dict(sd)
     return pol, sd
 

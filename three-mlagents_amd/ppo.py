@@ -60,6 +60,28 @@ def _dist_backend() -> str | None:
     return td.get_backend() if td.is_available() and td.is_initialized() else None
 
 
+def orthogonal_init(obs_dim: int, hidden: int, act_dim: int, continuous: bool, seed: int) -> dict[str, torch.Tensor]:
+    """SB3's initial parameters of ActorCriticPolicy(MlpPolicy) in its state_dict naming, on the CPU: what HipActorCriticPolicy(seed=...) loads."""
+    gen = torch.Generator().manual_seed(int(seed))
+    D, H, A = int(obs_dim), int(hidden), int(act_dim)
+
+    def ortho(o, i, gain):
+        w = torch.empty(o, i)
+        torch.nn.init.orthogonal_(w, gain=gain, generator=gen)
+        return w
+
+    g2 = math.sqrt(2.0)
+    sd = {
+        SB3_KEYS[0]: ortho(H, D, g2), SB3_KEYS[1]: torch.zeros(H), SB3_KEYS[2]: ortho(H, H, g2), SB3_KEYS[3]: torch.zeros(H),
+        SB3_KEYS[4]: ortho(A, H, 0.01), SB3_KEYS[5]: torch.zeros(A),
+        SB3_KEYS[6]: ortho(H, D, g2), SB3_KEYS[7]: torch.zeros(H), SB3_KEYS[8]: ortho(H, H, g2), SB3_KEYS[9]: torch.zeros(H),
+        SB3_KEYS[10]: ortho(1, H, 1.0), SB3_KEYS[11]: torch.zeros(1),
+    }
+    if continuous:
+        sd["log_std"] = torch.zeros(A)
+    return sd
+
+
 class HipActorCriticPolicy:
     """Parameters of SB3's ActorCriticPolicy(MlpPolicy) in one flat HBM buffer + the forward kernels."""
 
@@ -83,24 +105,7 @@ class HipActorCriticPolicy:
 
     # -- init / (de)serialisation in SB3's state_dict naming -------------------------------
     def _orthogonal_init(self, seed: int) -> dict[str, torch.Tensor]:
-        gen = torch.Generator().manual_seed(int(seed))
-        D, H, A = self.obs_dim, self.hidden, self.act_dim
-
-        def ortho(o, i, gain):
-            w = torch.empty(o, i)
-            torch.nn.init.orthogonal_(w, gain=gain, generator=gen)
-            return w
-
-        g2 = math.sqrt(2.0)
-        sd = {
-            SB3_KEYS[0]: ortho(H, D, g2), SB3_KEYS[1]: torch.zeros(H), SB3_KEYS[2]: ortho(H, H, g2), SB3_KEYS[3]: torch.zeros(H),
-            SB3_KEYS[4]: ortho(A, H, 0.01), SB3_KEYS[5]: torch.zeros(A),
-            SB3_KEYS[6]: ortho(H, D, g2), SB3_KEYS[7]: torch.zeros(H), SB3_KEYS[8]: ortho(H, H, g2), SB3_KEYS[9]: torch.zeros(H),
-            SB3_KEYS[10]: ortho(1, H, 1.0), SB3_KEYS[11]: torch.zeros(1),
-        }
-        if self.continuous:
-            sd["log_std"] = torch.zeros(A)
-        return sd
+        return orthogonal_init(self.obs_dim, self.hidden, self.act_dim, self.continuous, seed)
 
     def _segments(self):
         D, H, A = self.obs_dim, self.hidden, self.act_dim
