@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 212
+#define TMA_VERSION 213
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -421,6 +421,19 @@ enum {
     TMA_DISPATCH_GRID_CAPPED = 256
 };
 int tma_debug_last_dispatch(int32_t *fwd_out, int32_t *grad_out, int32_t *opt_out);
+/* Test aid (ABI 213): what those dispatchers WOULD choose, asked on the host alone -- no HIP call, so it answers on a machine without a GPU.  `which`
+ * selects the dispatcher and says what `n` is: TMA_PLAN_FWD -- tma_policy_act on n rows; TMA_PLAN_GRAD -- tma_ppo_minibatch_grad on a minibatch
+ * of n samples; TMA_PLAN_OPT -- tma_ppo_adam_step (n unused); TMA_PLAN_OPT_LOCAL -- tma_ppo_adam_step_local with last_count = n.  It validates
+ * `d` as the real call does, runs the same pure plan function (csrc/tma_policy_plan.h) with the environment switches the real call would read,
+ * and returns the real call's status and message where that would refuse the shape.  *id_out: the id tma_debug_last_dispatch reports after
+ * the real call.  grid / block / LDS bytes: the forward kernel's; the gradient's dominant kernel (the first of the two launches of the
+ * two-pass kernels) -- but *lds_bytes_out = -1 where the family's own launcher picks that geometry (H = 64, bf16, three-term split): grid and
+ * block are then the slab reduction's that follows; the optimizer kernel's that steps the parameters (LDS 0).  Any output pointer may be NULL. */
+#define TMA_PLAN_FWD 0
+#define TMA_PLAN_GRAD 1
+#define TMA_PLAN_OPT 2
+#define TMA_PLAN_OPT_LOCAL 3
+int tma_debug_plan_dispatch(const tma_policy_dims *d, int which, int64_t n, int32_t *id_out, int64_t *grid_out, int32_t *block_out, int32_t *lds_bytes_out);
 /* out8: sums since the last call of {policy_loss, value_sq_err, entropy, approx_kl, clipped, n_samples}, then the last
  * total grad norm and clip coefficient.  Synchronises `stream`. */
 int tma_ppo_pop_stats(void *workspace, double *out8_host, void *stream);

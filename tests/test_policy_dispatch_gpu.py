@@ -1,14 +1,17 @@
 """Every specialisation the policy's three dispatchers can pick -- the forward (launch_fwd), the minibatch gradient (minibatch_grad_impl) and
-the optimizer step (tma_ppo_adam_step / _local) -- against an independent float64 reference (oracle/sb3_ref.py run on .double() copies of
+the optimizer step (tma_ppo_adam_step / _local), each of which launches what its pure plan function (plan_fwd / plan_grad / plan_opt,
+csrc/tma_policy_plan.h) decides -- against an independent float64 reference (oracle/sb3_ref.py run on .double() copies of
 the exact f32 parameters and inputs), at the shapes where tile code breaks.  Each case names the branch it is meant to reach and asserts
-it through tma_debug_last_dispatch, so a threshold change cannot quietly move a case onto another kernel.
+it through tma_debug_last_dispatch, so a threshold change cannot quietly move a case onto another kernel; the host-only query
+tma_debug_plan_dispatch must name the same branch for the same arguments.
 
 Gradient comparison, per parameter segment s:  err_kernel,s <= K * err_torch32,s + F * max|g64,s|, where err_torch32 is the error of
 float32 torch CPU autograd on the same data (the calibration: what an honest f32 implementation of the same sums is off by).  Every
 gradient case also checks that the comparator REJECTS the float64 gradient of the same minibatch without its last row tile -- the
 tolerance is tight enough to see a dropped partial tile at that size.
 
-CASES is importable without a GPU: tests/test_policy_dispatch_table_cpu.py checks that every branch id of include/tma.h has a case."""
+CASES is importable without a GPU: tests/test_policy_dispatch_table_cpu.py checks that every branch id of include/tma.h has a case, and
+that the query alone gives every case its id."""
 import ctypes as C
 import math
 import os
@@ -168,6 +171,22 @@ def _last_dispatch():
     return f.value, g.value, o.value
 
 
+PLAN_WHICH = {"fwd": 0, "grad": 1, "opt": 2, "opt_local": 3}  # TMA_PLAN_* of include/tma.h
+
+
+def planned(dims, which, n):
+    """(status, id, grid, block, lds_bytes) of tma_debug_plan_dispatch: what the dispatcher `which` would choose for n rows.  No GPU work."""
+    from three_mlagents_amd import _lib
+
+    i, g, b, l = C.c_int32(-1), C.c_int64(-1), C.c_int32(-1), C.c_int32(-1)
+    rc = _lib.lib().tma_debug_plan_dispatch(C.byref(dims), PLAN_WHICH[which], n, C.byref(i), C.byref(g), C.byref(b), C.byref(l))
+    return rc, i.value, g.value, b.value, l.value
+
+
+def _entry_which(entry):
+    return "opt_local" if entry.startswith("opt_local") else entry.split("_")[0]
+
+
 def _name(v):
     names = [k for k, x in dispatch_ids().items() if x == v & 0xFF and k != "GRID_CAPPED"]
     return "|".join(names + (["GRID_CAPPED"] if v & 256 else []))
@@ -279,6 +298,7 @@ def test_gradient_branch_against_float64(entry, D, H, A, cont, B, ident, monkeyp
         grad, st, _ = _hip_grad(pol, bufs, T, N, perm, start, B, hp)
     got = _last_dispatch()[1]
     assert got == expected_value(ident), (ident, _name(got))
+    assert planned(pol.dims, "grad", B)[:2] == (0, got)
     idx = perm[start:start + B]
     g = pol.named_from_flat(grad)
     if dtype != "f32":  # (numerics: test_bf16_gpu.py / test_split3_gpu.py)
@@ -354,6 +374,7 @@ def test_forward_branch_against_float64(entry, D, H, A, cont, n, ident, record_p
     def check_id():
         got = _last_dispatch()[0]
         assert got == expected_value(ident), (ident, _name(got))
+        assert planned(pol.dims, "fwd", n)[:2] == (0, got)
 
     a, v, lp = pol.act(obs.cuda(), deterministic=True)
     check_id()
@@ -419,6 +440,7 @@ def test_optimizer_branch_against_float64_adam(entry, D, H, A, cont, B, ident, r
             got = _last_dispatch()[2]
             _lib.check(rc)
             assert got == expected_value(ident), (ident, _name(got))
+            assert planned(pol.dims, _entry_which(entry), B)[:2] == (0, got)
             out = (C.c_double * 8)()
             _lib.check(_lib.lib().tma_ppo_pop_stats(_lib.ptr(ws), out, _lib.stream_ptr()))
             assert float(grad.abs().max()) == 0.0  # re-zeroed for the next minibatch

@@ -1,6 +1,7 @@
 """The dispatch-record table of tests/test_policy_dispatch_gpu.py stays complete: every branch id include/tma.h declares has at least one
 case that is meant to reach it (so a new specialisation cannot ship without a float64 reference test), and every case names ids that
-exist.  Importing the table touches no GPU."""
+exist; and the host-only query tma_debug_plan_dispatch -- the pure plan functions of csrc/tma_policy_plan.h behind every launch -- gives every
+case the id the table expects and refuses what the real calls refuse.  None of this touches a GPU."""
 import os
 import re
 import sys
@@ -51,3 +52,62 @@ def test_every_dispatch_id_has_a_reference_case():
     # every case a distinct test id
     case_ids = [t._case_id(c) for c in t.CASES]
     assert len(case_ids) == len(set(case_ids))
+
+
+def _case_dims(entry, D, H, A, cont):
+    from three_mlagents_amd import _lib
+
+    mfma = 2 if entry.endswith("bf16x3") else (1 if entry.endswith("bf16") else 0)
+    return _lib.PolicyDims(D, H, A, int(cont), mfma, -1)
+
+
+def check_planned_cases(want_nodefer):
+    """tma_debug_plan_dispatch gives every CASES row its id (the table was verified on hardware through tma_debug_last_dispatch), a grid of at
+    least one block and at most 160 KB of LDS.  The grad_nodefer rows alone when want_nodefer: TMA_NO_DEFER_W2 is read once per process."""
+    import torch
+
+    import test_policy_dispatch_gpu as t
+
+    n = 0
+    for entry, D, H, A, cont, B, ident in t.CASES:
+        if (entry == "grad_nodefer") != want_nodefer:
+            continue
+        if entry == "grad_nodz1":
+            os.environ["TMA_NO_DZ1_CACHE"] = "1"
+        try:
+            rc, got, grid, block, lds = t.planned(_case_dims(entry, D, H, A, cont), t._entry_which(entry), B)
+        finally:
+            os.environ.pop("TMA_NO_DZ1_CACHE", None)
+        case = t._case_id((entry, D, H, A, cont, B, ident))
+        assert rc == 0 and got == t.expected_value(ident), (case, rc, t._name(got))
+        inner = ident in ("GRAD_H64_SMALL", "GRAD_H64", "GRAD_BF16", "GRAD_BF16X3")  # geometry picked by the family's own launcher: LDS -1
+        assert grid >= 1 and block >= 64 and block % 64 == 0 and (lds == -1 if inner else 0 <= lds <= 160 * 1024), (case, grid, block, lds)
+        n += 1
+    assert n == (3 if want_nodefer else len(t.CASES) - 3)
+    assert not torch.cuda.is_initialized()
+
+
+def test_plan_query_gives_every_case_its_id():
+    check_planned_cases(False)
+
+
+def test_plan_query_gives_the_no_defer_cases_their_ids_in_a_child_process():
+    import subprocess
+
+    code = f"import sys; sys.path[:0] = [{ROOT!r}, {HERE!r}]; import test_policy_dispatch_table_cpu as m; m.check_planned_cases(True)"
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TMA_NO_DEFER_W2="1"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+def test_plan_query_refuses_what_the_real_calls_refuse():
+    """the shapes test_accepted_but_unrunnable_shapes_are_refused_by_every_entry_point sends to the real calls, and mfma_dtype = 2 with a Box head"""
+    import test_policy_dispatch_gpu as t
+    from three_mlagents_amd import _lib
+
+    for D, H, A, cont in [(2500, 64, 3, False), (600, 1024, 2, True), (2100, 256, 4, False)]:
+        for which in ("fwd", "grad"):
+            rc = t.planned(_case_dims(which, D, H, A, cont), which, 40)[0]
+            assert rc == _lib.TMA_ERR_INVALID and "LDS" in _lib.last_error(), (D, H, which, rc, _lib.last_error())
+    rc = t.planned(_case_dims("grad_bf16x3", 6, 256, 3, True), "grad", 4096)[0]
+    assert rc == _lib.TMA_ERR_INVALID and "mfma_dtype 2" in _lib.last_error(), (rc, _lib.last_error())
+    assert t.planned(_case_dims("fwd", 6, 256, 3, True), "fwd", 0)[0] == _lib.TMA_ERR_INVALID  # (the real calls refuse n < 1)

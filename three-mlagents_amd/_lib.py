@@ -93,6 +93,7 @@ SIGNATURES = {
     "tma_debug_poison_lds": (_i32, [_u32, _vp]),
     "tma_debug_last_grad_kernel_us": (_i32, [C.POINTER(C.c_float)]),
     "tma_debug_last_dispatch": (_i32, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "tma_debug_plan_dispatch": (_i32, [_pd, _i32, _i64, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
     "tma_debug_last_rollout_waves": (_i32, []),
     "tma_debug_last_prep_fold": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
     "tma_ppo_epoch_prepare": (_i32, [C.POINTER(Rollout), C.POINTER(Minibatch), _i64, _pd, _vp, _vp]),

@@ -1356,6 +1356,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ppo_grad_wide_kernel(const fl
 }
 
 #include "tma_wide_bf16.h"
+#include "tma_policy_plan.h"
 
 // zero the layer-1 weight columns of every slab when they are accumulated in place (observations wider than 32)
 __global__ void slab_zero_w1_kernel(float *slabs, int n_slabs, PLayout L) {
@@ -1366,11 +1367,6 @@ __global__ void slab_zero_w1_kernel(float *slabs, int n_slabs, PLayout L) {
         const int x = (int)(e - b * 2 * per);
         slabs[b * L.P + (x < per ? L.pW1t + x : L.vW1t + (x - per))] = 0.0f;
     }
-}
-
-static int grad_wide_smem_bytes(const PLayout &L, int nw = 4) {
-    const int ldx = ((L.D + 3) & ~3) + 2, ld = L.H + 2;
-    return (32 * (ldx + 2 * ld + 34 + 4) + 2 * 32 + 64 + nw * 2 * 2 * 256 + 2 * L.H + 32 + 2 * 32 + 32 * 32) * 4;  // (last terms: row_off_next, the Box heads' action tile)
 }
 
 // grad[e] += sum over blocks of slab[b][e].  64 params x 4 slab quarters per block, partial sums folded through LDS in a
@@ -1907,15 +1903,6 @@ static int enter(const tma_policy_dims *d) {
 // what the calling thread's last call of each dispatcher chose (tma_debug_last_dispatch): set where the dispatcher decides, before it launches
 static thread_local int32_t g_disp_fwd = TMA_DISPATCH_NONE, g_disp_grad = TMA_DISPATCH_NONE, g_disp_opt = TMA_DISPATCH_NONE;
 
-static int fwd_smem_bytes(const PLayout &L, int wpb) {
-    const int ldx = ((L.D + 3) & ~3) + 2, ld = L.H + 2;
-    return wpb * (16 * (ldx + 2 * ld) + 32) * 4;
-}
-static int grad_smem_bytes(const PLayout &L, int wpb) {
-    const int ldx = ((L.D + 3) & ~3) + 2, ld = L.H + 2;
-    return wpb * (16 * (ldx + 2 * ld + 34) + 16 * 8) * 4;
-}
-
 
 // ------------------------------------------------------------------------------------------
 // H = 64 forward fast path: both nets' forward weight images staged in LDS once per block (float4 copies of the images
@@ -2003,18 +1990,13 @@ __global__ __launch_bounds__(256) void policy_fwd_h64_kernel(const float *__rest
 }
 
 template <int MODE>
-static int launch_fwd_h64(const float *params, const PLayout &L, const float *obs, int64_t n, uint32_t seed, uint32_t step, uint32_t env_offset,
+static int launch_fwd_h64(const FwdPlan &p, const float *params, const PLayout &L, const float *obs, int64_t n, uint32_t seed, uint32_t step, uint32_t env_offset,
                           int deterministic, void *actions, float *values, float *logp, const float *boot_obs, const uint8_t *boot_trunc, float gamma,
                           float *boot_rewards, hipStream_t s) {
-    const int64_t tiles = ceil_div(n, 16);
-    const int wpb = tiles >= 512 ? 4 : (tiles >= 64 ? 2 : 1);
-    const int smem = ((MODE == 0 || MODE == 3) ? 2 : 1) * FWD_IMG * 4;
-    int64_t blocks = ceil_div(tiles, wpb);
-    if (blocks > 2048) blocks = 2048;
     auto k = policy_fwd_h64_kernel<MODE>;
-    if (smem > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    k<<<dim3((unsigned)blocks), dim3(64 * wpb), smem, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, static_cast<int32_t *>(actions), values,
-                                                           logp, boot_obs, boot_trunc, gamma, boot_rewards);
+    if (p.lds > LDS_OPT_IN) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+    k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, static_cast<int32_t *>(actions), values, logp,
+                                                           boot_obs, boot_trunc, gamma, boot_rewards);
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
@@ -2354,9 +2336,17 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
     }
 }
 
-static int fwd_wide_smem_bytes(const PLayout &L) {
-    const int ldx = ((L.D + 3) & ~3) + 2, ld = L.H + 2;
-    return 32 * (ldx + 2 * ld) * 4;
+// The one place a runtime (Box head, H / 64) pair becomes the CONT / NTW template arguments of the column-parallel kernels: f(CONT, NTW) as constants
+template <class F>
+static int with_cont_ntw(bool cont, int ntw, F &&f) {
+    auto widths = [&](auto c) -> int {
+        return ntw == 4 ? f(c, std::integral_constant<int, 4>{}) : (ntw == 3 ? f(c, std::integral_constant<int, 3>{}) : f(c, std::integral_constant<int, 2>{}));
+    };
+    return cont ? widths(std::true_type{}) : widths(std::false_type{});
+}
+
+static int refuse(const PLayout &L, const FwdPlan &p) {
+    return fail(TMA_ERR_INVALID, "policy too wide for the forward kernel's LDS-resident tile (obs_dim %d, hidden %d: needs %d bytes)", L.D, L.H, p.lds);
 }
 
 // MODE 3 (tma_policy_evaluate_actions): `actions` is the input, `rewards` carries entropy_out; eligibility, grid caps and dispatch ids are MODE 0's
@@ -2365,72 +2355,97 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
                       int deterministic, void *actions, float *values, float *logp, const uint8_t *trunc, float gamma, float *rewards,
                       hipStream_t s) {
     const PLayout L = layout_of(d);
-    g_disp_fwd = TMA_DISPATCH_NONE;
-    const int32_t capped = ceil_div(n, 32) > 4096 ? TMA_DISPATCH_GRID_CAPPED : 0;  // (the column-parallel kernels: 4096 groups of 32 rows, then grid-stride)
-    if (L.img_pi >= 0) {
-        g_disp_fwd = TMA_DISPATCH_FWD_H64;
-        if constexpr (MODE == 2) return launch_fwd_h64<2>(params, L, nullptr, n, 0, 0, 0, 1, nullptr, nullptr, nullptr, obs, trunc, gamma, rewards, s);
-        else if constexpr (MODE == 3) return launch_fwd_h64<3>(params, L, obs, n, 0, 0, 0, 1, actions, values, logp, nullptr, nullptr, 0.0f, rewards, s);
-        else return launch_fwd_h64<MODE>(params, L, obs, n, seed, step, env_offset, deterministic, actions, values, logp, nullptr, nullptr, 0.0f, nullptr, s);
-    }
-    if (L.bf16) {
-        g_disp_fwd = (d->continuous ? TMA_DISPATCH_FWD_BF16_NTW2_BOX : TMA_DISPATCH_FWD_BF16_NTW2_DISCRETE) + (L.H / 64 - 2) | capped;
-        const int smemw = fwd_wide_bf_smem_bytes(L.D, L.H);
-        int64_t groups = ceil_div(n, 32);
-        if (groups > 4096) groups = 4096;
-        auto launchw = [&](auto k) -> int {
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smemw));
-            k<<<dim3((unsigned)((MODE == 0 || MODE == 3) ? 2 * groups : groups)), dim3(256), smemw, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions,
-                                                                                           values, logp, trunc, gamma, rewards);
-            return TMA_OK;
-        };
-        int wrc;
-        if (d->continuous) wrc = L.H == 256 ? launchw(policy_fwd_wide_kernel<true, MODE, 4, true>) : (L.H == 192 ? launchw(policy_fwd_wide_kernel<true, MODE, 3, true>) : launchw(policy_fwd_wide_kernel<true, MODE, 2, true>));
-        else wrc = L.H == 256 ? launchw(policy_fwd_wide_kernel<false, MODE, 4, true>) : (L.H == 192 ? launchw(policy_fwd_wide_kernel<false, MODE, 3, true>) : launchw(policy_fwd_wide_kernel<false, MODE, 2, true>));
-        if (wrc) return wrc;
+    const FwdPlan p = plan_fwd(L, n, MODE);
+    g_disp_fwd = p.id;
+    auto launch = [&](auto k, bool opt_in) -> int {
+        if (opt_in) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions, values, logp, trunc, gamma, rewards);
         TMA_LAUNCH_CHECK();
         return TMA_OK;
+    };
+    switch (p.family) {
+    case FwdFamily::Refused: return refuse(L, p);  // before any launch
+    case FwdFamily::H64:
+        if constexpr (MODE == 2) return launch_fwd_h64<2>(p, params, L, nullptr, n, 0, 0, 0, 1, nullptr, nullptr, nullptr, obs, trunc, gamma, rewards, s);
+        else if constexpr (MODE == 3) return launch_fwd_h64<3>(p, params, L, obs, n, 0, 0, 0, 1, actions, values, logp, nullptr, nullptr, 0.0f, rewards, s);
+        else return launch_fwd_h64<MODE>(p, params, L, obs, n, seed, step, env_offset, deterministic, actions, values, logp, nullptr, nullptr, 0.0f, nullptr, s);
+    case FwdFamily::WideF32:
+    case FwdFamily::WideBF16:
+        return with_cont_ntw(p.cont, p.ntw, [&](auto c, auto ntw) -> int {
+            constexpr bool C = decltype(c)::value;
+            constexpr int NTW = decltype(ntw)::value;
+            return p.family == FwdFamily::WideBF16 ? launch(policy_fwd_wide_kernel<C, MODE, NTW, true>, true) : launch(policy_fwd_wide_kernel<C, MODE, NTW, false>, true);
+        });
+    case FwdFamily::Generic: break;
     }
-    if ((L.H == 128 || L.H == 192 || L.H == 256) && fwd_wide_smem_bytes(L) <= 160 * 1024) {
-        g_disp_fwd = (d->continuous ? TMA_DISPATCH_FWD_F32_NTW2_BOX : TMA_DISPATCH_FWD_F32_NTW2_DISCRETE) + (L.H / 64 - 2) | capped;
-        const int smemw = fwd_wide_smem_bytes(L);
-        int64_t groups = ceil_div(n, 32);
-        if (groups > 4096) groups = 4096;
-        auto launchw = [&](auto k) -> int {
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smemw));
-            k<<<dim3((unsigned)((MODE == 0 || MODE == 3) ? 2 * groups : groups)), dim3(256), smemw, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions,
-                                                                                           values, logp, trunc, gamma, rewards);
-            return TMA_OK;
-        };
-        int wrc;
-        if (d->continuous) wrc = L.H == 256 ? launchw(policy_fwd_wide_kernel<true, MODE, 4, false>) : (L.H == 192 ? launchw(policy_fwd_wide_kernel<true, MODE, 3, false>) : launchw(policy_fwd_wide_kernel<true, MODE, 2, false>));
-        else wrc = L.H == 256 ? launchw(policy_fwd_wide_kernel<false, MODE, 4, false>) : (L.H == 192 ? launchw(policy_fwd_wide_kernel<false, MODE, 3, false>) : launchw(policy_fwd_wide_kernel<false, MODE, 2, false>));
-        if (wrc) return wrc;
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
+    return p.cont ? launch(policy_fwd_kernel<true, MODE>, p.lds > LDS_OPT_IN) : launch(policy_fwd_kernel<false, MODE>, p.lds > LDS_OPT_IN);
+}
+
+// The dispatchers' environment switches, each read where the parent dispatchers read it: DispatchSwitches says which once per process and which on
+// each call.  Only the f32 column-parallel shapes read more than the gradient's two cached ones (for_grad = false: tma_ppo_adam_step_local)
+static DispatchSwitches read_switches(const PLayout &L, int64_t count, bool for_grad) {
+    DispatchSwitches w{};
+    if (for_grad) {
+        static const bool force_wide = getenv("TMA_FORCE_WIDE") != nullptr;
+        static const int bf_debug = getenv("TMA_BF_DEBUG") ? atoi(getenv("TMA_BF_DEBUG")) : 0;
+        w.force_wide = force_wide, w.bf_debug = bf_debug;
     }
-    const int64_t tiles = ceil_div(n, 16);
-    int wpb = tiles >= 1024 ? 4 : 1;  // small batches: one wave per block so every CU gets work
-    while (wpb > 1 && fwd_smem_bytes(L, wpb) > 64 * 1024) wpb >>= 1;
-    const int smem = fwd_smem_bytes(L, wpb);
-    // (check_dims accepts up to 4096 observations and 1024 hidden units: refuse here, before any launch, what one wave's tile cannot hold)
-    if (smem > 160 * 1024) return fail(TMA_ERR_INVALID, "policy too wide for the forward kernel's LDS-resident tile (obs_dim %d, hidden %d: needs %d bytes)", L.D, L.H, smem);
-    int64_t blocks = ceil_div(tiles, wpb);
-    g_disp_fwd = (wpb == 4 ? TMA_DISPATCH_FWD_GENERIC_W4 : (wpb == 2 ? TMA_DISPATCH_FWD_GENERIC_W2 : TMA_DISPATCH_FWD_GENERIC_W1)) | (blocks > 8192 ? TMA_DISPATCH_GRID_CAPPED : 0);
-    if (blocks > 8192) blocks = 8192;
-    if (d->continuous) {
-        auto k = policy_fwd_kernel<true, MODE>;
-        if (smem > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        k<<<dim3((unsigned)blocks), dim3(64 * wpb), smem, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions, values, logp,
-                                                               trunc, gamma, rewards);
-    } else {
-        auto k = policy_fwd_kernel<false, MODE>;
-        if (smem > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        k<<<dim3((unsigned)blocks), dim3(64 * wpb), smem, s>>>(params, L, obs, n, seed, step, env_offset, deterministic, actions, values, logp,
-                                                               trunc, gamma, rewards);
+    if (!grad_wide_f32_shape(L)) return w;
+    if (!for_grad) {
+        w.force_wide_now = getenv("TMA_FORCE_WIDE") != nullptr;
+        return w;
     }
+    static const bool no_half = getenv("TMA_NO_HALF_GROUPS") != nullptr, no_defer = getenv("TMA_NO_DEFER_W2") != nullptr;
+    w.no_half = no_half, w.no_defer = no_defer;
+    w.nw4 = getenv("TMA_WIDE_NW4") != nullptr;
+    w.no_dz1 = getenv("TMA_NO_DZ1_CACHE") != nullptr;
+    w.split3 = tma_split3_eligible(L, count);
+    return w;
+}
+
+static int refuse(const GradPlan &p) { return fail(TMA_ERR_INVALID, "policy too wide for the LDS-resident tile (needs %d bytes)", p.lds); }
+
+// grad (+)= the sum of the slabs in a fixed order, and its sum-of-squares partials.  n_vf < 0: every parameter over n_pi slabs (the H = 64 kernel's
+// block pairs); else the value net's parameters over the first n_vf of them
+static int launch_slab_reduce(const float *slabs, int n_pi, int n_vf, const PLayout &L, float *grad, char *ws, hipStream_t s, int overwrite = 0,
+                              const PeerPush *push = nullptr) {
+    slab_reduce_kernel<<<dim3((unsigned)ceil_div(L.P, 64)), dim3(256), 0, s>>>(slabs, n_pi, L.P, grad, n_vf, n_vf < 0 ? 0 : L.vW1t, n_vf < 0 ? 0 : L.log_std,
+                                                                               sq_partials(ws, L), overwrite, push ? *push : PeerPush{});
     TMA_LAUNCH_CHECK();
     return TMA_OK;
+}
+
+// The f32 column-parallel gradient kernel of a plan: the one place its (kt1, half, eight, dz1_cached) become the KT1C / PASS / NQ1C / HALF / NW
+// template arguments.  aux: eight waves -- the dW2 deferral buffer (or null); four -- the dz1 cache of the two-pass kernels (or null: recompute)
+template <bool C, int NTW>
+static int launch_grad_wide(const GradPlan &p, const float *params, const PLayout &L, const Rollout &R, const Minibatch &M, const HParams &hpar,
+                            const float *ws_adv, float *slabs, double *slots, float *aux, hipStream_t s) {
+    auto launch = [&](auto k, float *aux_k) -> int {
+        TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, s>>>(params, L, R, M, hpar, ws_adv, slabs, slots, p.n_pi, aux_k,
+                                                               p.eight ? (int64_t)2 * W2_DEFER_ROWS * L.H : DZ1_CAP * L.H);
+        return TMA_OK;
+    };
+    if constexpr (NTW == 4) {  // H = 256, single-pass shapes: eight waves of 32 columns (TMA_WIDE_NW4=1: four of 64)
+        if (p.eight && p.kt1 == 1) return p.half ? launch(ppo_grad_wide_kernel<C, 2, 1, 0, 0, true, 8>, aux) : launch(ppo_grad_wide_kernel<C, 2, 1, 0, 0, false, 8>, aux);
+        if (p.eight && p.kt1 == 2) return p.half ? launch(ppo_grad_wide_kernel<C, 2, 2, 0, 0, true, 8>, aux) : launch(ppo_grad_wide_kernel<C, 2, 2, 0, 0, false, 8>, aux);
+        if (p.eight && p.kt1 == 7) return launch(ppo_grad_wide_kernel<C, 2, 7, 0, 0, true, 8>, aux);  // (small7 implies half groups)
+    }
+    if (p.kt1 == 1) return p.half ? launch(ppo_grad_wide_kernel<C, NTW, 1, 0, 0, true>, nullptr) : launch(ppo_grad_wide_kernel<C, NTW, 1>, nullptr);
+    if (p.kt1 == 2) return p.half ? launch(ppo_grad_wide_kernel<C, NTW, 2, 0, 0, true>, nullptr) : launch(ppo_grad_wide_kernel<C, NTW, 2>, nullptr);
+    if (p.kt1 == 11) {  // chain pass, then dW1 from the cached operands or from a recomputed chain
+        const int rc = launch(ppo_grad_wide_kernel<C, NTW, -1, 0, 11>, aux);
+        if (rc) return rc;
+        return p.dz1_cached ? launch(ppo_grad_wide_kernel<C, NTW, 11, 2, 11>, aux) : launch(ppo_grad_wide_kernel<C, NTW, 11, 1, 11>, nullptr);
+    }
+    if constexpr (C && NTW == 4) {
+        if (p.kt1 == 107) {
+            const int rc = launch(ppo_grad_wide_kernel<true, 4, -1, 0, 7>, aux);
+            if (rc) return rc;
+            return p.dz1_cached ? launch(ppo_grad_wide_kernel<true, 4, 7, 2, 7>, aux) : launch(ppo_grad_wide_kernel<true, 4, 7, 1, 7>, nullptr);
+        }
+    }
+    return launch(ppo_grad_wide_kernel<C, NTW, 0>, nullptr);
 }
 
 }  // namespace tma
@@ -2499,9 +2514,9 @@ int tma_policy_act_bootstrap(const float *params, const tma_policy_dims *d, cons
     if (n < 1) return fail(TMA_ERR_INVALID, "tma_policy_act_bootstrap: n must be >= 1");
     const PLayout L = layout_of(d);
     const bool boot = prev_terminal_obs && prev_truncated && prev_rewards_inout;
-    if (L.img_pi >= 0) {  // one launch: bootstrap of the previous step folded into this step's forward
-        g_disp_fwd = TMA_DISPATCH_FWD_H64;
-        return launch_fwd_h64<0>(params, L, obs, n, rng_seed, rng_step, env_offset, 0, actions_out, values_out, logp_out, boot ? prev_terminal_obs : nullptr,
+    if (const FwdPlan p = plan_fwd(L, n, 0); p.family == FwdFamily::H64) {  // one launch: bootstrap of the previous step folded into this step's forward
+        g_disp_fwd = p.id;
+        return launch_fwd_h64<0>(p, params, L, obs, n, rng_seed, rng_step, env_offset, 0, actions_out, values_out, logp_out, boot ? prev_terminal_obs : nullptr,
                                  boot ? prev_truncated : nullptr, (float)gamma, boot ? prev_rewards_inout : nullptr, (hipStream_t)stream);
     }
     if (boot) {
@@ -2572,13 +2587,13 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
     if (prepared && (mbi->prepared_batch < 256 || total > OFFS_CAP || mbi->start % mbi->prepared_batch != 0 || mbi->count > mbi->prepared_batch))
         return fail(TMA_ERR_INVALID, "minibatch [%lld, +%lld) does not match the prepared epoch split (batch %lld)", (long long)mbi->start,
                     (long long)mbi->count, (long long)mbi->prepared_batch);
-    static const int bf_debug = getenv("TMA_BF_DEBUG") ? atoi(getenv("TMA_BF_DEBUG")) : 0;
-    HParams hpar{(float)hp->clip_range, (float)hp->ent_coef, (float)hp->vf_coef, (hp->normalize_advantage && mbi->count > 1) ? 1 : 0, bf_debug};
+    const DispatchSwitches sw = read_switches(L, mbi->count, true);
+    const GradPlan p = plan_grad(L, d->continuous != 0, mbi->count, prepared, hp->normalize_advantage != 0, sw);
+    g_disp_grad = p.id;
+    HParams hpar{(float)hp->clip_range, (float)hp->ent_coef, (float)hp->vf_coef, p.normalize ? 1 : 0, sw.bf_debug};
     char *ws = static_cast<char *>(workspace);
     float *ws_adv = reinterpret_cast<float *>(ws + WS_ADV);
     double *slots = reinterpret_cast<double *>(ws + WS_STATS);
-    const int64_t tiles = ceil_div(mbi->count, 16);
-    const bool h64 = L.img_pi >= 0 && tiles >= 16;  // >= 256 samples: persistent LDS-image kernel; smaller batches: generic kernel
     double *adv_part = reinterpret_cast<double *>(ws + WS_ADV_PART);
     int nbk = (int)ceil_div(mbi->count, 1024);
     if (nbk > ADV_BLOCKS) nbk = ADV_BLOCKS;
@@ -2589,188 +2604,70 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
         adv_part = reinterpret_cast<double *>(ws + offs_base + OFFS_CAP * 4) + 2 * (mbi->start / mbi->prepared_batch) * stride;
         M.offs = reinterpret_cast<int32_t *>(ws + offs_base) + mbi->start;
     }
-    // offsets cache: written by the advantage pass, read by every gradient kernel (saves the permutation arithmetic per sample)
-    int32_t *offs = (!prepared && mbi->count <= OFFS_CAP && (hpar.normalize_advantage || L.bf16)) ? reinterpret_cast<int32_t *>(ws + offs_base) : nullptr;
-    if (!prepared && (hpar.normalize_advantage || offs)) {
+    if (p.adv_partial) {
+        int32_t *offs = p.offs_cache ? reinterpret_cast<int32_t *>(ws + offs_base) : nullptr;
         adv_partial_kernel<<<dim3(nbk), dim3(256), 0, s>>>(rb->advantages, M, rb->T, rb->N, adv_part, offs);
         TMA_LAUNCH_CHECK();
         M.offs = offs;
     }
     M.adv_part = adv_part, M.adv_n_part = nbk;
-    static const bool force_wide = getenv("TMA_FORCE_WIDE") != nullptr;  // test hook: take the column-parallel kernel at any batch size
-    const bool wide_f32 = !L.bf16 && (L.H == 128 || L.H == 192 || L.H == 256) && (tiles >= 8 || force_wide) && grad_wide_smem_bytes(L) <= 160 * 1024;
-    if (hpar.normalize_advantage) {
-        if (!h64 && !L.bf16 && !wide_f32) {  // the H = 64 and the column-parallel kernels fold the partials themselves
-            adv_final_kernel<<<dim3(1), dim3(64), 0, s>>>(adv_part, nbk, M.stats_n, ws_adv);
-            TMA_LAUNCH_CHECK();
-        }
-    }
-    if (h64) {
-        // register-accumulating persistent kernel (tma_h64.hip) + deterministic slab reduction
-        g_disp_grad = tiles <= H64_BLOCKS ? TMA_DISPATCH_GRAD_H64_SMALL : TMA_DISPATCH_GRAD_H64;  // (tma_launch_grad_h64: one tile per wave up to 2048 samples)
-        float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
-        int blocks4 = 0;
-        int lrc;
-        {
-            GradTimer timer(s);
-            lrc = tma_launch_grad_h64(params, L, R, M, hpar, adv_part, nbk, slabs, slots, &blocks4, s, fold, next);
-        }
-        if (lrc) return lrc;
-        slab_reduce_kernel<<<dim3((unsigned)ceil_div(L.P, 64)), dim3(256), 0, s>>>(slabs, (int)blocks4, L.P, grad, -1, 0, 0, sq_partials(ws, L), overwrite,
-                                                                                   push ? *push : PeerPush{});
+    if (p.adv_final) {
+        adv_final_kernel<<<dim3(1), dim3(64), 0, s>>>(adv_part, nbk, M.stats_n, ws_adv);
         TMA_LAUNCH_CHECK();
-        return TMA_OK;
     }
-    if (fold || overwrite || push || next) return fail(TMA_ERR_INVALID, "internal: folded optimizer step outside the H = 64 fast path");
-    if (L.bf16) {  // column-parallel bf16-MFMA kernel (tma_bf16.hip) + deterministic slab reduction
-        g_disp_grad = TMA_DISPATCH_GRAD_BF16;
+    const bool h64 = p.family == GradFamily::H64Small || p.family == GradFamily::H64;
+    if (!h64 && (fold || overwrite || push || next)) return fail(TMA_ERR_INVALID, "internal: folded optimizer step outside the H = 64 fast path");
+    float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
+    int n_pi = p.n_pi, n_vf = p.n_vf, lrc = TMA_OK;  // slabs the reduction sums (the inner launchers say how many they wrote)
+    switch (p.family) {  // the dominant kernel, between the GradTimer's events
+    case GradFamily::Refused: return refuse(p);
+    case GradFamily::H64Small:
+    case GradFamily::H64: {
+        GradTimer timer(s);
+        n_vf = -1;
+        lrc = tma_launch_grad_h64(params, L, R, M, hpar, adv_part, nbk, slabs, slots, &n_pi, s, fold, next);
+    } break;
+    case GradFamily::BF16: {
         if ((int64_t)rb->T * rb->N * L.D >= (int64_t)1 << 31)  // (its observation gather indexes the buffer with 32-bit arithmetic)
             return fail(TMA_ERR_INVALID, "bf16 update: T * N * obs_dim = %lld exceeds 2^31", (long long)((int64_t)rb->T * rb->N * L.D));
-        float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
-        int n_pi = 0, n_vf = 0, lrc;
+        GradTimer timer(s);
+        lrc = tma_launch_grad_wide_bf(params, L, R, M, hpar, ws_adv, slabs, slots, ws, &n_pi, &n_vf, s);
+    } break;
+    case GradFamily::BF16X3: {
+        GradTimer timer(s);
+        lrc = tma_launch_grad_split3(params, L, R, M, hpar, slabs, slots, &n_pi, &n_vf, s);
+    } break;
+    case GradFamily::WideF32: {
+        if (p.kt1 == 7 && !p.defer_w2) return fail(TMA_ERR_INVALID, "internal: the kt1 = 7 half-group kernel needs the dW2 deferral buffer (%lld samples)", (long long)mbi->count);
+        if (p.kt1 == 0 && (lrc = tma_launch_slab_zero_w1(slabs, p.n_pi, L, s))) return lrc;
+        float *const aux = p.defer_w2 ? slabs + (int64_t)64 * L.P  // behind slab 64 of the workspace's slab area
+                         : (p.dz1_cached ? reinterpret_cast<float *>(ws + offs_base + OFFS_CAP * 4 + EPOCH_PART_BYTES + WIDE_SQ_SLOTS * 8) : nullptr);
         {
             GradTimer timer(s);
-            lrc = tma_launch_grad_wide_bf(params, L, R, M, hpar, ws_adv, slabs, slots, ws, &n_pi, &n_vf, s);
-        }
-        if (lrc) return lrc;
-        slab_reduce_kernel<<<dim3((unsigned)ceil_div(L.P, 64)), dim3(256), 0, s>>>(slabs, n_pi, L.P, grad, n_vf, L.vW1t, L.log_std, sq_partials(ws, L));
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
-    }
-    if (wide_f32 && tma_split3_eligible(L, mbi->count)) {  // mfma_dtype = 2: the same update on the bf16 MFMA, every operand as three bf16 terms
-        g_disp_grad = TMA_DISPATCH_GRAD_BF16X3;
-        float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
-        int n_pi = 0, n_vf = 0, lrc;
-        {
-            GradTimer timer(s);
-            lrc = tma_launch_grad_split3(params, L, R, M, hpar, slabs, slots, &n_pi, &n_vf, s);
-        }
-        if (lrc) return lrc;
-        slab_reduce_kernel<<<dim3((unsigned)ceil_div(L.P, 64)), dim3(256), 0, s>>>(slabs, n_pi, L.P, grad, n_vf, L.vW1t, L.log_std, sq_partials(ws, L));
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
-    }
-    if (wide_f32) {
-        // column-parallel register-accumulating kernel + deterministic slab reduction
-        const int smemw = grad_wide_smem_bytes(L);
-        // small minibatches on single-pass shapes (D <= 32): 16-row half groups, so that the reference's literal batch_size = 256 runs on 32
-        // workgroups instead of 16 (TMA_NO_HALF_GROUPS=1: 32-row groups throughout)
-        // Round 6: ... and observations of up to 112 floats (the reference's `ant` task: Ant-v5, 105 observations, batch_size 256) on the same
-        // half groups with dW1 in registers (7 k-tiles: the eight-wave half-group kernel defers dW2, so it has them) -- that width took the
-        // runtime-width kernel with dW1 accumulated in the slab: 99.5 us per 256-sample gradient launch
-        static const bool no_half = getenv("TMA_NO_HALF_GROUPS") != nullptr;
-        static const bool no_defer = getenv("TMA_NO_DEFER_W2") != nullptr;  // (small7 and defer_w2 below read this one value: small7 has no dW2 accumulators)
-        const bool nw4 = getenv("TMA_WIDE_NW4") != nullptr;
-        const bool small7 = L.H == 256 && L.D > 32 && L.D <= 112 && mbi->count <= 1024 && !no_half && !nw4 && !no_defer &&
-                            (int64_t)64 * L.P + 4 * (int64_t)W2_DEFER_ROWS * L.H <= (int64_t)slab_cap(L) * L.P;  // (the deferral buffer must fit: that kernel has no dW2 accumulators)
-        const bool half = (L.D <= 32 || small7) && mbi->count <= 1024 && !no_half;  // (at 2048 samples the doubled slab count costs more than the shorter groups save: 79.6 against 76.6 us per call)
-        const int64_t groups = ceil_div(mbi->count, half ? 16 : 32);  // one row group per block while there are CUs to spare, then grid-stride
-        const int cap_pi = d->continuous ? 136 : 128, cap_vf = 256 - cap_pi;  // measured: the Categorical head leaves the two nets balanced
-        const int n_pi = (int)(groups < cap_pi ? groups : cap_pi), n_vf = (int)(groups < cap_vf ? groups : cap_vf);
-        const int64_t pairs = n_pi;  // slabs in use (the value net uses the first n_vf of them)
-        float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
-        // dW1: D <= 32 in registers; D in 161..176 (Crawler's 172: 11 k-tiles) by a second pass that keeps only dW1 in registers;
-        // any other width accumulates it in place in the slab
-        // (round 6: 97..112 observations with a Box head at H = 256 -- Ant-v5's 105 -- by the same two passes with seven k-tiles: kt1 = 107, "7 in two passes")
-        const int kt1 = L.D <= 16 ? 1 : (L.D <= 32 ? 2 : (small7 ? 7 : ((L.D > 160 && L.D <= 176) ? 11 : ((f32_two_pass(L) && L.D <= 112) ? 107 : 0))));
-        if (kt1 == 0) {
-            slab_zero_w1_kernel<<<dim3(256), dim3(256), 0, s>>>(slabs, (int)pairs, L);
-            TMA_LAUNCH_CHECK();
-        }
-        auto launch = [&](auto k, float *dz1 = nullptr) -> int {
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smemw));
-            k<<<dim3((unsigned)(n_pi + n_vf)), dim3(256), smemw, s>>>(params, L, R, M, hpar, ws_adv, slabs, slots, n_pi, dz1, DZ1_CAP * L.H);
-            return TMA_OK;
-        };
-        const bool eight = L.H == 256 && (kt1 == 1 || kt1 == 2 || kt1 == 7) && !nw4;
-        const int smem8 = grad_wide_smem_bytes(L, 8);
-        // half groups on the eight-wave kernel (<= 1024 samples: <= 64 slabs in use): dW2 deferred to wide_small_reduce_kernel through a buffer behind
-        // slab 64 of the workspace's slab area (TMA_NO_DEFER_W2=1: the slab path throughout)
-        const bool defer_w2 = half && eight && !no_defer && n_pi <= 64 && groups * 16 <= W2_DEFER_ROWS && (int64_t)64 * L.P + 4 * (int64_t)W2_DEFER_ROWS * L.H <= (int64_t)slab_cap(L) * L.P;
-        float *const w2buf = defer_w2 ? slabs + (int64_t)64 * L.P : nullptr;
-        if (kt1 == 7 && !w2buf) return fail(TMA_ERR_INVALID, "internal: the kt1 = 7 half-group kernel needs the dW2 deferral buffer (%lld samples)", (long long)mbi->count);
-        auto launch8 = [&](auto k) -> int {
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem8));
-            k<<<dim3((unsigned)(n_pi + n_vf)), dim3(512), smem8, s>>>(params, L, R, M, hpar, ws_adv, slabs, slots, n_pi, w2buf, (int64_t)2 * W2_DEFER_ROWS * L.H);
-            return TMA_OK;
-        };
-        // (as on the bf16 path) minibatches that fit the dz1 cache: chain pass + dW1 from the cached operands; else chain + recompute
-        float *const dz1_cache = (f32_two_pass(L) && (kt1 == 11 || kt1 == 107) && mbi->count <= DZ1_CAP && !getenv("TMA_NO_DZ1_CACHE"))
-            ? reinterpret_cast<float *>(ws + WS_SLABS + (int64_t)slab_cap(L) * L.P * 4 + OFFS_CAP * 4 + EPOCH_PART_BYTES + WIDE_SQ_SLOTS * 8) : nullptr;
-        if (kt1 == 7) g_disp_grad = TMA_DISPATCH_GRAD_F32_SMALL7;
-        else if (kt1 == 1 || kt1 == 2) {
-            const bool k2 = kt1 == 2;
-            if (eight) g_disp_grad = half ? (defer_w2 ? (k2 ? TMA_DISPATCH_GRAD_F32_KT2_HALF_W8_DEFER : TMA_DISPATCH_GRAD_F32_KT1_HALF_W8_DEFER)
-                                                      : (k2 ? TMA_DISPATCH_GRAD_F32_KT2_HALF_W8_SLAB : TMA_DISPATCH_GRAD_F32_KT1_HALF_W8_SLAB))
-                                          : (k2 ? TMA_DISPATCH_GRAD_F32_KT2_FULL_W8 : TMA_DISPATCH_GRAD_F32_KT1_FULL_W8);
-            else g_disp_grad = half ? (k2 ? TMA_DISPATCH_GRAD_F32_KT2_HALF_W4 : TMA_DISPATCH_GRAD_F32_KT1_HALF_W4)
-                                    : (k2 ? TMA_DISPATCH_GRAD_F32_KT2_FULL_W4 : TMA_DISPATCH_GRAD_F32_KT1_FULL_W4);
-        } else if (kt1 == 11) g_disp_grad = dz1_cache ? TMA_DISPATCH_GRAD_F32_KT11_CACHED : TMA_DISPATCH_GRAD_F32_KT11_RECOMPUTE;
-        else if (kt1 == 107) g_disp_grad = dz1_cache ? TMA_DISPATCH_GRAD_F32_KT107_CACHED : TMA_DISPATCH_GRAD_F32_KT107_RECOMPUTE;
-        else g_disp_grad = TMA_DISPATCH_GRAD_F32_KT0;
-        auto pick = [&](auto ntw) -> int {
-            constexpr int NTWc = decltype(ntw)::value;
-            auto both = [&](auto cont) -> int {
-                constexpr bool C = decltype(cont)::value;
-                if constexpr (NTWc == 4) {  // H = 256, single-pass shapes: eight waves of 32 columns (TMA_WIDE_NW4=1: four of 64)
-                    if (eight && kt1 == 1) return half ? launch8(ppo_grad_wide_kernel<C, 2, 1, 0, 0, true, 8>) : launch8(ppo_grad_wide_kernel<C, 2, 1, 0, 0, false, 8>);
-                    if (eight && kt1 == 2) return half ? launch8(ppo_grad_wide_kernel<C, 2, 2, 0, 0, true, 8>) : launch8(ppo_grad_wide_kernel<C, 2, 2, 0, 0, false, 8>);
-                    if (eight && kt1 == 7) return launch8(ppo_grad_wide_kernel<C, 2, 7, 0, 0, true, 8>);  // (small7 implies half groups)
-                }
-                if (kt1 == 1) return half ? launch(ppo_grad_wide_kernel<C, NTWc, 1, 0, 0, true>) : launch(ppo_grad_wide_kernel<C, NTWc, 1>);
-                if (kt1 == 2) return half ? launch(ppo_grad_wide_kernel<C, NTWc, 2, 0, 0, true>) : launch(ppo_grad_wide_kernel<C, NTWc, 2>);
-                if (kt1 == 11) {
-                    const int rc2 = launch(ppo_grad_wide_kernel<C, NTWc, -1, 0, 11>, dz1_cache);
-                    if (rc2) return rc2;
-                    return dz1_cache ? launch(ppo_grad_wide_kernel<C, NTWc, 11, 2, 11>, dz1_cache) : launch(ppo_grad_wide_kernel<C, NTWc, 11, 1, 11>);
-                }
-                if constexpr (C && NTWc == 4) {
-                    if (kt1 == 107) {
-                        const int rc2 = launch(ppo_grad_wide_kernel<true, 4, -1, 0, 7>, dz1_cache);
-                        if (rc2) return rc2;
-                        return dz1_cache ? launch(ppo_grad_wide_kernel<true, 4, 7, 2, 7>, dz1_cache) : launch(ppo_grad_wide_kernel<true, 4, 7, 1, 7>);
-                    }
-                }
-                return launch(ppo_grad_wide_kernel<C, NTWc, 0>);
-            };
-            return d->continuous ? both(std::true_type{}) : both(std::false_type{});
-        };
-        int lrc;
-        {
-            GradTimer timer(s);
-            lrc = L.H == 256 ? pick(std::integral_constant<int, 4>{}) : (L.H == 192 ? pick(std::integral_constant<int, 3>{}) : pick(std::integral_constant<int, 2>{}));
+            lrc = with_cont_ntw(p.cont, p.ntw, [&](auto c, auto ntw) -> int {
+                return launch_grad_wide<decltype(c)::value, decltype(ntw)::value>(p, params, L, R, M, hpar, ws_adv, slabs, slots, aux, s);
+            });
         }
         if (lrc) return lrc;
         TMA_LAUNCH_CHECK();
-        if (defer_w2) {
-            wide_small_reduce_kernel<<<dim3((unsigned)(128 + ceil_div(L.P - 2 * L.H * L.H, 64))), dim3(1024), 0, s>>>(slabs, n_pi, n_vf, L, w2buf, (int)(groups * 16), grad,
+        if (p.reduce == GradReduce::WideSmall) {
+            wide_small_reduce_kernel<<<dim3((unsigned)(128 + ceil_div(L.P - 2 * L.H * L.H, 64))), dim3(1024), 0, s>>>(slabs, n_pi, n_vf, L, aux, (int)(p.groups * 16), grad,
                                                                                                                   sq_partials(ws, L));
             TMA_LAUNCH_CHECK();
-            return TMA_OK;
         }
-        slab_reduce_kernel<<<dim3((unsigned)ceil_div(L.P, 64)), dim3(256), 0, s>>>(slabs, n_pi, L.P, grad, n_vf, L.vW1t, L.log_std, sq_partials(ws, L));
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
+    } break;
+    case GradFamily::Generic: {
+        auto launch = [&](auto k) -> int {
+            if (p.lds > LDS_OPT_IN) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+            k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, s>>>(params, L, R, M, hpar, ws_adv, grad, slots);
+            TMA_LAUNCH_CHECK();
+            return TMA_OK;
+        };
+        lrc = p.cont ? launch(ppo_grad_kernel<true>) : launch(ppo_grad_kernel<false>);
+    } break;
     }
-    int wpb = tiles >= 512 ? 4 : 1;
-    while (wpb > 1 && grad_smem_bytes(L, wpb) > 156 * 1024) wpb--;
-    const int smem = grad_smem_bytes(L, wpb);
-    if (smem > 160 * 1024) return fail(TMA_ERR_INVALID, "policy too wide for the LDS-resident tile (needs %d bytes)", smem);
-    int64_t blocks = ceil_div(tiles, wpb);
-    g_disp_grad = (wpb == 4 ? TMA_DISPATCH_GRAD_GENERIC_W4 : (wpb == 3 ? TMA_DISPATCH_GRAD_GENERIC_W3 : (wpb == 2 ? TMA_DISPATCH_GRAD_GENERIC_W2 : TMA_DISPATCH_GRAD_GENERIC_W1))) |
-                  (blocks > MAX_GRAD_BLOCKS / 2 ? TMA_DISPATCH_GRID_CAPPED : 0);
-    if (blocks > MAX_GRAD_BLOCKS / 2) blocks = MAX_GRAD_BLOCKS / 2;
-    if (d->continuous) {
-        auto k = ppo_grad_kernel<true>;
-        if (smem > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        k<<<dim3((unsigned)(2 * blocks)), dim3(64 * wpb), smem, s>>>(params, L, R, M, hpar, ws_adv, grad, slots);
-    } else {
-        auto k = ppo_grad_kernel<false>;
-        if (smem > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        k<<<dim3((unsigned)(2 * blocks)), dim3(64 * wpb), smem, s>>>(params, L, R, M, hpar, ws_adv, grad, slots);
-    }
-    TMA_LAUNCH_CHECK();
-    return TMA_OK;
+    if (lrc || p.reduce != GradReduce::Slab) return lrc;
+    return launch_slab_reduce(slabs, n_pi, n_vf, L, grad, ws, s, overwrite, push);
 }
 
 // count a persistent-epoch fallback in the workspace (WS_PERSIST_ERR + 8: int64) and say so once per process
@@ -3242,6 +3139,48 @@ int tma_ppo_epoch_adv_sums(void *workspace, const tma_policy_dims *d, int64_t ba
     return TMA_OK;
 }
 
+// The optimizer step of a plan.  Scatter kernels: ONE multi-block Adam launch that also scatters the derived copies of the layouts that have them,
+// behind the norm partials of the (all-reduced, scaled) gradient -- which a _local call that does not fall through finds where the gradient's
+// reduction left them
+static int launch_opt(const OptPlan &p, bool local, float *params, float *grad, float *exp_avg, float *exp_avg_sq, const PLayout &L, int64_t step, double lr,
+                      double beta1, double beta2, double eps, double max_grad_norm, double grad_scale, char *ws, hipStream_t s) {
+    double *partials = reinterpret_cast<double *>(ws + WS_NORM_PART);
+    double *norm_out = reinterpret_cast<double *>(ws + WS_NORM_OUT);
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
+    if (p.kernels == OptKernels::ScatterH64 || p.kernels == OptKernels::ScatterWide) {
+        double *sqp = sq_partials(ws, L);
+        const int n_part = (int)ceil_div(L.P, 64);
+        if (!local || p.falls_through) {
+            grad_sumsq64_kernel<<<dim3((unsigned)n_part), dim3(64), 0, s>>>(grad, L.P, (float)grad_scale, sqp);
+            TMA_LAUNCH_CHECK();
+        }
+        if (p.kernels == OptKernels::ScatterH64)
+            adam_scatter_h64_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, sqp, n_part, (float)max_grad_norm,
+                                                                                     (float)step_size, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out,
+                                                                                     (float)grad_scale, params, exp_avg, exp_avg_sq);
+        else
+            adam_scatter_wide_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, sqp, n_part, (float)max_grad_norm,
+                                                                                      (float)step_size, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out,
+                                                                                      (float)grad_scale);
+        TMA_LAUNCH_CHECK();
+        return TMA_OK;
+    }
+    if (p.kernels == OptKernels::Small) {
+        opt_small_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, (float)grad_scale, (float)max_grad_norm,
+                                                                          (float)step_size, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out);
+        TMA_LAUNCH_CHECK();
+        return launch_sync(params, L, s);
+    }
+    const int nb = (int)p.grid;
+    grad_sumsq_kernel<<<dim3(nb), dim3(p.block), 0, s>>>(grad, L.P, (float)grad_scale, partials);
+    TMA_LAUNCH_CHECK();
+    adam_kernel<<<dim3(nb), dim3(p.block), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L.P, (float)grad_scale, partials, nb, (float)max_grad_norm, (float)step_size,
+                                                   (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out);
+    TMA_LAUNCH_CHECK();
+    return launch_sync(params, L, s);
+}
+
 int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg_sq, const tma_policy_dims *d, int64_t step, double lr, double beta1,
                       double beta2, double eps, double max_grad_norm, double grad_scale, void *workspace, void *stream) {
     g_disp_opt = TMA_DISPATCH_NONE;
@@ -3249,50 +3188,11 @@ int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg
     if (rc) return rc;
     if (!params || !grad || !exp_avg || !exp_avg_sq || !workspace) return fail(TMA_ERR_INVALID, "tma_ppo_adam_step: null buffer");
     if (step < 1) return fail(TMA_ERR_INVALID, "Adam step index must be >= 1");
-    hipStream_t s = (hipStream_t)stream;
     const PLayout L = layout_of(d);
-    char *ws = static_cast<char *>(workspace);
-    double *partials = reinterpret_cast<double *>(ws + WS_NORM_PART);
-    double *norm_out = reinterpret_cast<double *>(ws + WS_NORM_OUT);
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
-    double *sqp = sq_partials(ws, L);
-    const bool scat_h64 = L.img_pi >= 0 && L.P <= 64 * 256, scat_wide = L.bf16 || L.fr_pi >= 0;
-    if (sqp && (scat_h64 || scat_wide)) {
-        // layouts whose derived copies the optimizer kernel scatters itself: norm partials of the (all-reduced, scaled) gradient, then
-        // ONE multi-block Adam + scatter launch -- two launches instead of three to five
-        const int n_part = (int)ceil_div(L.P, 64);
-        g_disp_opt = scat_h64 ? TMA_DISPATCH_OPT_SCATTER_H64 : TMA_DISPATCH_OPT_SCATTER_WIDE;
-        grad_sumsq64_kernel<<<dim3((unsigned)n_part), dim3(64), 0, s>>>(grad, L.P, (float)grad_scale, sqp);
-        TMA_LAUNCH_CHECK();
-        if (scat_h64)
-            adam_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, sqp, n_part,
-                                                                                             (float)max_grad_norm, (float)step_size, (float)beta1, (float)beta2,
-                                                                                             (float)bc2_sqrt, (float)eps, norm_out, (float)grad_scale, params,
-                                                                                             exp_avg, exp_avg_sq);
-        else
-            adam_scatter_wide_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, sqp, n_part,
-                                                                                              (float)max_grad_norm, (float)step_size, (float)beta1, (float)beta2,
-                                                                                              (float)bc2_sqrt, (float)eps, norm_out, (float)grad_scale);
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
-    }
-    if (L.P <= 32768) {
-        g_disp_opt = TMA_DISPATCH_OPT_SMALL;
-        opt_small_kernel<<<dim3(1), dim3(1024), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, (float)grad_scale, (float)max_grad_norm, (float)step_size,
-                                                        (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out);
-        TMA_LAUNCH_CHECK();
-        return launch_sync(params, L, s);
-    }
-    g_disp_opt = TMA_DISPATCH_OPT_ADAM;
-    int nb = (int)ceil_div(L.P, 1024);
-    if (nb > 256) nb = 256;
-    grad_sumsq_kernel<<<dim3(nb), dim3(256), 0, s>>>(grad, L.P, (float)grad_scale, partials);
-    TMA_LAUNCH_CHECK();
-    adam_kernel<<<dim3(nb), dim3(256), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L.P, (float)grad_scale, partials, nb, (float)max_grad_norm,
-                                               (float)step_size, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out);
-    TMA_LAUNCH_CHECK();
-    return launch_sync(params, L, s);
+    const OptPlan p = plan_opt(L, false, 0, DispatchSwitches{});  // (the global step reads no switch)
+    g_disp_opt = p.id;
+    return launch_opt(p, false, params, grad, exp_avg, exp_avg_sq, L, step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, static_cast<char *>(workspace),
+                      (hipStream_t)stream);
 }
 
 int tma_ppo_adam_step_local(float *params, float *grad, float *exp_avg, float *exp_avg_sq, const tma_policy_dims *d, int64_t step, double lr,
@@ -3303,29 +3203,10 @@ int tma_ppo_adam_step_local(float *params, float *grad, float *exp_avg, float *e
     if (!params || !grad || !exp_avg || !exp_avg_sq || !workspace) return fail(TMA_ERR_INVALID, "tma_ppo_adam_step_local: null buffer");
     if (step < 1) return fail(TMA_ERR_INVALID, "Adam step index must be >= 1");
     const PLayout L = layout_of(d);
-    // the partials exist only when the last tma_ppo_minibatch_grad ended in slab_reduce_kernel: the H == 64 persistent kernel
-    // (>= 256 samples), the bf16 column-parallel kernel (any size) or the f32 column-parallel kernel (>= 128 samples)
-    char *ws = static_cast<char *>(workspace);
-    const bool h64 = L.img_pi >= 0 && last_count >= 256;
-    const bool wide_f32 = !L.bf16 && (L.H == 128 || L.H == 192 || L.H == 256) && last_count >= 128 && grad_wide_smem_bytes(L) <= 160 * 1024 &&
-                          getenv("TMA_FORCE_WIDE") == nullptr;
-    const double *sqp = sq_partials(ws, L);
-    if (!(h64 || L.bf16 || wide_f32) || !sqp || last_count < 1)
-        return tma_ppo_adam_step(params, grad, exp_avg, exp_avg_sq, d, step, lr, beta1, beta2, eps, max_grad_norm, 1.0, workspace, stream);
-    hipStream_t s = (hipStream_t)stream;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
-    g_disp_opt = h64 ? TMA_DISPATCH_OPT_LOCAL_SCATTER_H64 : TMA_DISPATCH_OPT_LOCAL_SCATTER_WIDE;
-    if (h64)
-        adam_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
-            params, grad, exp_avg, exp_avg_sq, L, sqp, (int)ceil_div(L.P, 64), (float)max_grad_norm, (float)step_size, (float)beta1, (float)beta2,
-            (float)bc2_sqrt, (float)eps, reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f, params, exp_avg, exp_avg_sq);
-    else
-        adam_scatter_wide_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
-            params, grad, exp_avg, exp_avg_sq, L, sqp, (int)ceil_div(L.P, 64), (float)max_grad_norm, (float)step_size, (float)beta1, (float)beta2,
-            (float)bc2_sqrt, (float)eps, reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f);
-    TMA_LAUNCH_CHECK();
-    return TMA_OK;
+    const OptPlan p = plan_opt(L, true, last_count, read_switches(L, last_count, false));
+    g_disp_opt = p.id;
+    return launch_opt(p, true, params, grad, exp_avg, exp_avg_sq, L, step, lr, beta1, beta2, eps, max_grad_norm, 1.0, static_cast<char *>(workspace),
+                      (hipStream_t)stream);
 }
 
 int tma_ppo_permutation(uint32_t perm_seed, uint32_t perm_epoch, int64_t total, int64_t *indices_out_host) {
@@ -3349,6 +3230,31 @@ int tma_debug_last_dispatch(int32_t *fwd_out, int32_t *grad_out, int32_t *opt_ou
     if (grad_out) *grad_out = g_disp_grad;
     if (opt_out) *opt_out = g_disp_opt;
     return TMA_OK;
+}
+
+int tma_debug_plan_dispatch(const tma_policy_dims *d, int which, int64_t n, int32_t *id_out, int64_t *grid_out, int32_t *block_out, int32_t *lds_bytes_out) {
+    const int rc = check_dims(d);
+    if (rc) return rc;
+    if (which < TMA_PLAN_FWD || which > TMA_PLAN_OPT_LOCAL) return fail(TMA_ERR_INVALID, "tma_debug_plan_dispatch: unknown dispatcher %d", which);
+    if (n < 1 && which <= TMA_PLAN_GRAD) return fail(TMA_ERR_INVALID, "tma_debug_plan_dispatch: n must be >= 1");
+    const PLayout L = layout_of(d);
+    auto out = [&](int32_t id, int64_t grid, int block, int lds) {
+        if (id_out) *id_out = id;
+        if (grid_out) *grid_out = grid;
+        if (block_out) *block_out = block;
+        if (lds_bytes_out) *lds_bytes_out = lds;
+        return TMA_OK;
+    };
+    if (which == TMA_PLAN_FWD) {
+        const FwdPlan p = plan_fwd(L, n, 0);
+        return p.family == FwdFamily::Refused ? refuse(L, p) : out(p.id, p.grid, p.block, p.lds);
+    }
+    if (which == TMA_PLAN_GRAD) {  // (neither a prepared epoch nor normalize_advantage moves the choice: they decide the advantage pre-launches)
+        const GradPlan p = plan_grad(L, d->continuous != 0, n, false, true, read_switches(L, n, true));
+        return p.family == GradFamily::Refused ? refuse(p) : out(p.id, p.grid, p.block, p.lds);
+    }
+    const OptPlan p = which == TMA_PLAN_OPT ? plan_opt(L, false, 0, DispatchSwitches{}) : plan_opt(L, true, n, read_switches(L, n, false));
+    return out(p.id, p.grid, p.block, 0);
 }
 
 int tma_debug_last_grad_kernel_us(float *us_out) {
