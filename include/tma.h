@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 213
+#define TMA_VERSION 214
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -420,6 +420,15 @@ enum {
     /* flag on a forward or generic-gradient id: the grid is capped and the kernel loops over it */
     TMA_DISPATCH_GRID_CAPPED = 256
 };
+/* The optimizer ids of the RMSpropTFLike step (tma_rmsprop_step / _local, ABI 214): the same six kernel shapes, chosen by the same plan -- the
+ * Adam id + 8.  (Not members of the enum above: that table is the one tests/test_policy_dispatch_gpu.py holds a float64 case for, id by id; these
+ * have theirs in tests/test_a2c_gpu.py.)  tma_debug_plan_dispatch answers with the Adam ids for both optimizers. */
+#define TMA_DISPATCH_OPT_RMSPROP_SCATTER_H64 72
+#define TMA_DISPATCH_OPT_RMSPROP_SCATTER_WIDE 73
+#define TMA_DISPATCH_OPT_RMSPROP_SMALL 74
+#define TMA_DISPATCH_OPT_RMSPROP_STEP 75
+#define TMA_DISPATCH_OPT_RMSPROP_LOCAL_SCATTER_H64 76
+#define TMA_DISPATCH_OPT_RMSPROP_LOCAL_SCATTER_WIDE 77
 int tma_debug_last_dispatch(int32_t *fwd_out, int32_t *grad_out, int32_t *opt_out);
 /* Test aid (ABI 213): what those dispatchers WOULD choose, asked on the host alone -- no HIP call, so it answers on a machine without a GPU.  `which`
  * selects the dispatcher and says what `n` is: TMA_PLAN_FWD -- tma_policy_act on n rows; TMA_PLAN_GRAD -- tma_ppo_minibatch_grad on a minibatch
@@ -444,6 +453,10 @@ int tma_ppo_pop_stats(void *workspace, double *out8_host, void *stream);
 int64_t tma_ppo_stats_staging_bytes(void);
 int tma_ppo_stats_enqueue(void *workspace, void *staging_host, void *stream);
 int tma_ppo_stats_fold(const void *staging_host, double *out8_host);
+
+/* Clear the statistic slots ordered on `stream` without reading them (ABI 214): the next tma_ppo_stats_enqueue / tma_ppo_pop_stats then reports
+ * the updates queued after this call alone. */
+int tma_ppo_stats_clear(void *workspace, void *stream);
 
 /* ---- native rollout loop: SB3 OnPolicyAlgorithm.collect_rollouts driven by model.learn()
  *      (backend/mlagents/training.py:166-170; SURVEY.md §3.1 loop A) without a host round-trip per step ---- */
@@ -481,6 +494,56 @@ int tma_debug_last_rollout_waves(void);
 int tma_gae_flags(const float *rewards, const float *values, const uint8_t *terminated, const uint8_t *truncated,
                   const float *last_values, double gamma, double gae_lambda, int T, int64_t N, float *adv_out, float *ret_out,
                   void *stream);
+
+/* ---- A2C (ABI 214): replaces the SB3 objects A2C("MlpPolicy", env, **kwargs) builds when backend/mlagents/training.py:150 is reached with
+ *      `--algorithm a2c` (algorithm table training.py:31-37; _default_model_kwargs gives A2C only tensorboard_log and verbose, so SB3's defaults:
+ *      net_arch [64, 64], n_steps 5, RMSpropTFLike(alpha 0.99, eps 1e-5), max_grad_norm 0.5).  Semantics: SB3 2.9. ----
+ * clip_grad_norm_(max_grad_norm) + RMSpropTFLike.step() (+ refresh of the derived copies): the counterpart of tma_ppo_adam_step, on the same
+ * kernel shapes (tma_debug_plan_dispatch(TMA_PLAN_OPT) names the shape; tma_debug_last_dispatch reports TMA_DISPATCH_OPT_RMSPROP_*).  With g the
+ * gradient scaled by grad_scale and by the clip coefficient min(1, max_grad_norm / (norm + 1e-6)):
+ *     square_avg = alpha * square_avg + (1 - alpha) * g * g          (the caller starts square_avg at ONES: the "TF-like" part)
+ *     p          = p - lr * g / sqrt(square_avg + eps)               (eps INSIDE the root)
+ * No weight decay, momentum or centering.  Per element in f32 with the IEEE square root and division; the norm is a fixed-order f64 sum, so the
+ * step is bit-identical from run to run.  grad is zero afterwards.  lr, eps >= 0 and finite, alpha in [0, 1).  Null buffers, bad dims and bad
+ * constants are refused (TMA_ERR_INVALID) before any HIP call. */
+int tma_rmsprop_step(float *params, float *grad, float *square_avg, const tma_policy_dims *d, double lr, double alpha, double eps, double max_grad_norm,
+                     double grad_scale, void *workspace, void *stream);
+/* The counterpart of tma_ppo_adam_step_local: `grad` is exactly what the LAST gradient call on this workspace produced over last_count samples; the
+ * norm partials are read where that gradient's reduction left them (where tma_debug_plan_dispatch(TMA_PLAN_OPT_LOCAL, last_count) says it did), else
+ * this is tma_rmsprop_step(grad_scale = 1). */
+int tma_rmsprop_step_local(float *params, float *grad, float *square_avg, const tma_policy_dims *d, double lr, double alpha, double eps, double max_grad_norm,
+                           void *workspace, void *stream, int64_t last_count);
+typedef struct {
+    double ent_coef, vf_coef;
+    int normalize_advantage;
+} tma_a2c_hparams;
+/* One A2C.train(): the gradient of  -(adv * log_prob).mean() + ent_coef * -(entropy.mean()) + vf_coef * mse(returns, values)  over all T * N samples
+ * of the rollout view as ONE minibatch, then tma_rmsprop_step_local, issued natively.  The gradient launches are tma_ppo_minibatch_grad's with a
+ * clip range that never clips: the surrogate is then -adv * ratio, whose gradient at ratio = 1 is the one above.
+ * CONTRACT: rb->log_probs are the log-probabilities of rb->actions under `params` -- what the rollout wrote.  A2C updates once, right after the
+ * rollout, so this holds by construction; a caller that fills the plane itself uses tma_policy_evaluate_actions on the same parameters.
+ * Batches of up to 256 samples that land on the generic gradient kernel (float atomics) run it as one wave per net, its tiles in turn, so
+ * that the update is bit-identical from run to run at A2C's batch sizes; the H = 64 and column-parallel kernels end in a fixed-order reduction anyway.
+ * Statistics (tma_ppo_stats_enqueue + tma_a2c_stats_fold): policy_loss is SB3's -(adv * log_prob).mean() (a reduction kernel of its own over the
+ * two planes), value_loss and entropy as PPO's; approx_kl and clip_fraction are not reported.  grad must be zero on entry and is zero on return. */
+int tma_a2c_update_local(float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_a2c_hparams *hp, float *grad, float *square_avg, double lr,
+                         double alpha, double eps, double max_grad_norm, void *workspace, void *stream);
+/* Its gradient half alone (the gradient launches and the policy-loss reduction; grad accumulates): what A2C(use_rms_prop=False) puts in front of
+ * tma_ppo_adam_step_local, as SB3 steps that variant with Adam. */
+int tma_a2c_grad(const float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_a2c_hparams *hp, float *grad, void *workspace, void *stream);
+/* n_iterations whole A2C iterations in one call, with no host-language round trip between them (at the reference's 8 envs x 5 steps an iteration
+ * is 40 samples: the path is launch- and host-bound).  Each iteration, in order: [copy of observation slot T into slot 0 -- from the second
+ * iteration on, and in front of the first when carry_first != 0], tma_rollout_collect over [0, T) with rng_step0 = (rollout_counter0 + i) * T (the
+ * sampling counters of PPO.collect_rollouts), tma_gae_flags, tma_ppo_pack_samples where the shape has records and `packed` is not NULL,
+ * tma_a2c_update_local.  The same launches in the same order as the per-iteration calls, hence the same bits.  advantages / returns: [T][N] planes
+ * the GAE writes; the statistic slots are cleared in front of the LAST iteration's update, so what a caller reads afterwards is that update's
+ * (SB3 logs the last update's losses).  `env` is a device handle: null arguments are refused before any HIP call, everything else needs the GPU. */
+int tma_a2c_iterations_local(tma_env *env, float *params, const tma_policy_dims *d, const tma_rollout_buffers *buffers, float *advantages, float *returns,
+                             float *packed, int T, uint32_t rng_seed, uint32_t rollout_counter0, uint32_t env_offset, double gamma, double gae_lambda,
+                             int carry_first, int n_iterations, const tma_a2c_hparams *hp, float *grad, float *square_avg, double lr, double alpha, double eps,
+                             double max_grad_norm, void *workspace, void *stream);
+/* tma_ppo_stats_fold for an A2C update: out8 = {sum of -(adv * log_prob), value_sq_err, entropy, 0, 0, n_samples, grad norm, clip coefficient} */
+int tma_a2c_stats_fold(const void *staging_host, double *out8_host);
 
 #ifdef __cplusplus
 }

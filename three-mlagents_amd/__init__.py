@@ -8,4 +8,16 @@ __version__ = "0.2.0"
 
 from .tasks import ENGINE_TASKS, EngineTask, make_env, resolve  # noqa: E402
 
-__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__"]
+__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C"]
+
+
+def __getattr__(name):  # the algorithm classes import torch: on first use, not with the task table
+    if name == "PPO":
+        from .ppo import PPO
+
+        return PPO
+    if name == "A2C":
+        from .a2c import A2C
+
+        return A2C
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

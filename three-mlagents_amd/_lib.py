@@ -37,6 +37,10 @@ class PPOHParams(C.Structure):
     _fields_ = [("clip_range", _f64), ("ent_coef", _f64), ("vf_coef", _f64), ("normalize_advantage", _i32)]
 
 
+class A2CHParams(C.Structure):
+    _fields_ = [("ent_coef", _f64), ("vf_coef", _f64), ("normalize_advantage", _i32)]
+
+
 class RolloutBuffers(C.Structure):
     _fields_ = [("obs", _vp), ("actions", _vp), ("rewards", _vp), ("values", _vp), ("log_probs", _vp), ("terminated", _vp),
                 ("truncated", _vp), ("terminal_obs", _vp), ("last_values", _vp), ("N", _i64), ("terminal_obs_slots", _i32)]
@@ -128,6 +132,14 @@ SIGNATURES = {
     "tma_comm_p2p_enable": (_i32, [_vp, _i32]),
     "tma_comm_p2p_set_timeout": (_i32, [_vp, C.c_double]),
     "tma_comm_p2p_status": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64)]),
+    "tma_ppo_stats_clear": (_i32, [_vp, _vp]),
+    "tma_rmsprop_step": (_i32, [_vp, _vp, _vp, _pd, _f64, _f64, _f64, _f64, _f64, _vp, _vp]),
+    "tma_rmsprop_step_local": (_i32, [_vp, _vp, _vp, _pd, _f64, _f64, _f64, _f64, _vp, _vp, _i64]),
+    "tma_a2c_update_local": (_i32, [_vp, _pd, C.POINTER(Rollout), C.POINTER(A2CHParams), _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp]),
+    "tma_a2c_grad": (_i32, [_vp, _pd, C.POINTER(Rollout), C.POINTER(A2CHParams), _vp, _vp, _vp]),
+    "tma_a2c_iterations_local": (_i32, [_vp, _vp, _pd, C.POINTER(RolloutBuffers), _vp, _vp, _vp, _i32, _u32, _u32, _u32, _f64, _f64, _i32, _i32,
+                                        C.POINTER(A2CHParams), _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp]),
+    "tma_a2c_stats_fold": (_i32, [_vp, C.POINTER(_f64)]),
     "tma_rollout_collect": (_i32, [_vp, _vp, _pd, C.POINTER(RolloutBuffers), _i32, _i32, _i32, _u32, _u32, _u32, _f64, _i32, _i32, _vp]),
 }
 

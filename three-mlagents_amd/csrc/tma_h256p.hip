@@ -5,7 +5,7 @@
 // party; the loop model.learn() drives at /root/reference/backend/mlagents/training.py:166-170 with batch_size = 256 from training.py:379
 // and net_arch = dict(pi=[256, 256], vf=[256, 256]) from training.py:363-365), every minibatch's forward / loss / backward /
 // clip_grad_norm_ / Adam step.  As launches that is three dependent kernels per optimizer step (ppo_grad_wide_kernel on 32 workgroups,
-// wide_small_reduce_kernel, adam_scatter_wide_kernel: 34 us, the gradient launch at 0.06 of the f32 MFMA peak): a 256-sample minibatch is
+// wide_small_reduce_kernel, opt_scatter_wide_kernel: 34 us, the gradient launch at 0.06 of the f32 MFMA peak): a 256-sample minibatch is
 // 207 MFLOP -- 1.3 us of the chip -- behind 547 KB of weights that every workgroup has to stream and a gradient that leaves as slabs.
 //
 // Here the step is COLUMN-parallel and resident.  Each net runs on the 32 CUs of one XCD (two XCDs in all: the nets only meet in the clip
@@ -151,7 +151,7 @@ __device__ __forceinline__ bool q_wait_flags(__amdgpu_buffer_rsrc_t reg, int off
         }                                                                               \
     } while (0)
 
-// torch.optim.Adam on one parameter with the clip-scaled gradient: adam_update_h64 (tma_mlp.h), the routine adam_scatter_wide_kernel runs too
+// torch.optim.Adam on one parameter with the clip-scaled gradient: adam_update_h64 (tma_mlp.h), the routine opt_scatter_wide_kernel runs too
 __device__ __forceinline__ float q_adam(float p, float g, float coef, float &mm, float &vv, float beta1, float beta2, float inv_bc2_sqrt, float eps,
                                         float lr_step) {
     const float gv = (g * 1.0f) * coef;
@@ -793,7 +793,7 @@ __device__ __forceinline__ void epoch256_body(const Epoch256Args &a, int cu0, fl
             coef = coef > 1.0f ? 1.0f : coef;
             if (a.max_norm <= 0.0f) coef = 1.0f;
             last_norm = total_norm, last_coef = coef;
-            const float lr_step = tbs.x, bc2_sqrt = 1.0f / tbs.y;  // (adam_scatter_wide_kernel: inv_bc2 = 1.0f / bc2_sqrt)
+            const float lr_step = tbs.x, bc2_sqrt = 1.0f / tbs.y;  // (opt_scatter_wide_kernel: inv_bc2 = 1.0f / bc2_sqrt)
             float *pw = W2s + (4 * r + kt_l) * 8 * W2S_LD + w2_row;
             f32x4 w = *reinterpret_cast<const f32x4 *>(pw);
 #pragma unroll

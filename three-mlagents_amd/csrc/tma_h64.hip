@@ -367,7 +367,7 @@ __device__ __forceinline__ void image_store_h64(float *wimg, int D, int n_out, i
 }
 
 // The pending optimizer step of AdamFold for this workgroup's net, results into the LDS image (and, from workgroup 0 of the net, into the
-// next half of the state double buffer).  clip_grad_norm_ + Adam exactly as adam_scatter_h64_kernel: same fold of the norm partials, same
+// next half of the state double buffer).  clip_grad_norm_ + Adam exactly as opt_scatter_h64_kernel: same fold of the norm partials, same
 // adam_update_h64.  Ownership is chosen for the LDS stores: threads 0..255 own one 4 x 4 block of W2t each -- rows kr + 16 jj, columns
 // nr + 16 j -- which is one float4 per row of the forward image ([k][n & 15][n >> 4]) and one float4 per column of the input-gradient image
 // ([n][k & 15][k >> 4]): 8 ds_write_b128 per thread instead of 32 scalar stores, half of them 64-way bank conflicts (a wave covers 8 nr x 8

@@ -433,7 +433,7 @@ __device__ __forceinline__ void epoch_body(const EpochArgs &a, int j, float *sme
         __syncthreads();
         if (!ok_s) return;
         HP_TICK(5);
-        // ---- global norm, clip coefficient, Adam on every parameter of this net (adam_scatter_h64_kernel's arithmetic) ----
+        // ---- global norm, clip coefficient, Adam on every parameter of this net (opt_scatter_h64_kernel's arithmetic) ----
         {
             f32x4 g_w2[4], g_ms[NM];
 #pragma unroll

@@ -142,7 +142,7 @@ __host__ __device__ inline PLayout make_layout(int D, int H, int A, int cont, in
 
 // One Adam step of parameter p with the clip-scaled gradient gv (torch.optim.Adam, no weight decay / amsgrad; SB3's optimizer, SURVEY.md
 // Appendix C.5) on the hardware sqrt / rcp units (1 ulp each; the update term carries ~3 ulp, i.e. ~1e-10 absolute at lr 3e-4) with
-// explicit FMAs: 11 VALU operations instead of the ~55 of two IEEE divisions and an IEEE sqrt.  Shared by adam_scatter_h64_kernel and the
+// explicit FMAs: 11 VALU operations instead of the ~55 of two IEEE divisions and an IEEE sqrt.  Shared by opt_scatter_h64_kernel and the
 // persistent epoch kernel (tma_h64p.hip), which therefore stay bit-identical.  inv_bc2_sqrt = 1 / sqrt(1 - beta2^t).
 __device__ __forceinline__ float adam_update_h64(float p, float gv, float &mm, float &vv, float beta1, float beta2, float inv_bc2_sqrt, float eps,
                                                  float lr_step) {
@@ -151,6 +151,80 @@ __device__ __forceinline__ float adam_update_h64(float p, float gv, float &mm, f
     const float denom = __builtin_fmaf(__builtin_amdgcn_sqrtf(vv), inv_bc2_sqrt, eps);
     return __builtin_fmaf(-lr_step, mm * __builtin_amdgcn_rcpf(denom), p);
 }
+
+// ---- Update rules of the optimizer kernels (tma_policy.hip: opt_scatter_h64_kernel, opt_scatter_wide_kernel, opt_small_kernel, opt_step_kernel).
+// A kernel owns the norm, the clip coefficient, the re-zeroing of the gradient and the scatter into the derived copies; the rule owns the state
+// buffers and the arithmetic of one element:  clip(tot, coef): what a thread keeps of the launch's clip (tot: the f64 sum of squares of the scaled
+// gradient, coef: clip_grad_norm_'s coefficient in the f32 arithmetic the Adam step has always used);  load(e): the state of element e;
+// step(e, p, gs, state, clip): stores the new state and returns the new parameter, gs = grad[e] * grad_scale.
+struct ClipCoef { float coef; };
+struct AdamState { float m, v; };
+// torch.optim.Adam as adam_update_h64 computes it: the scatter kernels.  (m_src, v_src): the moments before the step -- m, v themselves, or the
+// other half of the AdamFold double buffer
+struct AdamFastRule {
+    static constexpr bool kClip64 = false;
+    using State = AdamState;
+    using Clip = ClipCoef;
+    float *m, *v;
+    const float *m_src, *v_src;
+    float beta1, beta2, bc2_sqrt, eps, lr_step;
+    __device__ __forceinline__ Clip clip(double, float coef) const { return {coef}; }
+    __device__ __forceinline__ State load(int e) const { return {m_src[e], v_src[e]}; }
+    __device__ __forceinline__ float step(int e, float p, float gs, State s, Clip c) const {
+        const float gv = gs * c.coef;
+        float mm = s.m, vv = s.v;
+        const float pn = adam_update_h64(p, gv, mm, vv, beta1, beta2, 1.0f / bc2_sqrt, eps, lr_step);
+        m[e] = mm;
+        v[e] = vv;
+        return pn;
+    }
+};
+// torch.optim.Adam with the IEEE square root and divisions: the single-block and the multi-block kernel
+struct AdamRule {
+    static constexpr bool kClip64 = false;
+    using State = AdamState;
+    using Clip = ClipCoef;
+    float *m, *v;
+    float beta1, beta2, bc2_sqrt, eps, lr_step;
+    __device__ __forceinline__ Clip clip(double, float coef) const { return {coef}; }
+    __device__ __forceinline__ State load(int e) const { return {m[e], v[e]}; }
+    __device__ __forceinline__ float step(int e, float p, float gs, State s, Clip c) const {
+        const float gv = gs * c.coef;
+        float mm = s.m, vv = s.v;
+        mm = mm + (gv - mm) * (1.0f - beta1);         // exp_avg.lerp_(grad, 1 - beta1)
+        vv = vv * beta2 + (gv * gv) * (1.0f - beta2);  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+        m[e] = mm;
+        v[e] = vv;
+        const float denom = sqrtf(vv) / bc2_sqrt + eps;
+        return p - lr_step * (mm / denom);  // param.addcdiv_(exp_avg, denom, value=-step_size)
+    }
+};
+// SB3's RMSpropTFLike (A2C's optimizer; no weight decay, momentum or centering) behind clip_grad_norm_:
+//   square_avg = alpha * square_avg + (1 - alpha) * g^2;  p -= lr * g / sqrt(square_avg + eps)      with g = coef * gs, eps INSIDE the root.
+// Per element everything is f32 with the IEEE square root and division (square_avg + eps can be as small as 1e-5: no v_rsq / v_rcp here).  The
+// clip coefficient is one number per launch: every thread derives it in f64 from the f64 sum of squares and folds it into the two constants it
+// multiplies the gradient with, k = (1 - alpha) coef^2 and lc = lr coef, each rounded to f32 once -- so an element sees no more roundings with the
+// clip active than without (square_avg: g * g, k, their product, the sum -- 4 x 2^-24; the update: 6.5 x 2^-24, of it 2.5 from the root's argument).
+struct RmspropClip { float k, lc; };
+struct RmspropRule {
+    static constexpr bool kClip64 = true;
+    struct State { float sq; };
+    using Clip = RmspropClip;
+    float *sq;
+    float alpha, eps;
+    double one_minus_alpha, lr, max_norm;
+    __device__ __forceinline__ Clip clip(double tot, float) const {
+        double c = max_norm / (sqrt(tot) + 1e-6);  // torch.nn.utils.clip_grad_norm_
+        c = (c > 1.0 || max_norm <= 0.0) ? 1.0 : c;
+        return {(float)(one_minus_alpha * c * c), (float)(lr * c)};
+    }
+    __device__ __forceinline__ State load(int e) const { return {sq[e]}; }
+    __device__ __forceinline__ float step(int e, float p, float gs, State s, Clip c) const {
+        const float sqn = s.sq * alpha + (gs * gs) * c.k;
+        sq[e] = sqn;
+        return p - __fdiv_rn(c.lc * gs, __fsqrt_rn(sqn + eps));
+    }
+};
 
 // Fast-path layouts (H == 64, LDS images): the derived locations of trainable parameter e -- its [out][in] copy and its slots in
 // the forward / input-gradient images of its net (inverse of build_image_elem).

@@ -8,7 +8,7 @@
 //   OnPolicyAlgorithm.collect_rollouts timeout bootstrap (rewards += gamma * V(terminal_obs))  -> bootstrap_kernel
 //   RolloutBuffer.get (minibatch permutation + gather)                            -> perm_index + gather in ppo_grad_kernel
 //   PPO.train loss (clipped surrogate, value MSE, entropy bonus) + autograd       -> ppo_grad_kernel
-//   clip_grad_norm_(max_grad_norm) + torch.optim.Adam(eps=1e-5).step()            -> grad_sumsq_kernel + adam_kernel
+//   clip_grad_norm_(max_grad_norm) + torch.optim.Adam(eps=1e-5).step()            -> grad_sumsq_kernel + opt_step_kernel
 // Formulas: SURVEY.md Appendix C.3 / C.5.  "Parity unpinned" at this boundary (SB3 is not importable here); checked
 // against a torch-CPU autograd restatement in tests/.
 #include "tma_h64_tile.h"
@@ -1529,9 +1529,10 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float *__restrict
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ params, float *__restrict__ grad, float *__restrict__ m, float *__restrict__ v,
-                                                   int P, float scale, const double *__restrict__ partials, int n_partials, float max_norm, float lr_step,
-                                                   float beta1, float beta2, float bc2_sqrt, float eps, double *norm_out) {
+// (the optimizer kernels: the per-element update is the Rule -- tma_mlp.h: Adam, or RMSpropTFLike -- everything else exists once)
+template <class Rule>
+__global__ __launch_bounds__(256) void opt_step_kernel(float *__restrict__ params, float *__restrict__ grad, int P, float scale,
+                                                       const double *__restrict__ partials, int n_partials, float max_norm, double *norm_out, Rule rule) {
     double tot = 0.0;
     for (int b = 0; b < n_partials; b++) tot += partials[b];
     const float total_norm = (float)sqrt(tot);
@@ -1542,16 +1543,11 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ params, f
         norm_out[0] = (double)total_norm;
         norm_out[1] = (double)coef;
     }
+    const typename Rule::Clip clip = rule.clip(tot, coef);
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < P; e += gridDim.x * blockDim.x) {
-        const float gv = (grad[e] * scale) * coef;
+        const float gs = grad[e] * scale;
         grad[e] = 0.0f;  // ready for the next minibatch
-        float mm = m[e], vv = v[e];
-        mm = mm + (gv - mm) * (1.0f - beta1);         // exp_avg.lerp_(grad, 1 - beta1)
-        vv = vv * beta2 + (gv * gv) * (1.0f - beta2);  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-        m[e] = mm;
-        v[e] = vv;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        params[e] = params[e] - lr_step * (mm / denom);  // param.addcdiv_(exp_avg, denom, value=-step_size)
+        params[e] = rule.step(e, params[e], gs, rule.load(e), clip);
     }
 }
 
@@ -1586,12 +1582,12 @@ __global__ __launch_bounds__(64) void grad_pull_sumsq64_kernel(float *__restrict
 // sum-of-squares partials slab_reduce_kernel left (every block folds them in the same fixed order), and each thread writes its
 // updated parameter to the flat buffer AND to its derived copies / image slots -- no single-block optimizer, no refresh launch.
 // (p_src, m_src, v_src): the state before the step -- the same buffers, or the other half of the AdamFold double buffer.
-__global__ __launch_bounds__(256) void adam_scatter_h64_kernel(float *params, float *__restrict__ grad, float *m, float *v, PLayout L,
-                                                               const double *__restrict__ sq_part, int n_part, float max_norm, float lr_step,
-                                                               float beta1, float beta2, float bc2_sqrt, float eps, double *norm_out, float scale,
-                                                               const float *p_src, const float *m_src, const float *v_src) {
+template <class Rule>
+__global__ __launch_bounds__(256) void opt_scatter_h64_kernel(float *params, float *__restrict__ grad, PLayout L, const double *__restrict__ sq_part,
+                                                              int n_part, float max_norm, double *norm_out, float scale, const float *p_src, Rule rule) {
     __shared__ double red[4];
     __shared__ float coef_s;
+    __shared__ double tot_s;
     double a = (int)threadIdx.x < n_part ? sq_part[threadIdx.x] : 0.0;
     for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
@@ -1603,17 +1599,15 @@ __global__ __launch_bounds__(256) void adam_scatter_h64_kernel(float *params, fl
         coef = coef > 1.0f ? 1.0f : coef;
         if (max_norm <= 0.0f) coef = 1.0f;
         coef_s = coef;
+        if constexpr (Rule::kClip64) tot_s = tot;
         if (blockIdx.x == 0) norm_out[0] = (double)total_norm, norm_out[1] = (double)coef;
     }
     __syncthreads();
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= L.P) return;
-    const float gv = (grad[e] * scale) * coef_s;
+    const float gs = grad[e] * scale;
     grad[e] = 0.0f;
-    float mm = m_src[e], vv = v_src[e];
-    const float pn = adam_update_h64(p_src[e], gv, mm, vv, beta1, beta2, 1.0f / bc2_sqrt, eps, lr_step);
-    m[e] = mm;
-    v[e] = vv;
+    const float pn = rule.step(e, p_src[e], gs, rule.load(e), rule.clip(Rule::kClip64 ? tot_s : 0.0, coef_s));
     params[e] = pn;
     if (e < L.log_std) scatter_derived_h64(params, L, e, pn);
 }
@@ -1686,18 +1680,20 @@ __device__ __forceinline__ void scatter_derived_wide(float *params, const PLayou
     }
 }
 
-// tma_ppo_adam_step_local for the column-parallel layouts: as adam_scatter_h64_kernel, with up to WIDE_SQ_SLOTS norm partials
-__global__ __launch_bounds__(256) void adam_scatter_wide_kernel(float *__restrict__ params, float *__restrict__ grad, float *__restrict__ m,
-                                                                float *__restrict__ v, PLayout L, const double *__restrict__ sq_part, int n_part,
-                                                                float max_norm, float lr_step, float beta1, float beta2, float bc2_sqrt, float eps,
-                                                                double *norm_out, float scale) {
+// tma_ppo_adam_step_local for the column-parallel layouts: as opt_scatter_h64_kernel, with up to WIDE_SQ_SLOTS norm partials
+template <class Rule>
+__global__ __launch_bounds__(256) void opt_scatter_wide_kernel(float *__restrict__ params, float *__restrict__ grad, PLayout L,
+                                                               const double *__restrict__ sq_part, int n_part, float max_norm, double *norm_out, float scale,
+                                                               Rule rule) {
     __shared__ double red[4];
     __shared__ float coef_s;
+    __shared__ double tot_s;
     // this thread's element first (its four loads fly under the fold of the norm partials), then the partials sixteen loads at a time:
     // one memory round trip per batch instead of one per partial (a thread of the 137 k-parameter net folds 9 of them); same order of additions
     const int e = blockIdx.x * 256 + threadIdx.x;
     const bool live = e < L.P;
-    const float g_e = live ? grad[e] : 0.0f, m_e = live ? m[e] : 0.0f, v_e = live ? v[e] : 0.0f, p_e = live ? params[e] : 0.0f;
+    const float g_e = live ? grad[e] : 0.0f, p_e = live ? params[e] : 0.0f;
+    const typename Rule::State st = live ? rule.load(e) : typename Rule::State{};
     double a = 0.0;
     for (int b0 = threadIdx.x; b0 < n_part; b0 += 256 * 16) {
         double t[16];
@@ -1717,34 +1713,34 @@ __global__ __launch_bounds__(256) void adam_scatter_wide_kernel(float *__restric
         coef = coef > 1.0f ? 1.0f : coef;
         if (max_norm <= 0.0f) coef = 1.0f;
         coef_s = coef;
+        if constexpr (Rule::kClip64) tot_s = tot;
         if (blockIdx.x == 0) norm_out[0] = (double)total_norm, norm_out[1] = (double)coef;
     }
     __syncthreads();
     if (!live) return;
-    const float gv = (g_e * scale) * coef_s;
     grad[e] = 0.0f;
-    float mm = m_e, vv = v_e;
     // (round 6: adam_update_h64 -- hardware sqrt / rcp + explicit FMAs, the H = 64 kernels' routine -- here as well: the 256-wide persistent epoch
     //  kernel, tma_h256p.hip, runs it on every workgroup each step, and the two paths share one arithmetic)
-    const float pn = adam_update_h64(p_e, gv, mm, vv, beta1, beta2, 1.0f / bc2_sqrt, eps, lr_step);
-    m[e] = mm;
-    v[e] = vv;
+    //  -- AdamFastRule)
+    const float pn = rule.step(e, p_e, g_e * scale, st, rule.clip(Rule::kClip64 ? tot_s : 0.0, coef_s));
     params[e] = pn;
     if (e < L.log_std) scatter_derived_wide(params, L, e, pn);
 }
 
 // small policies (P <= 32768): clip_grad_norm_ + Adam in ONE single-block launch (the norm needs no second kernel)
-__global__ __launch_bounds__(1024) void opt_small_kernel(float *__restrict__ params, float *__restrict__ grad, float *__restrict__ m, float *__restrict__ v,
-                                                         PLayout L, float scale, float max_norm, float lr_step, float beta1, float beta2, float bc2_sqrt,
-                                                         float eps, double *norm_out) {
+template <class Rule>
+__global__ __launch_bounds__(1024) void opt_small_kernel(float *__restrict__ params, float *__restrict__ grad, PLayout L, float scale, float max_norm,
+                                                         double *norm_out, Rule rule) {
     __shared__ double red[16];
     __shared__ float coef_s;
+    __shared__ double tot_s;
     const int P = L.P;
     // P <= 10240 (the 64x64 nets: 9350): every thread keeps its <= 10 elements of grad / m / v / params in registers, so all four
     // streams are in flight together and the second pass needs no global load (one memory round trip instead of two).
     constexpr int NE = 10;
     const bool small = P <= NE * 1024;
-    float rg[NE], rm[NE], rv[NE], rp[NE];
+    float rg[NE], rp[NE];
+    typename Rule::State rs[NE];
     double sq = 0.0;
     if (small) {
 #pragma unroll
@@ -1752,8 +1748,7 @@ __global__ __launch_bounds__(1024) void opt_small_kernel(float *__restrict__ par
             const int e = threadIdx.x + 1024 * i;
             const bool ok = e < P;
             rg[i] = ok ? grad[e] * scale : 0.0f;
-            rm[i] = ok ? m[e] : 0.0f;
-            rv[i] = ok ? v[e] : 0.0f;
+            rs[i] = ok ? rule.load(e) : typename Rule::State{};
             rp[i] = ok ? params[e] : 0.0f;
         }
 #pragma unroll
@@ -1775,39 +1770,27 @@ __global__ __launch_bounds__(1024) void opt_small_kernel(float *__restrict__ par
         coef = coef > 1.0f ? 1.0f : coef;
         if (max_norm <= 0.0f) coef = 1.0f;
         coef_s = coef;
+        if constexpr (Rule::kClip64) tot_s = tot;
         norm_out[0] = (double)total_norm;
         norm_out[1] = (double)coef;
     }
     __syncthreads();
-    const float coef = coef_s;
+    const typename Rule::Clip clip = rule.clip(Rule::kClip64 ? tot_s : 0.0, coef_s);
     if (small) {
 #pragma unroll
         for (int i = 0; i < NE; i++) {
             const int e = threadIdx.x + 1024 * i;
             if (e < P) {
-                const float gv = rg[i] * coef;
                 grad[e] = 0.0f;
-                float mm = rm[i], vv = rv[i];
-                mm = mm + (gv - mm) * (1.0f - beta1);
-                vv = vv * beta2 + (gv * gv) * (1.0f - beta2);
-                m[e] = mm;
-                v[e] = vv;
-                const float denom = sqrtf(vv) / bc2_sqrt + eps;
-                params[e] = rp[i] - lr_step * (mm / denom);
+                params[e] = rule.step(e, rp[i], rg[i], rs[i], clip);
             }
         }
         return;
     }
     for (int e = threadIdx.x; e < P; e += 1024) {
-        const float gv = (grad[e] * scale) * coef;
+        const float gs = grad[e] * scale;
         grad[e] = 0.0f;
-        float mm = m[e], vv = v[e];
-        mm = mm + (gv - mm) * (1.0f - beta1);
-        vv = vv * beta2 + (gv * gv) * (1.0f - beta2);
-        m[e] = mm;
-        v[e] = vv;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        params[e] = params[e] - lr_step * (mm / denom);
+        params[e] = rule.step(e, params[e], gs, rule.load(e), clip);
     }
 }
 
@@ -2562,7 +2545,8 @@ int tma_policy_bootstrap(const float *params, const tma_policy_dims *d, const fl
 // fold (H = 64 fast path only): the previous minibatch's optimizer step, done in the prologue of this gradient launch (AdamFold)
 static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_minibatch *mbi, const tma_ppo_hparams *hp,
                                float *grad, void *workspace, void *stream, const AdamFold *fold, int overwrite, const PeerPush *push = nullptr,
-                               const PrepNext *next = nullptr /* the next minibatch's pre-pass, carried by this launch (eight-wave H = 64 kernel only) */) {
+                               const PrepNext *next = nullptr /* the next minibatch's pre-pass, carried by this launch (eight-wave H = 64 kernel only) */,
+                               int64_t ordered_tiles = 0 /* generic kernel, minibatches of up to this many 16-row tiles: one wave per net (see A2C_ORDERED_TILES) */) {
     g_disp_grad = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
@@ -2588,8 +2572,10 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
         return fail(TMA_ERR_INVALID, "minibatch [%lld, +%lld) does not match the prepared epoch split (batch %lld)", (long long)mbi->start,
                     (long long)mbi->count, (long long)mbi->prepared_batch);
     const DispatchSwitches sw = read_switches(L, mbi->count, true);
-    const GradPlan p = plan_grad(L, d->continuous != 0, mbi->count, prepared, hp->normalize_advantage != 0, sw);
+    GradPlan p = plan_grad(L, d->continuous != 0, mbi->count, prepared, hp->normalize_advantage != 0, sw);
     g_disp_grad = p.id;
+    if (p.family == GradFamily::Generic && ceil_div(mbi->count, 16) <= ordered_tiles)  // the same kernel on ONE workgroup of one wave per net: its tiles in turn
+        p.grid = 2, p.block = 64, p.lds = grad_smem_bytes(L, 1);
     HParams hpar{(float)hp->clip_range, (float)hp->ent_coef, (float)hp->vf_coef, p.normalize ? 1 : 0, sw.bf_debug};
     char *ws = static_cast<char *>(workspace);
     float *ws_adv = reinterpret_cast<float *>(ws + WS_ADV);
@@ -2856,9 +2842,9 @@ static int h64_fold_epochs(float *params, const tma_policy_dims *d, const tma_ro
             if (k > 0) cur ^= 1;
         }
         const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
-        adam_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
-            params, grad, exp_avg, exp_avg_sq, L, sqp, (int)ceil_div(L.P, 64), (float)max_grad_norm, (float)(lr / bc1), (float)beta1, (float)beta2,
-            (float)sqrt(bc2), (float)eps, reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f, bufs[cur][0], bufs[cur][1], bufs[cur][2]);
+        opt_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
+            params, grad, L, sqp, (int)ceil_div(L.P, 64), (float)max_grad_norm, reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f, bufs[cur][0],
+            AdamFastRule{exp_avg, exp_avg_sq, bufs[cur][1], bufs[cur][2], (float)beta1, (float)beta2, (float)sqrt(bc2), (float)eps, (float)(lr / bc1)});
         TMA_LAUNCH_CHECK();
         cur = 0;  // (the optimizer launch left the state in the caller's buffers)
     }
@@ -2977,7 +2963,7 @@ int tma_ppo_train_epoch_dp(float *params, const tma_policy_dims *d, const tma_ro
     // Round 5, H = 64 fast path: the dependent chain of a data-parallel minibatch was gradient -> slab_reduce -> all-reduce -> grad_sumsq64 -> Adam.
     // What the collective forces is only that the NORM PARTIALS come from the all-reduced gradient; the step itself can still run where the
     // single-GPU epoch runs it -- in the prologue of the next gradient launch (AdamFold, with the 1/world scale of the summed gradient in the
-    // same place adam_scatter_h64_kernel applies it).  Chain: gradient(+ step k - 1) -> slab_reduce (overwrite) -> all-reduce -> grad_sumsq64:
+    // same place opt_scatter_h64_kernel applies it).  Chain: gradient(+ step k - 1) -> slab_reduce (overwrite) -> all-reduce -> grad_sumsq64:
     // one dependent launch fewer per minibatch, the epoch's last step by the ordinary optimizer launch.  Same routine on the same inputs
     // as the unfolded sequence: bit-identical (tests/test_dist_gpu.py, test_native_data_parallel_epoch_equals_the_single_gpu_epoch).
     // (Taking the partials inside the optimizer kernel instead -- every block re-summing the 37 KB gradient in shuffle-tree order, no
@@ -3031,9 +3017,9 @@ int tma_ppo_train_epoch_dp(float *params, const tma_policy_dims *d, const tma_ro
             TMA_LAUNCH_CHECK();
         }
         const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
-        adam_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
-            params, grad, exp_avg, exp_avg_sq, L, sqp, n_part, (float)max_grad_norm, (float)(lr / bc1), (float)beta1, (float)beta2,
-            (float)sqrt(bc2), (float)eps, reinterpret_cast<double *>(ws + WS_NORM_OUT), (float)grad_scale, bufs[cur][0], bufs[cur][1], bufs[cur][2]);
+        opt_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
+            params, grad, L, sqp, n_part, (float)max_grad_norm, reinterpret_cast<double *>(ws + WS_NORM_OUT), (float)grad_scale, bufs[cur][0],
+            AdamFastRule{exp_avg, exp_avg_sq, bufs[cur][1], bufs[cur][2], (float)beta1, (float)beta2, (float)sqrt(bc2), (float)eps, (float)(lr / bc1)});
         TMA_LAUNCH_CHECK();
         return TMA_OK;
     }
@@ -3139,15 +3125,16 @@ int tma_ppo_epoch_adv_sums(void *workspace, const tma_policy_dims *d, int64_t ba
     return TMA_OK;
 }
 
-// The optimizer step of a plan.  Scatter kernels: ONE multi-block Adam launch that also scatters the derived copies of the layouts that have them,
-// behind the norm partials of the (all-reduced, scaled) gradient -- which a _local call that does not fall through finds where the gradient's
-// reduction left them
-static int launch_opt(const OptPlan &p, bool local, float *params, float *grad, float *exp_avg, float *exp_avg_sq, const PLayout &L, int64_t step, double lr,
-                      double beta1, double beta2, double eps, double max_grad_norm, double grad_scale, char *ws, hipStream_t s) {
+}  // extern "C"
+
+// The optimizer step of a plan.  Scatter kernels: ONE multi-block launch that steps the parameters and also scatters the derived copies of the layouts
+// that have them, behind the norm partials of the (all-reduced, scaled) gradient -- which a _local call that does not fall through finds where the
+// gradient's reduction left them.  scatter_rule / flat_rule: the update rule (tma_mlp.h) of the scatter kernels and of the other two.
+template <class ScatterRule, class FlatRule>
+static int launch_opt(const OptPlan &p, bool local, float *params, float *grad, const PLayout &L, const ScatterRule &scatter_rule, const FlatRule &flat_rule,
+                      double max_grad_norm, double grad_scale, char *ws, hipStream_t s) {
     double *partials = reinterpret_cast<double *>(ws + WS_NORM_PART);
     double *norm_out = reinterpret_cast<double *>(ws + WS_NORM_OUT);
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
     if (p.kernels == OptKernels::ScatterH64 || p.kernels == OptKernels::ScatterWide) {
         double *sqp = sq_partials(ws, L);
         const int n_part = (int)ceil_div(L.P, 64);
@@ -3156,29 +3143,36 @@ static int launch_opt(const OptPlan &p, bool local, float *params, float *grad, 
             TMA_LAUNCH_CHECK();
         }
         if (p.kernels == OptKernels::ScatterH64)
-            adam_scatter_h64_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, sqp, n_part, (float)max_grad_norm,
-                                                                                     (float)step_size, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out,
-                                                                                     (float)grad_scale, params, exp_avg, exp_avg_sq);
+            opt_scatter_h64_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, L, sqp, n_part, (float)max_grad_norm, norm_out, (float)grad_scale,
+                                                                                    params, scatter_rule);
         else
-            adam_scatter_wide_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, sqp, n_part, (float)max_grad_norm,
-                                                                                      (float)step_size, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out,
-                                                                                      (float)grad_scale);
+            opt_scatter_wide_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, L, sqp, n_part, (float)max_grad_norm, norm_out, (float)grad_scale,
+                                                                                     scatter_rule);
         TMA_LAUNCH_CHECK();
         return TMA_OK;
     }
     if (p.kernels == OptKernels::Small) {
-        opt_small_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L, (float)grad_scale, (float)max_grad_norm,
-                                                                          (float)step_size, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out);
+        opt_small_kernel<<<dim3((unsigned)p.grid), dim3(p.block), 0, s>>>(params, grad, L, (float)grad_scale, (float)max_grad_norm, norm_out, flat_rule);
         TMA_LAUNCH_CHECK();
         return launch_sync(params, L, s);
     }
     const int nb = (int)p.grid;
     grad_sumsq_kernel<<<dim3(nb), dim3(p.block), 0, s>>>(grad, L.P, (float)grad_scale, partials);
     TMA_LAUNCH_CHECK();
-    adam_kernel<<<dim3(nb), dim3(p.block), 0, s>>>(params, grad, exp_avg, exp_avg_sq, L.P, (float)grad_scale, partials, nb, (float)max_grad_norm, (float)step_size,
-                                                   (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, norm_out);
+    opt_step_kernel<<<dim3(nb), dim3(p.block), 0, s>>>(params, grad, L.P, (float)grad_scale, partials, nb, (float)max_grad_norm, norm_out, flat_rule);
     TMA_LAUNCH_CHECK();
     return launch_sync(params, L, s);
+}
+
+extern "C" {
+
+static int launch_opt_adam(const OptPlan &p, bool local, float *params, float *grad, float *exp_avg, float *exp_avg_sq, const PLayout &L, int64_t step, double lr,
+                           double beta1, double beta2, double eps, double max_grad_norm, double grad_scale, char *ws, hipStream_t s) {
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
+    const AdamFastRule fast{exp_avg, exp_avg_sq, exp_avg, exp_avg_sq, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, (float)step_size};
+    const AdamRule ieee{exp_avg, exp_avg_sq, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, (float)step_size};
+    return launch_opt(p, local, params, grad, L, fast, ieee, max_grad_norm, grad_scale, ws, s);
 }
 
 int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg_sq, const tma_policy_dims *d, int64_t step, double lr, double beta1,
@@ -3191,8 +3185,8 @@ int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg
     const PLayout L = layout_of(d);
     const OptPlan p = plan_opt(L, false, 0, DispatchSwitches{});  // (the global step reads no switch)
     g_disp_opt = p.id;
-    return launch_opt(p, false, params, grad, exp_avg, exp_avg_sq, L, step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, static_cast<char *>(workspace),
-                      (hipStream_t)stream);
+    return launch_opt_adam(p, false, params, grad, exp_avg, exp_avg_sq, L, step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, static_cast<char *>(workspace),
+                           (hipStream_t)stream);
 }
 
 int tma_ppo_adam_step_local(float *params, float *grad, float *exp_avg, float *exp_avg_sq, const tma_policy_dims *d, int64_t step, double lr,
@@ -3205,8 +3199,158 @@ int tma_ppo_adam_step_local(float *params, float *grad, float *exp_avg, float *e
     const PLayout L = layout_of(d);
     const OptPlan p = plan_opt(L, true, last_count, read_switches(L, last_count, false));
     g_disp_opt = p.id;
-    return launch_opt(p, true, params, grad, exp_avg, exp_avg_sq, L, step, lr, beta1, beta2, eps, max_grad_norm, 1.0, static_cast<char *>(workspace),
-                      (hipStream_t)stream);
+    return launch_opt_adam(p, true, params, grad, exp_avg, exp_avg_sq, L, step, lr, beta1, beta2, eps, max_grad_norm, 1.0, static_cast<char *>(workspace),
+                           (hipStream_t)stream);
+}
+
+// ---- A2C (SB3 2.9 A2C.train: one gradient over the whole rollout, clip_grad_norm_, RMSpropTFLike) ----
+static int check_rmsprop(const char *who, double lr, double alpha, double eps) {
+    if (!(lr >= 0.0) || !(alpha >= 0.0 && alpha < 1.0) || !(eps >= 0.0) || std::isinf(lr) || std::isinf(eps))
+        return fail(TMA_ERR_INVALID, "%s: lr and eps must be finite and >= 0, alpha in [0, 1) (got lr %g, alpha %g, eps %g)", who, lr, alpha, eps);
+    return TMA_OK;
+}
+
+static int launch_opt_rmsprop(const OptPlan &p, bool local, float *params, float *grad, float *square_avg, const PLayout &L, double lr, double alpha, double eps,
+                              double max_grad_norm, double grad_scale, char *ws, hipStream_t s) {
+    const RmspropRule rule{square_avg, (float)alpha, (float)eps, 1.0 - alpha, lr, max_grad_norm};
+    return launch_opt(p, local, params, grad, L, rule, rule, max_grad_norm, grad_scale, ws, s);
+}
+constexpr int32_t OPT_RMSPROP_ID = TMA_DISPATCH_OPT_RMSPROP_SCATTER_H64 - TMA_DISPATCH_OPT_SCATTER_H64;  // the RMSprop ids follow the Adam ids in their order
+
+int tma_rmsprop_step(float *params, float *grad, float *square_avg, const tma_policy_dims *d, double lr, double alpha, double eps, double max_grad_norm,
+                     double grad_scale, void *workspace, void *stream) {
+    g_disp_opt = TMA_DISPATCH_NONE;
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (!params || !grad || !square_avg || !workspace) return fail(TMA_ERR_INVALID, "tma_rmsprop_step: null buffer");
+    if ((rc = check_rmsprop("tma_rmsprop_step", lr, alpha, eps)) || (rc = enter(d))) return rc;
+    const PLayout L = layout_of(d);
+    const OptPlan p = plan_opt(L, false, 0, DispatchSwitches{});
+    g_disp_opt = p.id + OPT_RMSPROP_ID;
+    return launch_opt_rmsprop(p, false, params, grad, square_avg, L, lr, alpha, eps, max_grad_norm, grad_scale, static_cast<char *>(workspace), (hipStream_t)stream);
+}
+
+int tma_rmsprop_step_local(float *params, float *grad, float *square_avg, const tma_policy_dims *d, double lr, double alpha, double eps, double max_grad_norm,
+                           void *workspace, void *stream, int64_t last_count) {
+    g_disp_opt = TMA_DISPATCH_NONE;
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (!params || !grad || !square_avg || !workspace) return fail(TMA_ERR_INVALID, "tma_rmsprop_step_local: null buffer");
+    if ((rc = check_rmsprop("tma_rmsprop_step_local", lr, alpha, eps)) || (rc = enter(d))) return rc;
+    const PLayout L = layout_of(d);
+    const OptPlan p = plan_opt(L, true, last_count, read_switches(L, last_count, false));
+    g_disp_opt = p.id + OPT_RMSPROP_ID;
+    return launch_opt_rmsprop(p, true, params, grad, square_avg, L, lr, alpha, eps, max_grad_norm, 1.0, static_cast<char *>(workspace), (hipStream_t)stream);
+}
+
+// SB3's A2C `train/policy_loss`, -(advantages * log_prob).mean(), as a SUM over the rollout into statistic slot [0][A2C_POLICY_LOSS_SLOT] (the gradient
+// kernels' own policy-loss statistic is the surrogate's, -(advantages * ratio): a constant at ratio = 1).  One workgroup, f64, fixed order.  With
+// normalize_advantage: sum (adv - mean) / (std + 1e-8) * logp = (sum adv logp - mean sum logp) / (std + 1e-8), the unbiased std as torch.std.
+constexpr int A2C_POLICY_LOSS_SLOT = 6;  // columns 6 and 7 of a statistic row are no gradient kernel's
+__global__ __launch_bounds__(256) void a2c_policy_loss_kernel(const float *__restrict__ adv, const float *__restrict__ logp, int64_t n, int normalize, double *slot) {
+    __shared__ double red[4][4];
+    double sa = 0.0, saa = 0.0, sl = 0.0, sal = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        const double a = (double)adv[i], l = (double)logp[i];
+        sa += a, saa += a * a, sl += l, sal += a * l;
+    }
+    for (int o = 32; o > 0; o >>= 1) sa += __shfl_down(sa, o, 64), saa += __shfl_down(saa, o, 64), sl += __shfl_down(sl, o, 64), sal += __shfl_down(sal, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = sa, red[threadIdx.x >> 6][1] = saa, red[threadIdx.x >> 6][2] = sl, red[threadIdx.x >> 6][3] = sal;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t[4];
+    for (int q = 0; q < 4; q++) t[q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+    double loss = -t[3];
+    if (normalize && n > 1) {
+        const double mean = t[0] / (double)n, var = (t[1] - (double)n * mean * mean) / (double)(n - 1);
+        loss = -(t[3] - mean * t[2]) / (sqrt(var > 0.0 ? var : 0.0) + 1e-8);
+    }
+    slot[A2C_POLICY_LOSS_SLOT] += loss;
+}
+
+// "a clip range that never clips": the surrogate of the PPO gradient kernels is then -adv * ratio, whose gradient at ratio = 1 is A2C's
+constexpr float A2C_NO_CLIP = 1e30f;
+// A2C's batches are small (40 samples at the reference's 8 envs x 5 steps) and most land on the generic gradient kernel, whose workgroups add
+// their tiles into the gradient with float atomics in whatever order they finish -- 200 launches on one 40-sample input gave 72 distinct
+// gradients.  Up to this many tiles (256 samples) A2C launches that kernel as one wave per net, which walks the tiles in turn: every gradient
+// element then receives its additions from one wave in program order and the update is bit-identical from run to run.  Larger batches on the
+// shapes without a slab-reducing kernel keep the parallel launch (and its run-to-run last-bit differences), as PPO's.
+constexpr int64_t A2C_ORDERED_TILES = 16;
+
+int tma_a2c_grad(const float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_a2c_hparams *hp, float *grad, void *workspace, void *stream) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (!params || !rb || !hp || !grad || !workspace) return fail(TMA_ERR_INVALID, "tma_a2c_grad: null argument");
+    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->advantages || !rb->returns) return fail(TMA_ERR_INVALID, "tma_a2c_grad: rollout view has a null buffer");
+    if (rb->T < 1 || rb->N < 1) return fail(TMA_ERR_INVALID, "tma_a2c_grad: T and N must be >= 1");
+    const int64_t total = (int64_t)rb->T * rb->N;
+    const tma_ppo_hparams php{(double)A2C_NO_CLIP, hp->ent_coef, hp->vf_coef, hp->normalize_advantage};
+    const tma_minibatch mb{nullptr, 0, 0, 0, total, 0, 0};  // every sample once: the order of the on-device permutation (a sum: SB3's order is the buffer's)
+    rc = minibatch_grad_impl(params, d, rb, &mb, &php, grad, workspace, stream, nullptr, 0, nullptr, nullptr, A2C_ORDERED_TILES);
+    if (rc) return rc;
+    a2c_policy_loss_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(rb->advantages, rb->log_probs, total, hp->normalize_advantage,
+                                                                           reinterpret_cast<double *>(static_cast<char *>(workspace) + WS_STATS));
+    TMA_LAUNCH_CHECK();
+    return TMA_OK;
+}
+
+int tma_a2c_update_local(float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_a2c_hparams *hp, float *grad, float *square_avg, double lr,
+                         double alpha, double eps, double max_grad_norm, void *workspace, void *stream) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (!params || !rb || !hp || !grad || !square_avg || !workspace) return fail(TMA_ERR_INVALID, "tma_a2c_update_local: null argument");
+    if ((rc = check_rmsprop("tma_a2c_update_local", lr, alpha, eps)) || (rc = tma_a2c_grad(params, d, rb, hp, grad, workspace, stream))) return rc;
+    return tma_rmsprop_step_local(params, grad, square_avg, d, lr, alpha, eps, max_grad_norm, workspace, stream, (int64_t)rb->T * rb->N);
+}
+
+int tma_a2c_iterations_local(tma_env *env, float *params, const tma_policy_dims *d, const tma_rollout_buffers *buffers, float *advantages, float *returns,
+                             float *packed, int T, uint32_t rng_seed, uint32_t rollout_counter0, uint32_t env_offset, double gamma, double gae_lambda,
+                             int carry_first, int n_iterations, const tma_a2c_hparams *hp, float *grad, float *square_avg, double lr, double alpha, double eps,
+                             double max_grad_norm, void *workspace, void *stream) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (!env || !params || !buffers || !advantages || !returns || !hp || !grad || !square_avg || !workspace)
+        return fail(TMA_ERR_INVALID, "tma_a2c_iterations_local: null argument");
+    if (!buffers->obs || !buffers->actions || !buffers->rewards || !buffers->values || !buffers->log_probs || !buffers->terminated || !buffers->truncated ||
+        !buffers->terminal_obs || !buffers->last_values)
+        return fail(TMA_ERR_INVALID, "tma_a2c_iterations_local: rollout buffers has a null plane");
+    if (T < 1 || buffers->N < 1 || n_iterations < 1) return fail(TMA_ERR_INVALID, "tma_a2c_iterations_local: T, N and n_iterations must be >= 1");
+    if ((rc = check_rmsprop("tma_a2c_iterations_local", lr, alpha, eps)) || (rc = enter(d))) return rc;
+    const int64_t N = buffers->N;
+    const size_t slot_bytes = (size_t)N * d->obs_dim * sizeof(float);
+    const bool records = packed && tma_ppo_packed_floats(d, T, N) > 0;
+    const tma_rollout view{buffers->obs, buffers->actions, buffers->log_probs, advantages, returns, T, N, records ? packed : nullptr};
+    hipStream_t s = (hipStream_t)stream;
+    for (int it = 0; it < n_iterations; it++) {
+        if (it > 0 || carry_first)  // the final new_obs of the rollout before is the observation step 0 acts on
+            TMA_HIP(hipMemcpyAsync(buffers->obs, buffers->obs + (size_t)T * N * d->obs_dim, slot_bytes, hipMemcpyDeviceToDevice, s));
+        if ((rc = tma_rollout_collect(env, params, d, buffers, 0, T, T, rng_seed, (rollout_counter0 + (uint32_t)it) * (uint32_t)T, env_offset, gamma, 1, 0, stream)))
+            return rc;
+        if ((rc = tma_gae_flags(buffers->rewards, buffers->values, buffers->terminated, buffers->truncated, buffers->last_values, gamma, gae_lambda, T, N, advantages,
+                                returns, stream)))
+            return rc;
+        if (records && (rc = tma_ppo_pack_samples(&view, d, packed, stream))) return rc;
+        if (it == n_iterations - 1)  // the statistics a caller reads after the call are those of the call's LAST update, as SB3 logs them
+            TMA_HIP(hipMemsetAsync(static_cast<char *>(workspace) + WS_STATS, 0, sizeof(double) * MAX_GRAD_BLOCKS * 8, s));
+        if ((rc = tma_a2c_update_local(params, d, &view, hp, grad, square_avg, lr, alpha, eps, max_grad_norm, workspace, stream))) return rc;
+    }
+    return TMA_OK;
+}
+
+int tma_ppo_stats_clear(void *workspace, void *stream) {
+    if (!workspace) return fail(TMA_ERR_INVALID, "tma_ppo_stats_clear: null argument");
+    TMA_HIP(hipMemsetAsync(static_cast<char *>(workspace) + WS_STATS, 0, sizeof(double) * MAX_GRAD_BLOCKS * 8, (hipStream_t)stream));
+    return TMA_OK;
+}
+
+int tma_a2c_stats_fold(const void *staging_host, double *out8_host) {
+    const int rc = tma_ppo_stats_fold(staging_host, out8_host);
+    if (rc) return rc;
+    const double *tmp = static_cast<const double *>(staging_host);
+    out8_host[0] = 0.0;
+    for (int b = 0; b < MAX_GRAD_BLOCKS; b++) out8_host[0] += tmp[b * 8 + A2C_POLICY_LOSS_SLOT];
+    out8_host[3] = out8_host[4] = 0.0;  // approx_kl, clip_fraction: not A2C's
+    return TMA_OK;
 }
 
 int tma_ppo_permutation(uint32_t perm_seed, uint32_t perm_epoch, int64_t total, int64_t *indices_out_host) {

@@ -24,11 +24,12 @@ import numpy as np
 from . import tasks
 from .callbacks import CallbackList, EvalCallback
 from .evaluation import evaluate_policy
+from .a2c import A2C
 from .ppo import PPO
 from .vec_env import HipVecEnv
 
 POLICIES_DIR, RUNS_DIR = (Path(name) for name in ("policies", "runs"))
-ALGORITHMS = dict(ppo=PPO)  # the one algorithm north_star puts on the GPU
+ALGORITHMS = dict(ppo=PPO, a2c=A2C)  # the algorithms with an MI355X implementation (the reference's table: training.py:31-37)
 EVAL_ENVS = int(os.environ.get("TMA_EVAL_ENVS", "128"))  # width of the evaluation vector (train_task / evaluate_model): up to one env per episode
 _SB3_NAMES = {"a2c", "dqn", "ppo", "sac", "td3"}  # what the reference's table accepts (training.py:31-37)
 
@@ -67,6 +68,44 @@ def ppo_defaults(task: tasks.EngineTask, n_envs: int | None = None) -> dict[str,
         batch = 256 * max(1, int(n_envs) // 8)
     return dict(learning_rate=3e-4, n_steps=task.ppo_n_steps, batch_size=batch, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                 ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5, policy_kwargs={"net_arch": {"pi": width, "vf": list(width)}, **extra})
+
+
+def model_defaults(algo: str, task: tasks.EngineTask, n_envs: int | None = None) -> dict[str, Any]:
+    """Hyper-parameters per algorithm, next to tensorboard_log and verbose: PPO's value table; nothing for A2C, which the reference constructs with
+    SB3's defaults (its _default_model_kwargs returns only those two)."""
+    return ppo_defaults(task, n_envs) if algo == "ppo" else {}
+
+
+def _schedule(algo: str, model, n_envs: int, model_kwargs) -> dict[str, Any]:
+    """metadata.json `schedule`: how a rollout is cut into optimizer steps."""
+    if algo != "ppo":  # A2C: one optimizer step over the whole rollout
+        return dict(n_steps=model.n_steps, n_envs=n_envs, samples_per_update=n_envs * model.n_steps, updates_per_rollout=1)
+    return dict(batch_size=model.batch_size, n_steps=model.n_steps, n_epochs=model.n_epochs, n_envs=n_envs,
+                minibatches_per_epoch=-(-n_envs * model.n_steps // model.batch_size), reference_batch_size=256,
+                literal_batch_env=bool(os.environ.get("TMA_LITERAL_BATCH")), batch_size_from="model_kwargs" if "batch_size" in (model_kwargs or {})
+                else ("TMA_LITERAL_BATCH" if os.environ.get("TMA_LITERAL_BATCH") else "256 * max(1, n_envs // 8)"))
+
+
+def _algorithm_from_metadata(path: Path) -> str:
+    """The algorithm that wrote a policy zip, from the metadata.json of its run (runs/<task>/<run_id>/, run_id = the zip's name behind the task's
+    prefix); without one, from the zip's own `data`; "ppo" where neither says (zips from before the key)."""
+    for meta in RUNS_DIR.glob("*/*/metadata.json"):
+        try:
+            with open(meta, encoding="utf-8") as fh:
+                record = json.load(fh)
+        except (OSError, ValueError):
+            continue
+        if record.get("model_filename") == Path(path).name:
+            algo = str(record.get("algorithm", "ppo")).lower()
+            return algo if algo in ALGORITHMS else "ppo"
+    try:  # no run record (a zip handed over by path): the engine's own zips name their algorithm
+        import zipfile
+
+        with zipfile.ZipFile(path) as z:
+            algo = str((json.loads(z.read("data").decode()).get("tma") or {}).get("algorithm", "ppo")).lower()
+        return algo if algo in ALGORITHMS else "ppo"
+    except (OSError, ValueError, KeyError, zipfile.BadZipFile):
+        return "ppo"
 
 
 def _algorithm_for(requested: str | None, task: tasks.EngineTask | None = None) -> tuple[str, str | None]:
@@ -117,7 +156,7 @@ def train_task(config, *, callback=None, model_kwargs=None):
         # the eval vector is seeded 10 000 past the training seed (the reference: ONE env, episodes one after the other on the host; here the
         # episodes are spread over up to EVAL_ENVS device envs stepped together -- evaluation.py, SB3's even split of episodes over envs)
         venv, eval_env = opened(n_envs, 0, run.monitor), opened(max(1, min(EVAL_ENVS, episodes)), 10_000)
-        hp = {**ppo_defaults(task, n_envs), "tensorboard_log": str(run.tb), "verbose": config.verbose, **(model_kwargs or {})}
+        hp = {**model_defaults(algo, task, n_envs), "tensorboard_log": str(run.tb), "verbose": config.verbose, **(model_kwargs or {})}
         model = ALGORITHMS[algo](config.policy or "MlpPolicy", venv, seed=config.seed, **hp)
         ev = dict(n_eval_episodes=episodes, deterministic=config.deterministic_eval)
         hooks = [EvalCallback(eval_env, log_path=str(run.eval), best_model_save_path=str(run.best), verbose=config.verbose,
@@ -130,10 +169,7 @@ def train_task(config, *, callback=None, model_kwargs=None):
         mean, std = statistics.fmean(returns), statistics.pstdev(returns)
         from . import __version__
 
-        schedule = dict(batch_size=model.batch_size, n_steps=model.n_steps, n_epochs=model.n_epochs, n_envs=n_envs,
-                        minibatches_per_epoch=-(-n_envs * model.n_steps // model.batch_size), reference_batch_size=256,
-                        literal_batch_env=bool(os.environ.get("TMA_LITERAL_BATCH")), batch_size_from="model_kwargs" if "batch_size" in (model_kwargs or {})
-                        else ("TMA_LITERAL_BATCH" if os.environ.get("TMA_LITERAL_BATCH") else "256 * max(1, n_envs // 8)"))
+        schedule = _schedule(algo, model, n_envs, model_kwargs)
         record = dict(task=task.card(), config=dataclasses.asdict(config), algorithm=algo, substituted_for=stands_in_for, schedule=schedule, run_id=run.id, model_filename=run.zip_name,
                       model_path=str(run.zip_path), mean_reward=mean, std_reward=std, episode_rewards=[float(r) for r in returns],
                       episode_lengths=[int(n) for n in lengths], train_log=model.logger_values,
@@ -159,14 +195,15 @@ def find_policy(task: tasks.EngineTask, name_or_path=None) -> Path:
 
 def load_model(task, name_or_path=None):
     task = tasks.resolve(task) if isinstance(task, str) else task
-    return PPO.load(find_policy(task, name_or_path))
+    path = find_policy(task, name_or_path)
+    return ALGORITHMS[_algorithm_from_metadata(path)].load(path)
 
 
 def evaluate_model(task_id, name_or_path, *, episodes=None, deterministic=True, seed=10_001):
     """-> dict(task_id, model, episodes, mean_reward, std_reward, episode_rewards, episode_lengths)"""
     task = tasks.resolve(task_id)
     path = find_policy(task, name_or_path)
-    model = PPO.load(path)
+    model = ALGORITHMS[_algorithm_from_metadata(path)].load(path)
     n = int(episodes or task.eval_episodes)
     with contextlib.closing(make_vector_env(task.id, n_envs=max(1, min(EVAL_ENVS, n)), seed=seed)) as env:
         returns, lengths = evaluate_policy(model, env, n_eval_episodes=n, deterministic=deterministic, return_episode_rewards=True)

@@ -264,7 +264,8 @@ class PPO:
         # policy_kwargs["mfma_dtype"] = "bf16" (engine extension; BASELINE.json configs[2]): bf16 MFMA operands for 128..256-wide nets
         self.policy = HipActorCriticPolicy(eng.obs_dim, A, cont, H, self.device, seed=self.seed,
                                            mfma_dtype=self.policy_kwargs.get("mfma_dtype", "f32"))
-        env.seed(self.seed)  # BaseAlgorithm.set_random_seed -> env.seed(seed): env i gets seed + i
+        if not getattr(self, "_keep_env_state", False):  # (load(..., force_reset=False): the env vector goes on where it stands)
+            env.seed(self.seed)  # BaseAlgorithm.set_random_seed -> env.seed(seed): env i gets seed + i
         T, N, D, dev = self.n_steps, self.n_envs, eng.obs_dim, self.device
         f32 = torch.float32
         # terminal-observation slots: the rollout paths that run the value net in batches (per-step launches; the fused f32 256-wide chunk,
@@ -1039,11 +1040,7 @@ class PPO:
         sd = self.policy.state_dict() if fz is None else self.policy.named_from_flat(fz["params"][: self.policy.n_trainable])
         order = sb3_format.parameter_order(self.policy.continuous)
         sd = {k: sd[k] for k in order}  # torch's registration order of an ActorCriticPolicy: also the optimizer's parameter indices
-        exp_avg, exp_avg_sq = (getattr(self, "exp_avg", None), getattr(self, "exp_avg_sq", None)) if fz is None else (fz["exp_avg"], fz["exp_avg_sq"])
-        has_moments = exp_avg is not None  # (a model loaded without an env has a policy but no optimizer state)
-        adam_step = (self._adam_step if fz is None else fz["adam_step"]) if has_moments else 0
-        opt = sb3_format.adam_state_dict(order, self.policy.named_from_flat(exp_avg) if has_moments else {},
-                                         self.policy.named_from_flat(exp_avg_sq) if has_moments else {}, adam_step, self.learning_rate)
+        opt = self._optimizer_state_dict(order, fz)
         with zipfile.ZipFile(path, "w") as z:  # stored, not deflated: what SB3's save_to_zip_file writes (and EvalCallback saves a zip per new best)
             z.writestr("data", json.dumps(self._data(), indent=2, default=str) if fz is None else fz["data"])
             z.writestr("policy.pth", _pth(sd))
@@ -1051,6 +1048,37 @@ class PPO:
             z.writestr("pytorch_variables.pth", _pth({}))
             z.writestr("_stable_baselines3_version", "2.9.0+three-mlagents_amd")
             z.writestr("system_info.txt", f"OS: {platform.platform()}\nPython: {platform.python_version()}\nPyTorch: {torch.__version__}\nGPU Enabled: True\n")
+
+    def _optimizer_state_dict(self, order, fz: dict | None) -> dict:
+        """`policy.optimizer.pth`: torch.optim.Adam's state_dict of the live moments (fz: of a freeze_for_save() snapshot)."""
+        from . import sb3_format
+
+        exp_avg, exp_avg_sq = (getattr(self, "exp_avg", None), getattr(self, "exp_avg_sq", None)) if fz is None else (fz["exp_avg"], fz["exp_avg_sq"])
+        has_moments = exp_avg is not None  # (a model loaded without an env has a policy but no optimizer state)
+        adam_step = (self._adam_step if fz is None else fz["adam_step"]) if has_moments else 0
+        return sb3_format.adam_state_dict(order, self.policy.named_from_flat(exp_avg) if has_moments else {},
+                                          self.policy.named_from_flat(exp_avg_sq) if has_moments else {}, adam_step, self.learning_rate)
+
+    ALGORITHM = "ppo"  # data["tma"]["algorithm"] of the zips a class writes and loads (zips from before the key existed are PPO's)
+
+    @classmethod
+    def _from_data(cls, data: dict, num, hidden: int, mfma: str) -> "PPO":
+        """An instance without an env from a zip's `data` (num(key, default): a scalar member, or the default where SB3 pickled an object)."""
+        return cls(data.get("policy_class", "MlpPolicy") if isinstance(data.get("policy_class"), str) else "MlpPolicy", None,
+                   learning_rate=num("learning_rate", 3e-4), n_steps=num("n_steps", 2048), batch_size=num("batch_size", 64),
+                   n_epochs=num("n_epochs", 10), gamma=num("gamma", 0.99), gae_lambda=num("gae_lambda", 0.95), clip_range=num("clip_range", 0.2),
+                   normalize_advantage=num("normalize_advantage", True), ent_coef=num("ent_coef", 0.0), vf_coef=num("vf_coef", 0.5),
+                   max_grad_norm=num("max_grad_norm", 0.5),
+                   policy_kwargs={"net_arch": [hidden, hidden], "mfma_dtype": mfma}, seed=num("seed", 0), _init_setup_model=False)
+
+    def _restore_extra(self, tma_extra: dict) -> None:
+        """Engine-only members of a zip's data["tma"] beyond the Adam step (none for PPO)."""
+
+    def _load_optimizer_state(self, state: dict, order) -> None:
+        if len(state) == len(order):  # torch.optim.Adam state, indexed in the policy's parameter order (SB3's own zips included)
+            self.exp_avg.copy_(self.policy.flat_from_named({k: state[i]["exp_avg"] for i, k in enumerate(order)}).to(self.device))
+            self.exp_avg_sq.copy_(self.policy.flat_from_named({k: state[i]["exp_avg_sq"] for i, k in enumerate(order)}).to(self.device))
+            self._adam_step = int(float(state[0]["step"]))
 
     @classmethod
     def load(cls, path, env=None, device="auto", **kwargs) -> "PPO":
@@ -1074,6 +1102,9 @@ class PPO:
         # whose keys/shapes are SB3's (mlp_extractor.policy_net.{0,2}, mlp_extractor.value_net.{0,2}, action_net, value_net, log_std)
         w1, wa = sd["mlp_extractor.policy_net.0.weight"], sd["action_net.weight"]
         tma_extra = data.get("tma") if isinstance(data.get("tma"), dict) else {}
+        written_by = str(tma_extra.get("algorithm", "ppo"))
+        if written_by != cls.ALGORITHM:
+            raise ValueError(f"{path} holds a {written_by.upper()} model; load it with {written_by.upper()}.load, not {cls.__name__}.load")
         data.setdefault("obs_dim", int(w1.shape[1]))
         data.setdefault("hidden", int(w1.shape[0]))
         data.setdefault("act_dim", int(wa.shape[0]))
@@ -1088,26 +1119,20 @@ class PPO:
             v = data.get(key, default)
             return default if isinstance(v, dict) or v is None else v  # SB3 stores schedules as pickled objects
 
-        model = cls(data.get("policy_class", "MlpPolicy") if isinstance(data.get("policy_class"), str) else "MlpPolicy", None,
-                    learning_rate=_num("learning_rate", 3e-4), n_steps=_num("n_steps", 2048), batch_size=_num("batch_size", 64),
-                    n_epochs=_num("n_epochs", 10), gamma=_num("gamma", 0.99), gae_lambda=_num("gae_lambda", 0.95), clip_range=_num("clip_range", 0.2),
-                    normalize_advantage=_num("normalize_advantage", True), ent_coef=_num("ent_coef", 0.0), vf_coef=_num("vf_coef", 0.5),
-                    max_grad_norm=_num("max_grad_norm", 0.5),
-                    policy_kwargs={"net_arch": [data["hidden"], data["hidden"]], "mfma_dtype": mfma}, seed=_num("seed", 0), _init_setup_model=False)
+        model = cls._from_data(data, _num, data["hidden"], mfma)
         model.num_timesteps, model._n_updates = data.get("num_timesteps", 0), data.get("_n_updates", 0)
         model._adam_step = int(tma_extra.get("adam_step", data.get("_adam_step", 0)))
         if env is not None:
             model.env = env
+            model._keep_env_state = not kwargs.get("force_reset", True)  # SB3's load(force_reset=True)
             model._setup_model()
+            model._restore_extra(tma_extra)
             model.policy.load_state_dict(sd)
             state = opt.get("state") or {}
             from . import sb3_format
 
             order = sb3_format.parameter_order(model.policy.continuous)
-            if len(state) == len(order):  # torch.optim.Adam state, indexed in the policy's parameter order (SB3's own zips included)
-                model.exp_avg.copy_(model.policy.flat_from_named({k: state[i]["exp_avg"] for i, k in enumerate(order)}).to(model.device))
-                model.exp_avg_sq.copy_(model.policy.flat_from_named({k: state[i]["exp_avg_sq"] for i, k in enumerate(order)}).to(model.device))
-                model._adam_step = int(float(state[0]["step"]))
+            model._load_optimizer_state(state, order)
         else:
             from .vec_env import _require_gpu
 

@@ -116,3 +116,14 @@ def adam_state_dict(order, exp_avg: dict, exp_avg_sq: dict, step: int, lr: float
     group = {"lr": lr, "betas": (0.9, 0.999), "eps": eps, "weight_decay": 0, "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
              "differentiable": False, "fused": None, "params": list(range(len(order)))}
     return {"state": state, "param_groups": [group]}
+
+
+def rmsprop_state_dict(order, square_avg: dict, step: int, lr: float, alpha: float = 0.99, eps: float = 1e-5) -> dict[str, Any]:
+    """stable_baselines3.common.sb2_compat.rmsprop_tf_like.RMSpropTFLike.state_dict() (A2C's optimizer; no momentum, not centered: the state of a
+    parameter is its step count and `square_avg`) for parameters `order`."""
+    state = {}
+    if step > 0:
+        for i, name in enumerate(order):
+            state[i] = {"step": int(step), "square_avg": square_avg[name].clone()}
+    group = {"lr": lr, "alpha": alpha, "eps": eps, "weight_decay": 0, "momentum": 0, "centered": False, "params": list(range(len(order)))}
+    return {"state": state, "param_groups": [group]}
