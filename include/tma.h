@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 214
+#define TMA_VERSION 215
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -188,6 +188,24 @@ int tma_policy_act_bootstrap(const float *params, const tma_policy_dims *d, cons
  * kernels.  Bad dims, null params / obs / actions, n < 1 and three NULL outputs are refused (TMA_ERR_INVALID) before any HIP call. */
 int tma_policy_evaluate_actions(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
                                 float *values_out, float *logp_out, float *entropy_out, void *stream);
+/* VJP of tma_policy_evaluate_actions with respect to the trainable parameters (ABI 215): what torch autograd computes behind SB3's
+ * ActorCriticPolicy.evaluate_actions when a caller's own loss is back-propagated through it --
+ *   grad_out[n_trainable] = sum_i  g_values[i] dV_i/dtheta + g_logp[i] dlogp_i/dtheta + g_entropy[i] dH_i/dtheta.
+ * Any cotangent (f32[n]) may be NULL (= zeros), not all three.  grad_out is OVERWRITTEN (every element written; the caller need not zero it).
+ * Parameter and gradient layout are tma_ppo_minibatch_grad's: the trainable prefix, [in][out] matrices, log_std last; `params` must be synced
+ * (the [out][in] copies are read).  obs f32[n][D] dense; actions i32[n] (Discrete) or f32[n][act_dim] (Box) as in tma_policy_evaluate_actions;
+ * a Discrete action outside [0, act_dim) is only ever compared with column indices: its one-hot is all zero and it never addresses memory.
+ * mfma_dtype 0 and 2 (2 runs the exact-f32 code, as evaluate_actions does); mfma_dtype 1 (bf16) is refused: its forward rounds the operands and
+ * an f32 backward would not be its derivative.  DETERMINISTIC: no float atomics; rows are walked in chunks (forward + input gradients of a
+ * chunk into `workspace`, then output-stationary weight-gradient GEMMs over its rows in row order, added to grad_out chunk after chunk), so the
+ * same inputs give the same bits on every run.  `workspace`: tma_policy_vjp_workspace_bytes(d, n) bytes of device memory, at most 256 MB for
+ * every accepted shape whatever n (0 + message for refused dims / n < 1).  TMA_VJP_CHUNK_ROWS (environment, read on every call; a multiple of 16,
+ * at least 16): a chunk length below the default.  Bad dims, null params / obs / actions / grad_out, n < 1, three NULL cotangents and a
+ * workspace below what the bytes function reports are refused (TMA_ERR_INVALID) before any HIP call. */
+int64_t tma_policy_vjp_workspace_bytes(const tma_policy_dims *d, int64_t n);
+int tma_policy_evaluate_actions_backward(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
+                                         const float *g_values, const float *g_logp, const float *g_entropy, float *grad_out, void *workspace,
+                                         int64_t workspace_bytes, void *stream);
 /* ActorCriticPolicy.predict_values */
 int tma_policy_values(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *values_out, void *stream);
 /* collect_rollouts timeout bootstrap: rewards[i] += gamma * V(terminal_obs[i]) where truncated[i] */

@@ -56,6 +56,7 @@ class A2C(PPO):
     def train(self) -> None:
         """SB3 A2C.train: one gradient over the whole rollout, clip_grad_norm_, one optimizer step."""
         L, pol, ws, st = _lib.lib(), self.policy, _lib.ptr(self.workspace), self._stream()
+        pol._sync_if_stepped()
         _lib.check(L.tma_ppo_stats_clear(ws, st))  # SB3 logs the last update's losses, not a mean over the log interval
         if self.use_rms_prop:
             _lib.check(L.tma_a2c_update_local(_lib.ptr(pol.params), C.byref(pol.dims), C.byref(self._rollout_view), C.byref(self._a2c_hp), _lib.ptr(self.grad),
@@ -104,6 +105,7 @@ class A2C(PPO):
             total_timesteps = int(total_timesteps) + self.num_timesteps
         self._total_timesteps = int(total_timesteps)
         L, eng, pol, b = _lib.lib(), self.env.engine, self.policy, self.buf
+        pol._sync_if_stepped()
         T, N = self.n_steps, self.n_envs
         per_iter = T * N
         t0 = time.time()

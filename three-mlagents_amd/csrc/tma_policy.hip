@@ -2441,6 +2441,8 @@ int tma_launch_slab_zero_w1(float *slabs, int n_slabs, const PLayout &L, hipStre
     return TMA_OK;
 }
 
+int tma_check_policy_dims(const tma_policy_dims *d) { return check_dims(d); }
+
 extern "C" {
 
 int64_t tma_ppo_workspace_bytes(const tma_policy_dims *d) {

@@ -286,3 +286,5 @@ int tma_launch_build_split3(float *params, const tma::PLayout &L, hipStream_t s)
 bool tma_split3_eligible(const tma::PLayout &L, int64_t count);
 // tma_policy.hip: zero the layer-1 weight columns of every slab (layouts that accumulate dW1 in place)
 int tma_launch_slab_zero_w1(float *slabs, int n_slabs, const tma::PLayout &L, hipStream_t s);
+// tma_policy.hip: the shape check every tma_policy_* entry point starts with (TMA_ERR_INVALID + message, no HIP call) -- for tma_vjp.hip
+int tma_check_policy_dims(const tma_policy_dims *d);

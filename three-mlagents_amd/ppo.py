@@ -82,6 +82,25 @@ def orthogonal_init(obs_dim: int, hidden: int, act_dim: int, continuous: bool, s
     return sd
 
 
+class _EvaluateActions(torch.autograd.Function):
+    """evaluate_actions as a node of a torch autograd graph (HipActorCriticPolicy.parameters() opts in): the forward is the forward-only call,
+    the backward ONE tma_policy_evaluate_actions_backward launch sequence with whichever cotangents autograd supplies."""
+
+    @staticmethod
+    def forward(ctx, leaf, policy, obs, actions):
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None -> NULL, not as a zero array
+        ctx.save_for_backward(leaf)  # (torch then refuses a backward after an in-place step on the leaf, as it does for its own modules)
+        ctx.policy, ctx.obs, ctx.actions = policy, obs, actions
+        return policy._evaluate_actions(obs, actions)
+
+    @staticmethod
+    def backward(ctx, g_values, g_logp, g_entropy):
+        (leaf,) = ctx.saved_tensors
+        if g_values is None and g_logp is None and g_entropy is None:
+            return torch.zeros_like(leaf), None, None, None
+        return ctx.policy.evaluate_actions_backward(ctx.obs, ctx.actions, g_values, g_logp, g_entropy), None, None, None
+
+
 class HipActorCriticPolicy:
     """Parameters of SB3's ActorCriticPolicy(MlpPolicy) in one flat HBM buffer + the forward kernels."""
 
@@ -101,6 +120,9 @@ class HipActorCriticPolicy:
         _lib.check(_lib.lib().tma_policy_param_offsets(C.byref(self.dims), offs))
         self.offsets = list(offs)
         self.params = torch.zeros(self.n_total, dtype=torch.float32, device=self.device)
+        self._leaf: torch.Tensor | None = None  # parameters(): the autograd leaf over params[:n_trainable]; None = forward-only, as ever
+        self._synced_version = 0                # ... and its _version when the derived copies were last rebuilt
+        self._vjp_ws: torch.Tensor | None = None
         self.load_state_dict(self._orthogonal_init(seed))
 
     # -- init / (de)serialisation in SB3's state_dict naming -------------------------------
@@ -113,8 +135,32 @@ class HipActorCriticPolicy:
         return list(zip(SB3_KEYS, self.offsets[:12], shapes))
 
     def load_state_dict(self, sd: dict[str, torch.Tensor]) -> None:
-        self.params[: self.n_trainable].copy_(self.flat_from_named(sd).to(self.device))
+        with torch.no_grad():
+            self.params[: self.n_trainable].copy_(self.flat_from_named(sd).to(self.device))
+        self.sync()
+
+    # -- torch autograd / optimizers (opt-in: nothing below runs until parameters() is called) ----
+    def parameters(self) -> list[torch.Tensor]:
+        """One leaf tensor (requires_grad) that ALIASES the trainable prefix of the flat buffer, created once: `torch.optim.X(policy.parameters())`
+        steps the live weights, and `evaluate_actions` becomes differentiable with respect to it.  The kernel-launching methods rebuild the
+        derived weight copies (`sync`) when an in-place step moved the leaf since the last rebuild.  bf16 policies are refused: their forward
+        rounds the operands and the f32 backward would not be its derivative."""
+        if self.mfma_dtype == "bf16":
+            raise ValueError("parameters(): the backward of evaluate_actions is not built for mfma_dtype='bf16' (use 'f32' or 'bf16x3')")
+        if self._leaf is None:
+            self._leaf = self.params[: self.n_trainable].detach().requires_grad_(True)
+            self._synced_version = self._leaf._version
+        return [self._leaf]
+
+    def sync(self) -> None:
+        """tma_policy_sync: rebuild everything derived from the trainable prefix ([out][in] copies, LDS / fragment images)."""
         _lib.check(_lib.lib().tma_policy_sync(_lib.ptr(self.params), C.byref(self.dims), _lib.stream_ptr(self.device)))
+        if self._leaf is not None:
+            self._synced_version = self._leaf._version
+
+    def _sync_if_stepped(self) -> None:
+        if self._leaf is not None and self._leaf._version != self._synced_version:
+            self.sync()
 
     def state_dict(self) -> dict[str, torch.Tensor]:
         return self.named_from_flat(self.params[: self.n_trainable])
@@ -151,6 +197,7 @@ class HipActorCriticPolicy:
         return obs.to(self.device, torch.float32).contiguous()
 
     def act(self, obs: torch.Tensor, *, rng_seed: int = 0, rng_step: int = 0, env_offset: int = 0, deterministic: bool = False):
+        self._sync_if_stepped()
         obs = self._rows(obs)
         n = obs.shape[0]
         if self.continuous:
@@ -174,20 +221,65 @@ class HipActorCriticPolicy:
         log-probabilities of the GIVEN actions and the entropies of the action distributions (tma_policy_evaluate_actions: the kernels `act` runs,
         so `values` carries act's bits, and `log_prob` too where `actions` are the ones it drew).  actions: int32 [n] (Discrete; an action outside
         [0, n_actions) gives that row a NaN log_prob) or float32 [n, act_dim] (Box, unclipped) -- the rollout buffer's dtypes and layout, anything
-        else is a ValueError."""
-        obs = self._rows(obs)
+        else is a ValueError.
+
+        After `parameters()` -- and while its leaf requires grad and torch.is_grad_enabled() -- the three outputs (the same kernels, the same
+        bits) are nodes of a torch autograd graph: `loss.backward()` leaves the gradient with respect to the flat trainable vector in
+        `parameters()[0].grad` (one tma_policy_evaluate_actions_backward call).  Gradients with respect to `obs` are not built: an `obs` that
+        requires grad is a ValueError."""
+        self._sync_if_stepped()
+        differentiable = self._leaf is not None and self._leaf.requires_grad and torch.is_grad_enabled()
+        if differentiable and isinstance(obs, torch.Tensor) and obs.requires_grad:
+            raise ValueError("evaluate_actions: gradients with respect to the observations are not built (obs.requires_grad is set)")
+        obs, actions = self._rows_actions(obs, actions)
+        if differentiable:
+            return _EvaluateActions.apply(self._leaf, self, obs, actions)
+        return self._evaluate_actions(obs, actions)
+
+    def _rows_actions(self, obs: torch.Tensor, actions: torch.Tensor):
+        obs = self._rows(obs.detach())
         n = obs.shape[0]
         want_shape, want_dtype = ((n, self.act_dim), torch.float32) if self.continuous else ((n,), torch.int32)
         if not isinstance(actions, torch.Tensor) or actions.dtype != want_dtype or tuple(actions.shape) != want_shape:
             raise ValueError(f"actions must be a {want_dtype} tensor of shape {list(want_shape)}, got "
                              f"{getattr(actions, 'dtype', type(actions).__name__)} {list(getattr(actions, 'shape', []))}")
-        actions = actions.to(self.device).contiguous()
+        return obs, actions.detach().to(self.device).contiguous()
+
+    def _evaluate_actions(self, obs: torch.Tensor, actions: torch.Tensor):
+        n = obs.shape[0]
         values, logp, entropy = (torch.empty((n,), dtype=torch.float32, device=self.device) for _ in range(3))
         _lib.check(_lib.lib().tma_policy_evaluate_actions(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), _lib.ptr(actions), n,
                                                           _lib.ptr(values), _lib.ptr(logp), _lib.ptr(entropy), _lib.stream_ptr(self.device)))
         return values, logp, entropy
 
+    def evaluate_actions_backward(self, obs: torch.Tensor, actions: torch.Tensor, g_values=None, g_logp=None, g_entropy=None) -> torch.Tensor:
+        """Vector-Jacobian product of evaluate_actions with respect to the trainable parameters (tma_policy_evaluate_actions_backward): the flat
+        gradient [n_trainable] of  sum_i g_values[i] V_i + g_logp[i] logp_i + g_entropy[i] H_i.  A cotangent may be None (zeros), not all three.
+        Deterministic: equal inputs give equal bits."""
+        self._sync_if_stepped()
+        obs, actions = self._rows_actions(obs, actions)
+        n = obs.shape[0]
+        cots = []
+        for name, c in (("g_values", g_values), ("g_logp", g_logp), ("g_entropy", g_entropy)):
+            if c is not None:
+                if tuple(c.shape) != (n,):
+                    raise ValueError(f"{name} must have shape [{n}], got {list(c.shape)}")
+                c = c.detach().to(self.device, torch.float32).contiguous()
+            cots.append(c)
+        L = _lib.lib()
+        need = int(L.tma_policy_vjp_workspace_bytes(C.byref(self.dims), n))
+        if need <= 0:
+            _lib.check(_lib.TMA_ERR_INVALID)
+        if self._vjp_ws is None or self._vjp_ws.numel() < need:  # allocated lazily, kept: it grows to the chunk bound and stays there
+            self._vjp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        grad = torch.empty(self.n_trainable, dtype=torch.float32, device=self.device)
+        _lib.check(L.tma_policy_evaluate_actions_backward(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), _lib.ptr(actions), n,
+                                                          _lib.ptr(cots[0]), _lib.ptr(cots[1]), _lib.ptr(cots[2]), _lib.ptr(grad),
+                                                          _lib.ptr(self._vjp_ws), self._vjp_ws.numel(), _lib.stream_ptr(self.device)))
+        return grad
+
     def predict_values(self, obs: torch.Tensor) -> torch.Tensor:
+        self._sync_if_stepped()
         obs = self._rows(obs)
         values = torch.empty((obs.shape[0],), dtype=torch.float32, device=self.device)
         _lib.check(_lib.lib().tma_policy_values(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), obs.shape[0], _lib.ptr(values),
@@ -499,6 +591,7 @@ class PPO:
     def collect_rollouts(self, callback=None, chunk: int | None = None) -> bool:
         """SB3 OnPolicyAlgorithm.collect_rollouts: n_steps vector steps through the native driver, then GAE."""
         L, T, eng = _lib.lib(), self.n_steps, self.env.engine
+        self.policy._sync_if_stepped()  # (a torch optimizer stepped policy.parameters(): rebuild the derived copies the drivers read)
         if not self._last_obs_valid:
             eng.reset(self.buf["obs"][0])
             self._last_obs_valid = True
@@ -541,6 +634,7 @@ class PPO:
     def train(self) -> None:
         """SB3 PPO.train: n_epochs passes over the permuted rollout in minibatches of batch_size."""
         L = _lib.lib()
+        self.policy._sync_if_stepped()
         total = self.n_steps * self.n_envs
         scale = 1.0 / self.world_size
         perm_seed = (self.seed * 2654435761 + 12345) & 0xFFFFFFFF
