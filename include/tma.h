@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 215
+#define TMA_VERSION 216
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -416,8 +416,9 @@ enum {
     TMA_DISPATCH_FWD_BF16_NTW2_DISCRETE = 8, TMA_DISPATCH_FWD_BF16_NTW3_DISCRETE = 9, TMA_DISPATCH_FWD_BF16_NTW4_DISCRETE = 10,
     TMA_DISPATCH_FWD_BF16_NTW2_BOX = 11, TMA_DISPATCH_FWD_BF16_NTW3_BOX = 12, TMA_DISPATCH_FWD_BF16_NTW4_BOX = 13,
     TMA_DISPATCH_FWD_GENERIC_W4 = 14, TMA_DISPATCH_FWD_GENERIC_W2 = 15, TMA_DISPATCH_FWD_GENERIC_W1 = 16,
-    /* gradient: H = 64 kernel (<= 2048 samples: one tile per wave; else the persistent eight-wave kernel); bf16; three-term bf16 split */
-    TMA_DISPATCH_GRAD_H64_SMALL = 32, TMA_DISPATCH_GRAD_H64 = 33, TMA_DISPATCH_GRAD_BF16 = 34, TMA_DISPATCH_GRAD_BF16X3 = 35,
+    /* gradient: H = 64 kernel (<= 2048 samples: one tile per wave; else the persistent eight-wave kernel); three-term bf16 split.  (34 was
+     * TMA_DISPATCH_GRAD_BF16 up to ABI 215: the bf16 kernels have one id per leaf below) */
+    TMA_DISPATCH_GRAD_H64_SMALL = 32, TMA_DISPATCH_GRAD_H64 = 33, TMA_DISPATCH_GRAD_BF16X3 = 35,
     /* f32 column-parallel, layer-1 k-tiles kt1 = 1 (D <= 16) / 2 (D <= 32): half (16-row) or full row groups, four or eight waves,
      * dW2 deferred to the follow-up reduction or accumulated in the slabs */
     TMA_DISPATCH_GRAD_F32_KT1_HALF_W4 = 36, TMA_DISPATCH_GRAD_F32_KT1_FULL_W4 = 37, TMA_DISPATCH_GRAD_F32_KT2_HALF_W4 = 38,
@@ -431,6 +432,14 @@ enum {
     TMA_DISPATCH_GRAD_F32_KT107_RECOMPUTE = 50, TMA_DISPATCH_GRAD_F32_KT0 = 51,
     /* generic float-atomic kernel by waves per block */
     TMA_DISPATCH_GRAD_GENERIC_W4 = 52, TMA_DISPATCH_GRAD_GENERIC_W3 = 53, TMA_DISPATCH_GRAD_GENERIC_W2 = 54, TMA_DISPATCH_GRAD_GENERIC_W1 = 55,
+    /* bf16 column-parallel (ABI 216; plan_grad_bf): dW1 in registers, one (D <= 16) / two (D <= 32) k-tiles, 32-row (MT2) or 64-row (MT4) groups,
+     * _W8: eight waves (Discrete head, H = 256); two passes with 2 (33..64 observations) / 6 (161..192) / 4 (97..128, Box head, H = 256) layer-1
+     * k-steps, dW1 from the cached dz1 images or a recomputed chain, _W8: eight waves (Box head, H = 256); any other width: runtime width */
+    TMA_DISPATCH_GRAD_BF16_KT1_MT2 = 80, TMA_DISPATCH_GRAD_BF16_KT1_MT4 = 81, TMA_DISPATCH_GRAD_BF16_KT1_MT4_W8 = 82,
+    TMA_DISPATCH_GRAD_BF16_KT2_MT2 = 83, TMA_DISPATCH_GRAD_BF16_KT2_MT4 = 84,
+    TMA_DISPATCH_GRAD_BF16_KS2_CACHED = 85, TMA_DISPATCH_GRAD_BF16_KS2_RECOMPUTE = 86, TMA_DISPATCH_GRAD_BF16_KS6_CACHED = 87,
+    TMA_DISPATCH_GRAD_BF16_KS6_RECOMPUTE = 88, TMA_DISPATCH_GRAD_BF16_KS6_W8_CACHED = 89, TMA_DISPATCH_GRAD_BF16_KS6_W8_RECOMPUTE = 90,
+    TMA_DISPATCH_GRAD_BF16_KS4_W8_CACHED = 91, TMA_DISPATCH_GRAD_BF16_KS4_W8_RECOMPUTE = 92, TMA_DISPATCH_GRAD_BF16_RUNTIME = 93,
     /* optimizer: Adam + scatter into the derived copies (H = 64 fast path / column-parallel layouts); single-block kernel; multi-block kernel
      * + tma_policy_sync; the _local forms of the two scatters, which fold the norm partials the gradient's reduction left */
     TMA_DISPATCH_OPT_SCATTER_H64 = 64, TMA_DISPATCH_OPT_SCATTER_WIDE = 65, TMA_DISPATCH_OPT_SMALL = 66, TMA_DISPATCH_OPT_ADAM = 67,
@@ -454,7 +463,7 @@ int tma_debug_last_dispatch(int32_t *fwd_out, int32_t *grad_out, int32_t *opt_ou
  * `d` as the real call does, runs the same pure plan function (csrc/tma_policy_plan.h) with the environment switches the real call would read,
  * and returns the real call's status and message where that would refuse the shape.  *id_out: the id tma_debug_last_dispatch reports after
  * the real call.  grid / block / LDS bytes: the forward kernel's; the gradient's dominant kernel (the first of the two launches of the
- * two-pass kernels) -- but *lds_bytes_out = -1 where the family's own launcher picks that geometry (H = 64, bf16, three-term split): grid and
+ * two-pass kernels; ABI 216: the bf16 kernels' too) -- but *lds_bytes_out = -1 where the family's own launcher picks that geometry (H = 64, three-term split): grid and
  * block are then the slab reduction's that follows; the optimizer kernel's that steps the parameters (LDS 0).  Any output pointer may be NULL. */
 #define TMA_PLAN_FWD 0
 #define TMA_PLAN_GRAD 1

@@ -76,24 +76,28 @@ def test_bf16_forward(D, H, A, cont):
         assert torch.allclose(lp.cpu(), lp_e, rtol=4e-3, atol=4e-3)
 
 
-def _emulated_grad(sd, obs, actions, old_lp, adv, ret, hp):
+def _emulated_grad(sd, obs, actions, old_lp, adv, ret, hp, dtype=torch.float32):
     """Gradient of the PPO loss with the kernel's rounding points: bf16 weights / activations / back-propagated deltas as
-    GEMM operands, f32 everywhere else (loss, accumulation).  The hidden-layer bias gradients are the column sums of the SAME bf16
-    deltas the weight gradients use (ones^T . dz on the MFMA -- what torch.autocast(bfloat16) computes too: grad_output is bf16
-    there); the head bias gradient sums the f32 loss gradient.  Returns (grads in SB3 naming, stats)."""
+    GEMM operands, `dtype` everywhere else (loss, accumulation: float32 as the kernel has it; float64: the reference of
+    tests/test_policy_dispatch_gpu.py, the same rounding points with exact sums).  The hidden-layer bias gradients are the column sums of
+    the SAME bf16 deltas the weight gradients use (ones^T . dz on the MFMA -- what torch.autocast(bfloat16) computes too: grad_output is bf16
+    there); the head bias gradient sums the unrounded loss gradient.  Returns (grads in SB3 naming, stats)."""
     cont = "log_std" in sd
-    X = _bf(obs)
+    bf = lambda x: _bf(x.float()).to(dtype)  # noqa: E731
+    w = lambda k: sd[k].to(dtype)  # noqa: E731
+    old_lp, adv, ret = old_lp.to(dtype), adv.to(dtype), ret.to(dtype)
+    X = bf(obs)
     acts, outs = {}, {}
     for prefix, head in (("policy_net", "action_net"), ("value_net", "value_net")):
-        h1 = _bf(torch.tanh(X @ _bf(sd[f"mlp_extractor.{prefix}.0.weight"]).t() + sd[f"mlp_extractor.{prefix}.0.bias"]))
-        h2 = _bf(torch.tanh(h1 @ _bf(sd[f"mlp_extractor.{prefix}.2.weight"]).t() + sd[f"mlp_extractor.{prefix}.2.bias"]))
+        h1 = bf(torch.tanh(X @ bf(sd[f"mlp_extractor.{prefix}.0.weight"]).t() + w(f"mlp_extractor.{prefix}.0.bias")))
+        h2 = bf(torch.tanh(h1 @ bf(sd[f"mlp_extractor.{prefix}.2.weight"]).t() + w(f"mlp_extractor.{prefix}.2.bias")))
         acts[prefix] = (h1, h2)
-        outs[prefix] = (h2 @ _bf(sd[f"{head}.weight"]).t() + sd[f"{head}.bias"]).detach().requires_grad_()
+        outs[prefix] = (h2 @ bf(sd[f"{head}.weight"]).t() + w(f"{head}.bias")).detach().requires_grad_()
     out_pi, out_v = outs["policy_net"], outs["value_net"]
-    ls = sd["log_std"].clone().requires_grad_() if cont else None
+    ls = w("log_std").clone().requires_grad_() if cont else None
     if cont:
         dist = torch.distributions.Normal(out_pi, torch.ones_like(out_pi) * ls.exp())
-        log_prob, entropy = dist.log_prob(actions).sum(dim=1), dist.entropy().sum(dim=1)
+        log_prob, entropy = dist.log_prob(actions.to(dtype)).sum(dim=1), dist.entropy().sum(dim=1)
     else:
         dist = torch.distributions.Categorical(logits=out_pi)
         log_prob, entropy = dist.log_prob(actions.long().flatten()), dist.entropy()
@@ -108,18 +112,20 @@ def _emulated_grad(sd, obs, actions, old_lp, adv, ret, hp):
     grads = {}
     for prefix, head, dz3 in (("policy_net", "action_net", out_pi.grad), ("value_net", "value_net", out_v.grad)):
         h1, h2 = acts[prefix]
-        z3 = _bf(dz3)
+        z3 = bf(dz3)
         grads[f"{head}.weight"], grads[f"{head}.bias"] = z3.t() @ h2, dz3.sum(0)
-        dz2 = (z3 @ _bf(sd[f"{head}.weight"])) * (1 - h2 * h2)
-        z2 = _bf(dz2)
+        dz2 = (z3 @ bf(sd[f"{head}.weight"])) * (1 - h2 * h2)
+        z2 = bf(dz2)
         grads[f"mlp_extractor.{prefix}.2.weight"], grads[f"mlp_extractor.{prefix}.2.bias"] = z2.t() @ h1, z2.sum(0)
-        dz1 = (z2 @ _bf(sd[f"mlp_extractor.{prefix}.2.weight"])) * (1 - h1 * h1)
-        z1 = _bf(dz1)
+        dz1 = (z2 @ bf(sd[f"mlp_extractor.{prefix}.2.weight"])) * (1 - h1 * h1)
+        z1 = bf(dz1)
         grads[f"mlp_extractor.{prefix}.0.weight"], grads[f"mlp_extractor.{prefix}.0.bias"] = z1.t() @ X, z1.sum(0)
     if cont:
         grads["log_std"] = ls.grad
-    stats = dict(policy_loss=pl.item(), value_loss=vl.item(), entropy_loss=(-entropy.mean()).item(),
-                 clip_fraction=float(((ratio - 1).abs() > hp["clip_range"]).float().mean()), log_prob=log_prob.detach())
+    with torch.no_grad():
+        approx_kl = ((ratio - 1) - (log_prob - old_lp)).mean().item()
+    stats = dict(policy_loss=pl.item(), value_loss=vl.item(), entropy_loss=(-entropy.mean()).item(), approx_kl=approx_kl,
+                 clip_fraction=float(((ratio - 1).abs() > hp["clip_range"]).to(dtype).mean()), log_prob=log_prob.detach())
     return grads, stats
 
 

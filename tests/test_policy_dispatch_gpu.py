@@ -39,12 +39,34 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 K, F = 16.0, 4e-6
 K_BF, F_BF = 8.0, 4e-3  # (a sum that lands on a bf16 rounding boundary flips one activation by one bf16 ulp: test_bf16_gpu.py's 4e-3)
 CLIP_MARGIN = 2e-2  # |ratio - 1| kept this far from clip_range in float64 (tests/test_ppo_gpu.py's _rollout keeps 5e-3 in float32)
+# bf16 gradient rows: reference = test_bf16_gpu._emulated_grad (the kernel's bf16 rounding points) in float64, calibration = the same in float32.
+# Where no float32 sum lands on the other side of a bf16 rounding boundary the kernels sit 1e-7 .. 2e-6 of max |g| from the reference; one such flip
+# of an activation or a delta moves one sample's terms by 2^-8 of themselves, and the float32 emulation has flips of its own, in other places
+# (its sums are in yet another order).  In a large minibatch both average out (kernel and calibration 1e-4 .. 1e-3 of max |g|, ratio 0.3 .. 3);
+# in a small one a flip is a rare whole event that the calibration may not have, so F has to carry it: at B = 1 a flip is up to 2.2 * 2^-8
+# of max |g|.  MI355X run with these constants: worst budget use 0.48 (17 x 256 x 3 Discrete, B = 1, action_net.weight: 8.7e-3 of max |g|,
+# calibration exact), next 0.12; the dropped-tile reference overshoots at least 2.0-fold (Box 32 x 256 x 4, 4096 samples), the heavy-tile rows
+# at least 6-fold; statistics at most 1.03e-3 (Box 105 x 256 x 8, B = 1: policy_loss of the one sample), 0.41 of S_BF_G, next 1.8e-4.
+# First run, K = 8, F = 4e-6: worst use 412 (Box 172 x 256 x 20, B = 77) -- F cannot be the float32 rows' F.
+K_BF_G, F_BF_G = 8.0, 1.8e-2
+S_BF_G = 2.5e-3  # the four averaged statistics, relative to max(1, |reference|)
+# A dropped tile of `drop` rows out of B moves a segment by about sqrt(drop / B) of its max |g| (a sum of B terms of either sign), and the
+# budget above is 2e-2 .. 3e-2 of it: where the last row tile holds less than a thousandth of the minibatch the comparator could not see
+# it go.  Those rows make the tile heavy instead: its advantages and returns times BF_HEAVY, normalize_advantage off (so that the factor
+# is not divided out again).
+BF_HEAVY = 100.0
+
+
+def bf_heavy_tile(B):
+    return (B % 16 or 16) * 1024 < B
 
 # (entry, D, H, A, continuous, B or n, expected dispatch id: TMA_DISPATCH_ name without the prefix, "|GRID_CAPPED" where the grid is capped)
 # entries: grad (explicit indices) / grad_perm (Feistel permutation) / grad_noadv (normalize_advantage off) / grad_nodz1 (TMA_NO_DZ1_CACHE) /
-# grad_nodefer (TMA_NO_DEFER_W2, in a child process: read once per process) / grad_bf16 / grad_bf16x3 (dispatch only: their numerics are
-# test_bf16_gpu.py's and test_split3_gpu.py's) / fwd / fwd_bf16 / opt / opt_bf16 (tma_ppo_adam_step after a gradient of B samples) /
+# grad_nodefer (TMA_NO_DEFER_W2, in a child process: read once per process) / grad_bf16x3 (dispatch only: its numerics are
+# test_split3_gpu.py's) / fwd / fwd_bf16 / opt / opt_bf16 (tma_ppo_adam_step after a gradient of B samples) /
 # opt_local / opt_local_bf16 (tma_ppo_adam_step_local with last_count = B)
+# bf16 gradient rows (float64 emulation with the kernel's rounding points): grad_bf16 / grad_perm_bf16 / grad_noadv_bf16 / grad_nodz1_bf16 and, in a
+# child process each (read once per process), grad_nw4_bf16 (TMA_BF_NW4: four waves throughout) / grad_mt2_bf16 (TMA_BF_MT2: 32-row groups)
 _N_EDGES = (1, 15, 16, 17, 31, 32, 33)
 _FWD_SHAPES = [  # (D, H, A, cont, id) -- Discrete A = 2 / 16 and Box A = 1 / 32 among them
     (4, 64, 5, False, "FWD_H64"), (4, 64, 16, False, "FWD_H64"),
@@ -72,6 +94,78 @@ def _wide_grad_cases():
                 ident = ("KT2_HALF_W8_DEFER" if half else "KT2_FULL_W8") if w8 else ("KT2_HALF_W4" if half else "KT2_FULL_W4")
                 out.append(("grad", D, H, A + 1, cont, B, "GRAD_F32_" + ident))
     return out
+
+
+_BF_EDGES = (1, 31, 32, 33, 77)  # row-group edges of the 32-row leaves
+
+
+def _bf_grad_cases():
+    """Every leaf of plan_grad_bf (csrc/tma_policy_plan.h) at every hidden width and head it takes, both ends of every observation-width class
+    (16 / 17, 32 / 33, 64 / 65, 96 / 97, 128 / 129, 160 / 161, 192 / 193), head widths Discrete 2 / 16 and Box 1 / 32 on 32-row and on 64-row
+    leaves.  Sizes: the row-group edges; 3841 = 121 groups of 32 (between the value net's block cap and the policy net's: only the value blocks
+    loop) with a 1-row last group; 4500 / 4733 = more 32-row groups than blocks (136 / 144 policy blocks); 4096 | 4097 = the switch to 64-row
+    groups (65 groups, the last with one row); 7681 = 121 groups of 64, between the two caps of the eight-wave kernel; 9001 / 9301 = more 64-row groups than blocks, ragged; 33000 on the two timed configurations."""
+    e, G = "grad_bf16", "GRAD_BF16_"
+    out = [(e, 6, 256, 5, False, 1000, G + "KT1_MT2")]
+    # dW1 in registers, 32-row groups: up to 4096 samples, and at H = 192 throughout
+    out += [(e, 16, 128, 5, False, B, G + "KT1_MT2") for B in _BF_EDGES]
+    out += [(e, 16, 192, 16, False, 3841, G + "KT1_MT2"), (e, 6, 192, 2, False, 4500, G + "KT1_MT2"), (e, 16, 256, 2, False, 4096, G + "KT1_MT2"),
+            (e, 16, 128, 1, True, 3841, G + "KT1_MT2"), (e, 8, 192, 32, True, 4733, G + "KT1_MT2"), (e, 16, 256, 3, True, 4096, G + "KT1_MT2")]
+    out += [(e, 17, 256, 3, False, B, G + "KT2_MT2") for B in _BF_EDGES]
+    out += [(e, 32, 128, 16, False, 3841, G + "KT2_MT2"), (e, 21, 192, 3, False, 4500, G + "KT2_MT2"), (e, 17, 128, 1, True, 77, G + "KT2_MT2"),
+            (e, 32, 192, 32, True, 4733, G + "KT2_MT2"), (e, 17, 192, 4, True, 3841, G + "KT2_MT2"), (e, 32, 256, 4, True, 4096, G + "KT2_MT2")]
+    # 64-row groups beyond 4096 samples; the Discrete head at H = 256 with <= 16 observations on eight waves
+    out += [(e, 16, 128, 5, False, 4097, G + "KT1_MT4"), (e, 16, 128, 16, False, 9001, G + "KT1_MT4"), (e, 16, 128, 32, True, 4097, G + "KT1_MT4"),
+            (e, 16, 256, 1, True, 9301, G + "KT1_MT4"), (e, 6, 256, 3, True, 4097, G + "KT1_MT4"),
+            (e, 16, 256, 5, False, 4097, G + "KT1_MT4_W8"), (e, 16, 256, 2, False, 9001, G + "KT1_MT4_W8"), (e, 4, 256, 16, False, 4097, G + "KT1_MT4_W8"),
+            (e, 6, 256, 5, False, 33000, G + "KT1_MT4_W8"),  # Ball3D
+            (e, 6, 256, 5, False, 7681, G + "KT1_MT4_W8"),  # 121 groups of 64: between this kernel's 116 value blocks and 140 policy blocks
+            (e, 17, 128, 3, False, 4097, G + "KT2_MT4"), (e, 32, 128, 2, False, 9001, G + "KT2_MT4"), (e, 21, 256, 3, False, 4097, G + "KT2_MT4"),  # Basic
+            (e, 17, 256, 16, False, 9001, G + "KT2_MT4"), (e, 17, 128, 1, True, 9301, G + "KT2_MT4"), (e, 32, 256, 32, True, 4097, G + "KT2_MT4")]
+    # two passes, two layer-1 k-steps (33 .. 64 observations)
+    out += [(e, 33, 128, 5, False, B, G + "KS2_CACHED") for B in _BF_EDGES]
+    out += [(e, 64, 192, 2, False, 3841, G + "KS2_CACHED"), (e, 64, 256, 16, False, 4733, G + "KS2_CACHED"), (e, 33, 128, 1, True, 3841, G + "KS2_CACHED"),
+            (e, 40, 192, 7, True, 4733, G + "KS2_CACHED"), (e, 64, 256, 32, True, 1025, G + "KS2_CACHED"),
+            ("grad_nodz1_bf16", 64, 256, 5, False, 4733, G + "KS2_RECOMPUTE"), ("grad_nodz1_bf16", 33, 128, 3, True, 1025, G + "KS2_RECOMPUTE")]
+    # ... six (161 .. 192: Crawler's 172), on four waves except for Box heads at H = 256
+    out += [(e, 161, 128, 5, False, B, G + "KS6_CACHED") for B in _BF_EDGES]
+    out += [(e, 192, 192, 16, False, 3841, G + "KS6_CACHED"), (e, 172, 256, 2, False, 4733, G + "KS6_CACHED"), (e, 161, 128, 20, True, 3841, G + "KS6_CACHED"),
+            (e, 192, 192, 1, True, 4733, G + "KS6_CACHED"),
+            ("grad_nodz1_bf16", 192, 256, 5, False, 1025, G + "KS6_RECOMPUTE"), ("grad_nodz1_bf16", 172, 192, 32, True, 4733, G + "KS6_RECOMPUTE")]
+    out += [(e, 172, 256, 20, True, B, G + "KS6_W8_CACHED") for B in _BF_EDGES + (33000,)]
+    out += [(e, 161, 256, 1, True, 3841, G + "KS6_W8_CACHED"), (e, 192, 256, 32, True, 4733, G + "KS6_W8_CACHED"),
+            ("grad_nodz1_bf16", 161, 256, 20, True, 4733, G + "KS6_W8_RECOMPUTE")]
+    # ... four (97 .. 128 with a Box head at H = 256: the reference's ant task), eight waves
+    out += [(e, 105, 256, 8, True, B, G + "KS4_W8_CACHED") for B in _BF_EDGES]
+    out += [(e, 97, 256, 1, True, 3841, G + "KS4_W8_CACHED"), (e, 128, 256, 32, True, 4733, G + "KS4_W8_CACHED"),
+            ("grad_nodz1_bf16", 128, 256, 8, True, 1025, G + "KS4_W8_RECOMPUTE"), ("grad_nodz1_bf16", 97, 256, 3, True, 4733, G + "KS4_W8_RECOMPUTE")]
+    # runtime width: everything else (the Ant width with a Discrete head or at H = 128 among it)
+    out += [(e, 65, 128, 5, False, B, G + "RUNTIME") for B in _BF_EDGES]
+    out += [(e, 96, 192, 2, False, 3841, G + "RUNTIME"), (e, 129, 256, 16, False, 4733, G + "RUNTIME"), (e, 160, 128, 3, False, 1025, G + "RUNTIME"),
+            (e, 193, 256, 4, False, 1025, G + "RUNTIME"), (e, 105, 256, 5, False, 3841, G + "RUNTIME"), (e, 97, 192, 3, False, 77, G + "RUNTIME"),
+            (e, 105, 128, 8, True, 4733, G + "RUNTIME"), (e, 128, 192, 32, True, 3841, G + "RUNTIME"), (e, 65, 256, 3, True, 4733, G + "RUNTIME"),
+            (e, 96, 192, 6, True, 77, G + "RUNTIME"), (e, 129, 256, 1, True, 1025, G + "RUNTIME"), (e, 160, 128, 4, True, 1025, G + "RUNTIME"),
+            (e, 193, 192, 2, True, 1025, G + "RUNTIME")]
+    # the Feistel-permutation and normalize_advantage = False entries: a 64-row leaf, a two-pass leaf and the runtime width each
+    out += [("grad_perm_bf16", 16, 256, 5, False, 4097, G + "KT1_MT4_W8"), ("grad_noadv_bf16", 21, 256, 3, False, 4097, G + "KT2_MT4"),
+            ("grad_perm_bf16", 172, 256, 20, True, 1025, G + "KS6_W8_CACHED"), ("grad_noadv_bf16", 40, 128, 4, False, 1025, G + "KS2_CACHED"),
+            ("grad_perm_bf16", 100, 128, 4, False, 1025, G + "RUNTIME"), ("grad_noadv_bf16", 105, 256, 5, False, 1025, G + "RUNTIME")]
+    # per-process switches: the four-wave kernels that TMA_BF_NW4 alone reaches; 32-row groups past 4096 samples at H = 256
+    out += [("grad_nw4_bf16", 16, 256, 5, False, 4097, G + "KT1_MT4"), ("grad_nw4_bf16", 172, 256, 20, True, 1025, G + "KS6_CACHED"),
+            ("grad_nw4_bf16", 105, 256, 8, True, 1025, G + "RUNTIME"), ("grad_mt2_bf16", 6, 256, 5, False, 4500, G + "KT1_MT2")]
+    return out
+
+
+# entries whose switch is read once per process: the case runs in a child process with it set (and so does its plan query in the table test)
+SWITCH_ENTRIES = {"grad_nodefer": "TMA_NO_DEFER_W2", "grad_nw4_bf16": "TMA_BF_NW4", "grad_mt2_bf16": "TMA_BF_MT2"}
+
+
+def bf_expected_geometry(ident, cont, B):
+    """(grid, block) of a bf16 gradient leaf, restated from the design: one block per CU, the policy net gets 144 (Box), 140 (eight-wave
+    Discrete kernel) or 136 of the 256; a block loops once there are more row groups than its net has blocks."""
+    groups = -(-B // (64 if "_MT4" in ident else 32))
+    cap_pi = 144 if cont else (140 if ident.endswith("KT1_MT4_W8") else 136)
+    return min(groups, cap_pi) + min(groups, 256 - cap_pi), (512 if "_W8" in ident else 256)
 
 
 CASES = (
@@ -119,7 +213,9 @@ CASES = (
     # TMA_NO_DEFER_W2: eight-wave half groups accumulate dW2 in the slabs; the Ant literal batch leaves small7 for the two-pass kernel
     + [("grad_nodefer", 16, 256, 5, False, 1000, "GRAD_F32_KT1_HALF_W8_SLAB"), ("grad_nodefer", 21, 256, 3, False, 256, "GRAD_F32_KT2_HALF_W8_SLAB"),
        ("grad_nodefer", 105, 256, 8, True, 256, "GRAD_F32_KT107_CACHED")]
-    + [("grad_bf16", 6, 256, 5, False, 1000, "GRAD_BF16"), ("grad_bf16x3", 6, 256, 5, False, 4096, "GRAD_BF16X3")]
+    + [("grad_bf16x3", 6, 256, 5, False, 4096, "GRAD_BF16X3")]
+    # ---- gradient: bf16 column-parallel kernels, every leaf
+    + _bf_grad_cases()
     # ---- forward: every launch_fwd leaf at the tile edges; the grid caps (wide: 4096 groups of 32 rows; generic: 8192 blocks)
     + [("fwd", D, H, A, cont, n, ident) for (D, H, A, cont, ident) in _FWD_SHAPES for n in _N_EDGES]
     + [("fwd_bf16", D, H, A, cont, n, ident) for (D, H, A, cont, ident) in _FWD_BF_SHAPES for n in _N_EDGES]
@@ -218,11 +314,15 @@ def _sd64(sd):
     return {k: v.detach().double() for k, v in sd.items()}
 
 
-def _rollout(sd, D, A, cont, T, N, seed=0):
-    """(T, N, ...) rollout buffers whose old log-probabilities keep every sample CLIP_MARGIN away from the clip boundary in float64."""
+def _rollout(sd, D, A, cont, T, N, seed=0, bf=False):
+    """(T, N, ...) rollout buffers whose old log-probabilities keep every sample CLIP_MARGIN away from the clip boundary in float64
+    (bf: in the float64 emulation of the bf16 forward, which is what the bf16 kernels' ratios are near)."""
     g, flat, act = _rows(D, A, cont, T * N, seed)
     with torch.no_grad():
-        _, lp64, _ = sb3_ref.evaluate_actions(_sd64(sd), flat.double(), act.double() if cont else act)
+        if bf:
+            lp64 = _logp(_emulated_forward64(sd, flat)[0], _sd64(sd), act, cont)
+        else:
+            _, lp64, _ = sb3_ref.evaluate_actions(_sd64(sd), flat.double(), act.double() if cont else act)
     old = (lp64 + 0.25 * torch.randn(T * N, generator=g, dtype=torch.float64)).float()
     for _ in range(10):
         near = (((torch.exp(lp64 - old.double()) - 1.0).abs() - 0.2).abs() < CLIP_MARGIN)
@@ -257,8 +357,19 @@ def _segment_errors(g, ref, cal):
     return {k: (float((g[k].double() - ref[k]).abs().max()), float((cal[k].double() - ref[k]).abs().max()), float(ref[k].abs().max())) for k in ref}
 
 
-def _rejects(errs):
-    return any(e > K * e32 + F * m for e, e32, m in errs.values())
+def _rejects(errs, k=K, f=F):
+    return any(e > k * e32 + f * m for e, e32, m in errs.values())
+
+
+def _emulated_grads(sd, rows, idx, dtype, hp):
+    """(grads in SB3 naming, stats) of the PPO loss over rows[idx] with the bf16 kernels' rounding points (test_bf16_gpu._emulated_grad), sums
+    and loss in `dtype` (float64: the reference of the bf16 gradient rows; float32: their calibration)."""
+    from test_bf16_gpu import _emulated_grad
+
+    if len(idx) == 0:
+        return {k: torch.zeros_like(v, dtype=dtype) for k, v in sd.items()}, None
+    x = {k: v[idx] for k, v in rows.items()}
+    return _emulated_grad(sd, x["obs"], x["actions"], x["old_lp"], x["adv"], x["ret"], hp, dtype)
 
 
 def _run_child(request, env):
@@ -272,46 +383,72 @@ def _run_child(request, env):
 
 @pytest.mark.parametrize("entry,D,H,A,cont,B,ident", _cases("grad"))
 def test_gradient_branch_against_float64(entry, D, H, A, cont, B, ident, monkeypatch, request, record_property):
+    """f32 rows: float64 / float32 torch autograd (see the module docstring).  bf16 rows (grad_*_bf16): reference = the emulation with the
+    kernel's bf16 rounding points in float64, calibration = the same emulation in float32; per segment (log_std included)
+    err_kernel <= K_BF_G * err_emu32 + F_BF_G * max|g64|, exact clip count, the four averaged statistics within S_BF_G, and the comparator
+    must reject the float64 emulation of the minibatch without its last row tile."""
     from test_ppo_gpu import _hip_grad
 
-    if entry == "grad_nodefer" and os.environ.get("TMA_NO_DEFER_W2") != "1":
-        return _run_child(request, {"TMA_NO_DEFER_W2": "1"})
-    if entry == "grad_nodz1":
+    dtype = "bf16x3" if entry == "grad_bf16x3" else ("bf16" if entry.endswith("_bf16") else "f32")
+    bf = dtype == "bf16"
+    kind = entry[:-len("_bf16")] if bf else entry
+    if entry in SWITCH_ENTRIES and os.environ.get(SWITCH_ENTRIES[entry]) != "1":
+        return _run_child(request, {SWITCH_ENTRIES[entry]: "1"})
+    if kind == "grad_nodz1":
         monkeypatch.setenv("TMA_NO_DZ1_CACHE", "1")
-    dtype = {"grad_bf16": "bf16", "grad_bf16x3": "bf16x3"}.get(entry, "f32")
-    hp = dict(HP, normalize_advantage=entry != "grad_noadv")
+    drop = B % 16 or 16  # rows of the last row tile
+    heavy = bf and bf_heavy_tile(B)
+    hp = dict(HP, normalize_advantage=kind != "grad_noadv" and not heavy)
     start = 3
     T = 16
     N = (start + B + T - 1) // T + 1
     pol, sd = _policy(D, H, A, cont, dtype)
-    bufs, rows = _rollout(sd, D, A, cont, T, N, seed=B % 7919)
+    # (bf16 rows: a data seed of their own, under which every dropped-tile reference overshoots K_BF_G, F_BF_G at least fourfold: checked on the CPU,
+    #  from the float64 and float32 emulations alone.  Under the f32 rows' seed the one row of the 16 x H x 5 Discrete minibatches' last tile is a
+    #  clipped sample with a return of 0.006: thirty times nothing)
+    bufs, rows = _rollout(sd, D, A, cont, T, N, seed=B % 7919 + (30000 if bf else 0), bf=bf)
     total = T * N
-    if entry == "grad_perm":
+    if kind == "grad_perm":
         from three_mlagents_amd import _lib
 
         perm_np = np.zeros(total, dtype=np.int64)
         _lib.check(_lib.lib().tma_ppo_permutation(77, 3, total, perm_np.ctypes.data_as(C.c_void_p)))
         perm = torch.from_numpy(perm_np)
-        grad, st, _ = _hip_grad(pol, bufs, T, N, None, start, B, hp, perm=(77, 3))
     else:
         perm = torch.randperm(total, generator=torch.Generator().manual_seed(B))
+    idx = perm[start:start + B]
+    if heavy:  # the last row tile's advantages and returns times BF_HEAVY (flat row f lies at [f % T, f // T] of the buffers)
+        last = idx[B - drop:]
+        for k in ("adv", "ret"):
+            rows[k][last] *= BF_HEAVY
+            bufs[k][last % T, last // T] *= BF_HEAVY
+    if kind == "grad_perm":
+        grad, st, _ = _hip_grad(pol, bufs, T, N, None, start, B, hp, perm=(77, 3))
+    else:
         grad, st, _ = _hip_grad(pol, bufs, T, N, perm, start, B, hp)
     got = _last_dispatch()[1]
     assert got == expected_value(ident), (ident, _name(got))
-    assert planned(pol.dims, "grad", B)[:2] == (0, got)
-    idx = perm[start:start + B]
+    plan = planned(pol.dims, "grad", B)
+    assert plan[:2] == (0, got)
     g = pol.named_from_flat(grad)
-    if dtype != "f32":  # (numerics: test_bf16_gpu.py / test_split3_gpu.py)
+    if dtype == "bf16x3":  # (numerics: test_split3_gpu.py)
         assert all(torch.isfinite(v).all() for v in g.values()) and st[5] == B
         return
-    g64, s64 = _grads(sd, rows, idx, torch.float64, hp)
-    g32, _ = _grads(sd, rows, idx, torch.float32, hp)
+    if bf:
+        assert plan[2:4] == bf_expected_geometry(ident, cont, B) and 0 <= plan[4] <= 160 * 1024, plan
+        k, f, s_tol, ref_fn = K_BF_G, F_BF_G, S_BF_G, _emulated_grads
+    else:
+        k, f, s_tol, ref_fn = K, F, 2e-6, _grads
+    g64, s64 = ref_fn(sd, rows, idx, torch.float64, hp)
+    g32, _ = ref_fn(sd, rows, idx, torch.float32, hp)
+    assert not bf or set(g) == set(g64)
     errs = _segment_errors(g, g64, g32)
-    drop = B % 16 or 16
-    gdrop, _ = _grads(sd, rows, idx[:B - drop], torch.float64, hp)
+    gdrop, _ = ref_fn(sd, rows, idx[:B - drop], torch.float64, hp)
     errs_drop = _segment_errors(gdrop, g64, g32)
-    budget = max(e / (K * e32 + F * m) if (e32 or m) else (0.0 if e == 0 else math.inf) for e, e32, m in errs.values())
-    record_property("grad_errs", repr({"budget": budget, "errs": errs, "drop": {k: v[0] for k, v in errs_drop.items()}}))
+    use = lambda e, e32, m: e / (k * e32 + f * m) if (e32 or m) else (0.0 if e == 0 else math.inf)  # noqa: E731
+    budget = max(use(*v) for v in errs.values())
+    record_property("grad_errs", repr({"budget": budget, "drop_overshoot": max(use(*v) for v in errs_drop.values()), "errs": errs,
+                                       "drop": {key: v[0] for key, v in errs_drop.items()}}))
     # statistics: sums of {policy_loss, value_sq_err, entropy, approx_kl, clipped, n} (the last two exact); no optimizer step on this workspace
     n = st[5]
     stats = ((st[0] / n, s64["policy_loss"], "policy_loss"), (st[1] / n, s64["value_loss"], "value_loss"),
@@ -320,11 +457,11 @@ def test_gradient_branch_against_float64(entry, D, H, A, cont, B, ident, monkeyp
     assert n == B
     assert st[4] == round(s64["clip_fraction"] * B), (st[4], s64["clip_fraction"] * B)
     for got_v, ref_v, what in stats:
-        assert abs(got_v - ref_v) <= 2e-6 * max(1.0, abs(ref_v)), (what, got_v, ref_v)
+        assert abs(got_v - ref_v) <= s_tol * max(1.0, abs(ref_v)), (what, got_v, ref_v)
     assert st[6] == 0.0 and st[7] == 0.0
-    bad = {k: v for k, v in errs.items() if v[0] > K * v[1] + F * v[2]}
+    bad = {key: v for key, v in errs.items() if v[0] > k * v[1] + f * v[2]}
     assert not bad, bad
-    assert _rejects(errs_drop), ("the comparator does not see the last row tile dropped", errs_drop)
+    assert _rejects(errs_drop, k, f), ("the comparator does not see the last row tile dropped", errs_drop)
 
 
 def _emulated_forward64(sd, obs):

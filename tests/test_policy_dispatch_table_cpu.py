@@ -61,18 +61,19 @@ def _case_dims(entry, D, H, A, cont):
     return _lib.PolicyDims(D, H, A, int(cont), mfma, -1)
 
 
-def check_planned_cases(want_nodefer):
+def check_planned_cases(switch_entry=None):
     """tma_debug_plan_dispatch gives every CASES row its id (the table was verified on hardware through tma_debug_last_dispatch), a grid of at
-    least one block and at most 160 KB of LDS.  The grad_nodefer rows alone when want_nodefer: TMA_NO_DEFER_W2 is read once per process."""
+    least one block and at most 160 KB of LDS; a bf16 gradient row the grid (n_pi + n_vf) and block of its leaf as well.  The rows of one
+    SWITCH_ENTRIES entry alone when switch_entry names it: their switch is read once per process, so the caller is a child process with it set."""
     import torch
 
     import test_policy_dispatch_gpu as t
 
     n = 0
     for entry, D, H, A, cont, B, ident in t.CASES:
-        if (entry == "grad_nodefer") != want_nodefer:
+        if (entry != switch_entry) if switch_entry else (entry in t.SWITCH_ENTRIES):
             continue
-        if entry == "grad_nodz1":
+        if entry.startswith("grad_nodz1"):
             os.environ["TMA_NO_DZ1_CACHE"] = "1"
         try:
             rc, got, grid, block, lds = t.planned(_case_dims(entry, D, H, A, cont), t._entry_which(entry), B)
@@ -80,23 +81,55 @@ def check_planned_cases(want_nodefer):
             os.environ.pop("TMA_NO_DZ1_CACHE", None)
         case = t._case_id((entry, D, H, A, cont, B, ident))
         assert rc == 0 and got == t.expected_value(ident), (case, rc, t._name(got))
-        inner = ident in ("GRAD_H64_SMALL", "GRAD_H64", "GRAD_BF16", "GRAD_BF16X3")  # geometry picked by the family's own launcher: LDS -1
+        inner = ident in ("GRAD_H64_SMALL", "GRAD_H64", "GRAD_BF16X3")  # geometry picked by the family's own launcher: LDS -1
         assert grid >= 1 and block >= 64 and block % 64 == 0 and (lds == -1 if inner else 0 <= lds <= 160 * 1024), (case, grid, block, lds)
+        if ident.startswith("GRAD_BF16_"):
+            assert entry.endswith("_bf16") and block in (256, 512) and (grid, block) == t.bf_expected_geometry(ident, cont, B), (case, grid, block)
         n += 1
-    assert n == (3 if want_nodefer else len(t.CASES) - 3)
+    rows = {"grad_nodefer": 3, "grad_nw4_bf16": 3, "grad_mt2_bf16": 1}
+    assert sorted(rows) == sorted(t.SWITCH_ENTRIES)
+    assert n == (rows[switch_entry] if switch_entry else len(t.CASES) - sum(rows.values()))
     assert not torch.cuda.is_initialized()
 
 
 def test_plan_query_gives_every_case_its_id():
-    check_planned_cases(False)
+    check_planned_cases()
+
+
+def _planned_in_child(entry):
+    import subprocess
+
+    import test_policy_dispatch_gpu as t
+
+    code = f"import sys; sys.path[:0] = [{ROOT!r}, {HERE!r}]; import test_policy_dispatch_table_cpu as m; m.check_planned_cases({entry!r})"
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **{t.SWITCH_ENTRIES[entry]: "1"}), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
 
 
 def test_plan_query_gives_the_no_defer_cases_their_ids_in_a_child_process():
-    import subprocess
+    _planned_in_child("grad_nodefer")
 
-    code = f"import sys; sys.path[:0] = [{ROOT!r}, {HERE!r}]; import test_policy_dispatch_table_cpu as m; m.check_planned_cases(True)"
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TMA_NO_DEFER_W2="1"), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+
+def test_plan_query_gives_the_bf16_four_wave_cases_their_ids_in_a_child_process():
+    _planned_in_child("grad_nw4_bf16")
+
+
+def test_plan_query_gives_the_bf16_32_row_group_case_its_id_in_a_child_process():
+    _planned_in_child("grad_mt2_bf16")
+
+
+def test_every_bf16_gradient_leaf_has_a_case_at_every_width_and_head_it_takes():
+    import test_policy_dispatch_gpu as t
+
+    have = {(ident[len("GRAD_BF16_"):], H, cont) for entry, D, H, A, cont, B, ident in t.CASES if ident.startswith("GRAD_BF16_")}
+    both, widths = (False, True), (128, 192, 256)
+    want = {(leaf, H, c) for leaf in ("KT1_MT2", "KT2_MT2", "KS2_CACHED", "KS6_CACHED", "RUNTIME") for H in widths for c in both}
+    want |= {(leaf, H, c) for leaf in ("KT1_MT4", "KT2_MT4") for H in (128, 256) for c in both}  # (H = 192 only has 32-row groups)
+    want |= {("KT1_MT4_W8", 256, False)} | {(leaf, 256, True) for leaf in ("KS6_W8_CACHED", "KS6_W8_RECOMPUTE", "KS4_W8_CACHED", "KS4_W8_RECOMPUTE")}
+    want |= {("KS2_RECOMPUTE", 256, False), ("KS6_RECOMPUTE", 256, False)}
+    assert want <= have, sorted(want - have)
+    # every bf16 gradient row is compared (the dropped-tile rejection included): none of them is a dispatch-only entry
+    assert all(e.endswith("_bf16") for e, D, H, A, cont, B, ident in t.CASES if ident.startswith("GRAD_BF16_"))
 
 
 def test_plan_query_refuses_what_the_real_calls_refuse():

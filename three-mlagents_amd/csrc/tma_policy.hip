@@ -2365,13 +2365,19 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
 }
 
 // The dispatchers' environment switches, each read where the parent dispatchers read it: DispatchSwitches says which once per process and which on
-// each call.  Only the f32 column-parallel shapes read more than the gradient's two cached ones (for_grad = false: tma_ppo_adam_step_local)
+// each call.  Only the column-parallel shapes (f32, bf16) read more than the gradient's two cached ones (for_grad = false: tma_ppo_adam_step_local)
 static DispatchSwitches read_switches(const PLayout &L, int64_t count, bool for_grad) {
     DispatchSwitches w{};
     if (for_grad) {
         static const bool force_wide = getenv("TMA_FORCE_WIDE") != nullptr;
         static const int bf_debug = getenv("TMA_BF_DEBUG") ? atoi(getenv("TMA_BF_DEBUG")) : 0;
         w.force_wide = force_wide, w.bf_debug = bf_debug;
+        if (L.bf16) {  // plan_grad_bf
+            static const bool bf_mt2 = getenv("TMA_BF_MT2") != nullptr, bf_nw4 = getenv("TMA_BF_NW4") != nullptr;
+            static const int bf_npi = getenv("TMA_BF_NPI") ? atoi(getenv("TMA_BF_NPI")) : 0;
+            w.bf_mt2 = bf_mt2, w.bf_nw4 = bf_nw4, w.bf_npi = bf_npi;
+            w.no_dz1 = getenv("TMA_NO_DZ1_CACHE") != nullptr;  // (test hook for the recompute pass)
+        }
     }
     if (!grad_wide_f32_shape(L)) return w;
     if (!for_grad) {
@@ -2619,7 +2625,7 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
         if ((int64_t)rb->T * rb->N * L.D >= (int64_t)1 << 31)  // (its observation gather indexes the buffer with 32-bit arithmetic)
             return fail(TMA_ERR_INVALID, "bf16 update: T * N * obs_dim = %lld exceeds 2^31", (long long)((int64_t)rb->T * rb->N * L.D));
         GradTimer timer(s);
-        lrc = tma_launch_grad_wide_bf(params, L, R, M, hpar, ws_adv, slabs, slots, ws, &n_pi, &n_vf, s);
+        lrc = tma_launch_grad_wide_bf(params, L, R, M, hpar, ws_adv, slabs, slots, ws, p.bf, s);
     } break;
     case GradFamily::BF16X3: {
         GradTimer timer(s);

@@ -1,7 +1,7 @@
 // tma_policy_plan.h -- WHICH kernel specialisation the policy's three dispatchers run for a shape, and with what launch geometry: plain structs
 // and pure host functions (no HIP call, no global, no environment read), so that the selection is checkable without a GPU
-// (tma_debug_plan_dispatch).  The launchers of tma_policy.hip validate, call plan_*, record plan.id and launch what the plan says: every
-// threshold and cap of the selection is written here, once.
+// (tma_debug_plan_dispatch).  The launchers of tma_policy.hip (and tma_bf16.hip's, for plan_grad_bf) validate, call plan_*, record plan.id and
+// launch what the plan says: every threshold and cap of the selection is written here, once.
 // Included inside namespace tma by tma_policy.hip, after tma_ppo_types.h, W2_DEFER_ROWS and tma_wide_bf16.h.
 #pragma once
 
@@ -15,6 +15,10 @@ struct DispatchSwitches {
     bool no_dz1;          // TMA_NO_DZ1_CACHE: on each call.  The two-pass kernels recompute the chain
     bool split3;          // tma_split3_eligible(L, count), which reads TMA_NO_SPLIT3: on each call
     int bf_debug;         // TMA_BF_DEBUG: once per process.  Phase mask of the bf16 wide kernel (HParams::debug)
+    // the bf16 column-parallel gradient (plan_grad_bf), which also reads no_dz1
+    bool bf_mt2;          // TMA_BF_MT2: once per process.  Development switch: 32-row groups throughout
+    bool bf_nw4;          // TMA_BF_NW4: once per process.  A/B switch: every shape on four waves (the Ant width then takes the runtime-width kernel)
+    int bf_npi;           // TMA_BF_NPI: once per process.  Development switch: policy-net block count (0: the measured split)
 };
 
 constexpr int LDS_LIMIT = 160 * 1024;         // dynamic LDS of one workgroup: what needs more is refused
@@ -88,6 +92,51 @@ inline FwdPlan plan_fwd(const PLayout &L, int64_t n, int mode) {
     return p;
 }
 
+// ---- minibatch gradient, bf16 column-parallel kernels (tma_bf16.hip launches what this returns).  It reads bf_mt2, bf_nw4, bf_npi and no_dz1.
+constexpr int64_t BF_MT4_FROM = 4096;  // 64-row groups beyond this many samples
+inline GradBfPlan plan_grad_bf(const PLayout &L, int64_t count, const DispatchSwitches &sw) {
+    GradBfPlan p{};
+    // observation width classes: <= 16, <= 32: dW1 in registers (one / two k-tiles); 33..64, 161..192 (Crawler's 172) and 97..128 with a Box head at
+    // H = 256 (the reference's ant task): two passes with 2 / 6 / 4 layer-1 k-steps; any other width: runtime width, dW1 in place in the slab
+    const int variant = L.D <= 16 ? 0 : (L.D <= 32 ? 1 : (L.D <= 64 ? 2 : ((L.D > 160 && L.D <= 192) ? 3 : ((L.D > 96 && L.D <= 128 && L.cont && L.H == 256) ? 5 : 4))));
+    // observations of up to 32 floats: 64-row groups (half the weight bytes, barriers and latency chains per sample); wider ones keep
+    // 32-row groups (their observation images would not fit next to 64-row activation images).  Minibatches too small to give every block a
+    // 64-row group take 32-row groups as well: twice the workgroups on a launch that is all latency
+    p.mt = (variant <= 1 && !sw.bf_mt2 && L.H != 192 && count > BF_MT4_FROM) ? 4 : 2;  // (H = 192: three column tiles per wave do not split in halves)
+    const int smemw = grad_wide_bf_smem_bytes(L.D, L.H, p.mt);
+    const int64_t groups = ceil_div(count, 16 * p.mt);
+    // eight waves (two per SIMD, 32 columns each): 64-row groups of the Discrete layouts with observations of up to 16 floats at H = 256
+    // (GridWorld, Push, Ball3D, WallJump), and the two-pass Box layouts of the Ant and Crawler widths at H = 256
+    const bool eight_kt1 = !sw.bf_nw4 && p.mt == 4 && variant == 0 && !L.cont && L.H == 256;
+    const bool eight_ks = !sw.bf_nw4 && (variant == 5 || (variant == 3 && L.cont && L.H == 256));
+    // 256 blocks = one per CU.  A policy-net row group costs 1.15-1.3x a value-net one (the loss), so the policy net gets 136 to 144 of the
+    // blocks (the Categorical loss is cheaper than the DiagGaussian one; the eight-wave kernel shares a tile's loss between two waves: swept
+    // 124 .. 160, best 136 .. 140); with fewer row groups than that, one block per group
+    const int cap_pi = sw.bf_npi > 0 ? sw.bf_npi : (L.cont ? 144 : (eight_kt1 ? 140 : 136)), cap_vf = 256 - cap_pi;
+    p.n_pi = (int)(groups < cap_pi ? groups : cap_pi), p.n_vf = (int)(groups < cap_vf ? groups : cap_vf);
+    p.waves = (eight_kt1 || eight_ks) ? 8 : 4, p.block = 64 * p.waves;
+    // two-pass layouts: minibatches that fit the dz1 cache take PASS 0 (which leaves dz1 there) + PASS 2 (dW1 from the cache) instead of
+    // PASS 0 + PASS 1 (dW1 from a recomputed forward / backward chain); the results are bit-identical
+    const bool cached = bf_two_pass(L) && count <= DZ1_CAP && !sw.no_dz1;
+    if (variant == 4 || (variant == 5 && sw.bf_nw4)) {
+        p.id = TMA_DISPATCH_GRAD_BF16_RUNTIME, p.pass = BfPass::Single, p.zero_w1 = true, p.lds = smemw;
+    } else if (variant <= 1) {
+        p.kt1c = variant + 1, p.ks1c = 1, p.pass = BfPass::Single;
+        p.id = eight_kt1 ? TMA_DISPATCH_GRAD_BF16_KT1_MT4_W8
+                         : (variant == 0 ? (p.mt == 4 ? TMA_DISPATCH_GRAD_BF16_KT1_MT4 : TMA_DISPATCH_GRAD_BF16_KT1_MT2)
+                                         : (p.mt == 4 ? TMA_DISPATCH_GRAD_BF16_KT2_MT4 : TMA_DISPATCH_GRAD_BF16_KT2_MT2));
+        p.lds = eight_kt1 ? smemw + (L.H / 32) * 1024 + 12 * 4 * 5 * 8 : smemw;  // + the head fragments + the statistics slots of the row-lane loss (64 in all)
+    } else {
+        p.ks1c = variant == 2 ? 2 : (variant == 3 ? 6 : 4), p.pass = cached ? BfPass::Cached : BfPass::Recompute;
+        p.id = variant == 2 ? (cached ? TMA_DISPATCH_GRAD_BF16_KS2_CACHED : TMA_DISPATCH_GRAD_BF16_KS2_RECOMPUTE)
+             : variant == 5 ? (cached ? TMA_DISPATCH_GRAD_BF16_KS4_W8_CACHED : TMA_DISPATCH_GRAD_BF16_KS4_W8_RECOMPUTE)
+             : eight_ks     ? (cached ? TMA_DISPATCH_GRAD_BF16_KS6_W8_CACHED : TMA_DISPATCH_GRAD_BF16_KS6_W8_RECOMPUTE)
+                            : (cached ? TMA_DISPATCH_GRAD_BF16_KS6_CACHED : TMA_DISPATCH_GRAD_BF16_KS6_RECOMPUTE);
+        p.lds = eight_ks ? smemw + 4 * 4 * 5 * 8 : smemw;  // + the statistics of four more waves
+    }
+    return p;
+}
+
 // ---- minibatch gradient
 enum class GradFamily { Refused, H64Small, H64, BF16, BF16X3, WideF32, Generic };
 enum class GradReduce { None, Slab, WideSmall };
@@ -106,10 +155,11 @@ struct GradPlan {
     bool dz1_cached;  // two passes: the second takes dz1 from the workspace cache instead of recomputing the chain
     int n_pi, n_vf;   // blocks = slabs of the policy net; the value net's blocks use the first n_vf of them
     int64_t groups;
-    // WideF32 (the first dominant launch) and Generic: the launch.  lds = -1: the family's own launcher picks the dominant kernel's geometry
-    // (tma_h64.hip, tma_bf16.hip, tma_split3.hip) and grid / block are the slab reduction's that follows.  Refused: lds = one wave's tile
+    // WideF32, BF16 (the first dominant launch) and Generic: the launch.  lds = -1: the family's own launcher picks the dominant kernel's geometry
+    // (tma_h64.hip, tma_split3.hip) and grid / block are the slab reduction's that follows.  Refused: lds = one wave's tile
     int64_t grid;
     int block, lds;
+    GradBfPlan bf;  // BF16: what tma_launch_grad_wide_bf launches
     GradReduce reduce;
     int32_t id;  // TMA_DISPATCH_GRAD_* [| TMA_DISPATCH_GRID_CAPPED]; NONE when refused
 };
@@ -129,7 +179,9 @@ inline GradPlan plan_grad(const PLayout &L, bool cont, int64_t count, bool prepa
         p.family = tiles <= H64_BLOCKS ? GradFamily::H64Small : GradFamily::H64;
         p.id = tiles <= H64_BLOCKS ? TMA_DISPATCH_GRAD_H64_SMALL : TMA_DISPATCH_GRAD_H64;
     } else if (L.bf16) {  // column-parallel bf16-MFMA kernel (tma_bf16.hip)
-        p.family = GradFamily::BF16, p.id = TMA_DISPATCH_GRAD_BF16;
+        p.family = GradFamily::BF16, p.bf = plan_grad_bf(L, count, sw);
+        p.id = p.bf.id, p.n_pi = p.bf.n_pi, p.n_vf = p.bf.n_vf;
+        p.grid = p.n_pi + p.n_vf, p.block = p.bf.block, p.lds = p.bf.lds;  // (of every launch of the leaf)
     } else if (wide_f32 && sw.split3) {  // mfma_dtype = 2: the same update on the bf16 MFMA, every operand as three bf16 terms
         p.family = GradFamily::BF16X3, p.id = TMA_DISPATCH_GRAD_BF16X3;
     } else if (wide_f32) {  // column-parallel register-accumulating kernel

@@ -36,6 +36,20 @@ static inline int64_t dz1_cache_bytes(const PLayout &L) {  // both nets; bf16 im
 static inline int rec_floats(const PLayout &L) { return (L.img_pi >= 0 && L.D <= 8) ? ((L.D + 3) & ~3) + 4 : 0; }
 static inline int slab_cap(const PLayout &L) { return (L.bf16 || L.fr_pi >= 0) ? BF_SLABS : H64_BLOCKS; }  // partial-gradient slabs in the workspace
 
+// What the bf16 column-parallel gradient launches for a shape (plan_grad_bf in tma_policy_plan.h decides, tma_launch_grad_wide_bf launches):
+// ppo_grad_wide_bf_kernel<cont, H / 64, mt, kt1c, ks1c, PASS, waves>
+enum class BfPass { Single, Cached, Recompute };  // one launch; PASS 0 + PASS 2 (dW1 from the dz1 cache); PASS 0 + PASS 1 (dW1 from a recomputed chain)
+struct GradBfPlan {
+    int32_t id;      // TMA_DISPATCH_GRAD_BF16_*
+    int mt;          // 16-row tiles per row group: 2 or 4
+    int waves;       // 4 (64 columns each) or 8 (32 columns each)
+    int kt1c, ks1c;  // layer-1 k-tiles of dW1 in registers (single pass) / layer-1 k-steps (two passes); both 0: runtime width
+    BfPass pass;
+    int n_pi, n_vf;  // blocks = slabs of the policy net; the value net's blocks use the first n_vf of them
+    int block, lds;  // threads, dynamic LDS bytes of every launch
+    bool zero_w1;    // runtime width: dW1 accumulates in place in the slabs, behind slab_zero_w1_kernel
+};
+
 struct Minibatch {
     const int64_t *indices;  // optional explicit flat (env-major: f = i*T + t) indices
     uint32_t perm_seed, perm_epoch;
@@ -276,9 +290,10 @@ int tma_launch_epoch_h256p(float *params, const tma::PLayout &L, const tma::Roll
                            const double *adv_part, int adv_stride, int64_t total, int64_t batch_size, float *exp_avg, float *exp_avg_sq,
                            int64_t first_step, double lr, double beta1, double beta2, double eps, double max_grad_norm, char *ws, hipStream_t s);
 
-// tma_bf16.hip: the column-parallel bf16-MFMA gradient kernel (hidden 128 / 192 / 256); `ws` is the update workspace (dz1 cache)
+// tma_bf16.hip: the column-parallel bf16-MFMA gradient kernel (hidden 128 / 192 / 256); `ws` is the update workspace (dz1 cache).  It launches
+// what `plan` says (plan_grad_bf, tma_policy_plan.h) and decides nothing itself
 int tma_launch_grad_wide_bf(const float *params, const tma::PLayout &L, const tma::Rollout &R, const tma::Minibatch &M, const tma::HParams &hpar,
-                            const float *ws_adv, float *slabs, double *slots, char *ws, int *n_pi_out, int *n_vf_out, hipStream_t s);
+                            const float *ws_adv, float *slabs, double *slots, char *ws, const tma::GradBfPlan &plan, hipStream_t s);
 // tma_bf16.hip: the three-term bf16 split of the 256-wide f32 update (mfma_dtype = 2; tma_split3.h) and the rebuild of its weight planes
 int tma_launch_grad_split3(const float *params, const tma::PLayout &L, const tma::Rollout &R, const tma::Minibatch &M, const tma::HParams &hpar, float *slabs,
                            double *slots, int *n_pi_out, int *n_vf_out, hipStream_t s);
