@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 216
+#define TMA_VERSION 217
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -571,6 +571,62 @@ int tma_a2c_iterations_local(tma_env *env, float *params, const tma_policy_dims 
                              double max_grad_norm, void *workspace, void *stream);
 /* tma_ppo_stats_fold for an A2C update: out8 = {sum of -(adv * log_prob), value_sq_err, entropy, 0, 0, n_samples, grad norm, clip coefficient} */
 int tma_a2c_stats_fold(const void *staging_host, double *out8_host);
+
+/* ---- VecNormalize (ABI 217): SB3's VecNormalize wrapper -- running mean / variance of the observations and of the per-env discounted
+ *      returns, normalisation and clipping of observations and rewards -- on the device.  SB3 users put it around the vector env for tasks with
+ *      unbounded observations and wide return ranges; the reference's own runs do not use it, so nothing selects it unless the caller does.
+ * The handle owns, in device memory, all float64: obs mean[D], var[D], count; return mean, var, count; returns[N]; and float32 copies of the last
+ * step's raw observations [N][D] and rewards [N].  Device memory is allocated on the handle's first use, so tma_vecnorm_create and every argument
+ * check below answer without a GPU; that first use -- the first reset, step, rollout or statistics call on the handle -- allocates, fills the
+ * buffers with synchronous copies and drains the device ONCE (hipDeviceSynchronize), later calls wait for nothing.  Initial statistics are RunningMeanStd(epsilon = 1e-4)'s: mean 0, var 1, count 1e-4.
+ * A batch's moments are float64, two-pass (mean, then the sum of squared distances from it; never E[x^2] - E[x]^2), summed in an order that
+ * (N, D) alone fixes -- no float atomics, run-to-run bit-identical -- and merged into the running ones by exactly
+ *     delta = bm - mean;  tot = count + n;  mean' = mean + delta * n / tot;
+ *     M2 = var * count + bv * n + delta * delta * count * n / tot;  var' = M2 / tot;  count' = tot
+ * normalize_obs(o) = float(clip((double(o) - mean) / sqrt(var + epsilon), -clip_obs, clip_obs)), normalize_reward(r) =
+ * float(clip(double(r) / sqrt(ret_var + epsilon), -clip_reward, clip_reward)): IEEE subtract, square root and divide in float64.
+ * Up to TMA_VECNORM_ONE_LAUNCH_MAX envs a training step is ONE launch of one workgroup; beyond it two (per-workgroup partial moments, then a
+ * fixed-order fold every workgroup repeats in front of its own rows).  All calls on one handle must be ordered on one stream.
+ * Refused with TMA_ERR_INVALID before any HIP call: NULL handles or planes, D <= 0 or > TMA_VECNORM_MAX_DIM, N <= 0, clips or epsilon that are
+ * not positive, gamma outside [0, 1], a row count or observation width that differs from the handle's. */
+#define TMA_VECNORM_ONE_LAUNCH_MAX 256
+#define TMA_VECNORM_MAX_DIM 1024
+typedef struct tma_vecnorm tma_vecnorm;
+int tma_vecnorm_create(int D, int64_t N, int norm_obs, int norm_reward, double clip_obs, double clip_reward, double gamma, double epsilon, int device,
+                       tma_vecnorm **out);
+int tma_vecnorm_destroy(tma_vecnorm *h);
+/* norm_obs / norm_reward may change after construction (SB3 exposes them as attributes) */
+int tma_vecnorm_set_flags(tma_vecnorm *h, int norm_obs, int norm_reward);
+/* VecNormalize.reset(): returns = 0; training && norm_obs: the observation statistics take obs[n][D]; obs is normalised in place.  n == N. */
+int tma_vecnorm_reset(tma_vecnorm *h, float *obs, int64_t n, int training, void *stream);
+/* VecNormalize.step_wait() on the outputs of one vector step, in place, in SB3's order: (1) training && norm_obs: the observation statistics take
+ * obs; (2) obs is normalised; (3) training: returns = returns * gamma + rewards and the return statistics take returns (whether or not norm_reward
+ * is set); (4) rewards are normalised; (5) where terminated | truncated, terminal_obs (may be NULL) is normalised with the statistics of (1) --
+ * terminal observations never enter them; (6) returns = 0 where terminated | truncated.  The raw obs and rewards are kept (tma_vecnorm_get_original). */
+int tma_vecnorm_step(tma_vecnorm *h, float *obs, float *rewards, float *terminal_obs, const uint8_t *terminated, const uint8_t *truncated, int64_t n,
+                     int training, void *stream);
+/* stateless maps with the current statistics over any n rows; in and out are device memory and may be the same; identity where the flag is off */
+int tma_vecnorm_normalize_obs(tma_vecnorm *h, const float *in, float *out, int64_t n, void *stream);
+int tma_vecnorm_unnormalize_obs(tma_vecnorm *h, const float *in, float *out, int64_t n, void *stream);     /* float(double(o) * sqrt(var + eps) + mean) */
+int tma_vecnorm_normalize_reward(tma_vecnorm *h, const float *in, float *out, int64_t n, void *stream);
+int tma_vecnorm_unnormalize_reward(tma_vecnorm *h, const float *in, float *out, int64_t n, void *stream);  /* float(double(r) * sqrt(ret_var + eps)) */
+/* statistics to / from HOST float64: obs_mean[D], obs_var[D], scalars4 = {obs count, return mean, return var, return count}.  Synchronise `stream`. */
+int tma_vecnorm_get_stats(tma_vecnorm *h, double *obs_mean_host, double *obs_var_host, double *scalars4_host, void *stream);
+int tma_vecnorm_set_stats(tma_vecnorm *h, const double *obs_mean_host, const double *obs_var_host, const double *scalars4_host, void *stream);
+/* sync_envs_normalization: dst's statistics = src's, device to device, ordered on `stream` (same D) */
+int tma_vecnorm_copy_stats(tma_vecnorm *dst, tma_vecnorm *src, void *stream);
+/* the per-env discounted returns to HOST float64[N] (synchronises `stream`) */
+int tma_vecnorm_get_returns(tma_vecnorm *h, double *returns_host, void *stream);
+/* get_original_obs / get_original_reward: the raw values of the last reset / step into DEVICE memory [N][D] / [N]; either may be NULL */
+int tma_vecnorm_get_original(tma_vecnorm *h, float *obs_out, float *rewards_out, void *stream);
+/* tma_rollout_collect's per-step composition (policy forward, env step, timeout bootstrap; both its K == 1 form and its terminal-observation
+ * window) with one tma_vecnorm_step behind every tma_env_step, BEFORE the bootstrap that reads that step's terminal_obs and rewards: SB3 adds
+ * gamma * V(normalised terminal observation) to the normalised reward.  The buffers end up holding normalised observations and rewards.
+ * b->obs slot t_begin must hold NORMALISED observations (tma_vecnorm_reset, or the previous call's last slot).  training = 0 freezes the
+ * statistics (evaluation).  The fused chunk kernels are not used: every shape runs launch by launch. */
+int tma_rollout_collect_norm(tma_env *env, tma_vecnorm *vn, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b, int t_begin,
+                             int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, uint32_t env_offset, double gamma, int compute_last_values,
+                             int deterministic, int training, void *stream);
 
 #ifdef __cplusplus
 }

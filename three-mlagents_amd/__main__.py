@@ -14,7 +14,8 @@ VERBS = {
     "inspect": [(("task",), {})],
     "train": [(("task",), {}), (("--algorithm", "-a"), {}), (("--timesteps", "-t"), {"type": int}), (("--seed",), {"type": int, "default": 1}),
               (("--n-envs",), {"type": int}), (("--eval-episodes",), {"type": int}), (("--eval-freq",), {"type": int, "default": 10_000}),
-              (("--run-name",), {}), (("--quiet",), {"action": "store_true"})],
+              (("--run-name",), {}), (("--quiet",), {"action": "store_true"}),
+              (("--normalize",), {"action": "store_true"})],  # engine-only: VecNormalize around the training and evaluation vectors
     "evaluate": [(("task",), {}), (("model",), {}), (("--episodes",), {"type": int}), (("--seed",), {"type": int, "default": 10_001}),
                  (("--stochastic",), {"action": "store_true"})],
 }
@@ -43,7 +44,7 @@ def run(argv=None) -> dict | list:
         return spaces
     if a.command == "train":
         cfg = harness.TrainConfig(a.task, a.timesteps, a.algorithm, a.seed, a.n_envs, a.eval_episodes, a.eval_freq, run_name=a.run_name,
-                                  verbose=int(not a.quiet))
+                                  verbose=int(not a.quiet), normalize=bool(a.normalize))
         return dataclasses.asdict(harness.train_task(cfg))
     return harness.evaluate_model(a.task, a.model, episodes=a.episodes, deterministic=not a.stochastic, seed=a.seed)
 

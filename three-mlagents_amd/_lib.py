@@ -15,6 +15,7 @@ TMA_OK, TMA_ERR_INVALID, TMA_ERR_UNKNOWN_TASK, TMA_ERR_HIP = 0, 1, 2, 3
 ACT_I32, ACT_I64, ACT_F32 = 0, 1, 2
 EP_STRIDE = 1 << 20
 EV_SCRATCH_DOUBLES = 1536  # include/tma.h TMA_EV_SCRATCH_DOUBLES
+VECNORM_ONE_LAUNCH_MAX = 256  # include/tma.h TMA_VECNORM_ONE_LAUNCH_MAX
 
 _vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_double
 
@@ -143,6 +144,21 @@ SIGNATURES = {
                                         C.POINTER(A2CHParams), _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp]),
     "tma_a2c_stats_fold": (_i32, [_vp, C.POINTER(_f64)]),
     "tma_rollout_collect": (_i32, [_vp, _vp, _pd, C.POINTER(RolloutBuffers), _i32, _i32, _i32, _u32, _u32, _u32, _f64, _i32, _i32, _vp]),
+    "tma_vecnorm_create": (_i32, [_i32, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _i32, C.POINTER(_vp)]),
+    "tma_vecnorm_destroy": (_i32, [_vp]),
+    "tma_vecnorm_set_flags": (_i32, [_vp, _i32, _i32]),
+    "tma_vecnorm_reset": (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    "tma_vecnorm_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "tma_vecnorm_normalize_obs": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "tma_vecnorm_unnormalize_obs": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "tma_vecnorm_normalize_reward": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "tma_vecnorm_unnormalize_reward": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "tma_vecnorm_get_stats": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "tma_vecnorm_set_stats": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "tma_vecnorm_copy_stats": (_i32, [_vp, _vp, _vp]),
+    "tma_vecnorm_get_returns": (_i32, [_vp, _vp, _vp]),
+    "tma_vecnorm_get_original": (_i32, [_vp, _vp, _vp, _vp]),
+    "tma_rollout_collect_norm": (_i32, [_vp, _vp, _vp, _pd, C.POINTER(RolloutBuffers), _i32, _i32, _i32, _u32, _u32, _u32, _f64, _i32, _i32, _i32, _vp]),
 }
 
 # tma_allreduce_fn (include/tma.h): int (*)(void *ctx, float *buffer, int64_t count)

@@ -270,7 +270,19 @@ class EvalCallback(BaseCallback):
         model = self.model
         side = model.side_stream() if hasattr(model, "side_stream") and getattr(self.eval_env, "device", None) == getattr(model, "device", None) else None
         main = torch.cuda.current_stream(model.device) if side is not None else None
+        synced = None
+        from .vec_normalize import VecNormalize, sync_envs_normalization
+
+        if isinstance(self.eval_env, VecNormalize) and isinstance(getattr(model, "env", None), VecNormalize):
+            # both are VecNormalize: SB3's EvalCallback syncs the statistics before every evaluation.  The copy is queued on the COMPUTE stream, behind
+            # every rollout step queued so far (the statistics buffers it reads are those steps'), and the side stream waits for it
+            sync_envs_normalization(model.env, self.eval_env)
+            if side is not None:
+                synced = torch.cuda.Event(enable_timing=False)
+                synced.record(main)
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            if synced is not None:
+                side.wait_event(synced)
             if side is not None:
                 ev = getattr(model, "_update_done", None)
                 if ev is not None:

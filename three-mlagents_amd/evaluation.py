@@ -20,6 +20,12 @@ import torch
 from . import _lib
 
 
+def _is_vecnormalize(env) -> bool:
+    from .vec_normalize import VecNormalize  # (local: vec_normalize imports nothing from here, but keeps this module's import light)
+
+    return isinstance(env, VecNormalize)
+
+
 def _targets(n_eval_episodes: int, n: int) -> np.ndarray:
     return np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)  # SB3: episodes split evenly over envs
 
@@ -69,7 +75,10 @@ def evaluate_policy_begin(model, env, n_eval_episodes: int = 10, deterministic: 
     cap = max(4096, K * n)  # at most one episode per env and step can finish inside a chunk
     if getattr(eng, "_log_cap", 0) < cap:
         eng.episode_log(cap)
-    eng.reset(bufs.obs[0])
+    if _is_vecnormalize(env):  # a VecNormalize: reset + normalise (its statistics move only while env.training)
+        env.reset_device(bufs.obs[0])
+    else:
+        eng.reset(bufs.obs[0])
     # drop whatever an earlier user of the env left (a step() from a callback, a direct tma_rollout_collect, the previous evaluation's unused
     # episodes and its Monitor aggregate): stream-ordered clear, no host round trip -- the chunk queued next starts from an empty log
     eng.clear_episode_log()
@@ -82,8 +91,11 @@ def evaluate_policy_begin(model, env, n_eval_episodes: int = 10, deterministic: 
 
 def _eval_chunk(st: dict) -> None:
     eng, bufs, K, pol = st["env"].engine, st["bufs"], st["K"], st["model"].policy
-    _lib.check(_lib.lib().tma_rollout_collect(eng._h, _lib.ptr(st["params"]), C.byref(pol.dims), C.byref(bufs.rb), 0, K, K, st["seed"], st["steps"] & 0xFFFFFFFF,
-                                             eng.env_offset & 0xFFFFFFFF, st["gamma"], 0, 1 if st["deterministic"] else 0, _lib.stream_ptr(eng.device)))
+    if _is_vecnormalize(st["env"]):  # a VecNormalize: the policy sees normalised observations; the episode log (the returns reported) stays raw
+        st["env"].collect(st["params"], pol.dims, bufs.rb, 0, K, K, st["seed"], st["steps"], st["gamma"], False, bool(st["deterministic"]))
+    else:
+        _lib.check(_lib.lib().tma_rollout_collect(eng._h, _lib.ptr(st["params"]), C.byref(pol.dims), C.byref(bufs.rb), 0, K, K, st["seed"], st["steps"] & 0xFFFFFFFF,
+                                                 eng.env_offset & 0xFFFFFFFF, st["gamma"], 0, 1 if st["deterministic"] else 0, _lib.stream_ptr(eng.device)))
     bufs.obs[0].copy_(bufs.obs[K])  # the next chunk continues from the last observation
     st["steps"] += K
     st["queued"] = True
@@ -130,11 +142,11 @@ def evaluate_policy_stepwise(model, env, n_eval_episodes: int = 10, deterministi
     targets = _targets(n_eval_episodes, n)
     counts = np.zeros(n, dtype=int)
     rewards, lengths = [], []
-    obs = eng.reset()
+    obs = env.reset_device()  # (a VecNormalize normalises here and in step_device; a plain HipVecEnv: engine.reset / engine.step)
     steps = 0
     while (counts < targets).any() and steps < max_steps:
         actions, _, _ = model.policy.act(obs, rng_seed=model.seed ^ 0xE7A1, rng_step=steps, env_offset=eng.env_offset, deterministic=deterministic)
-        out = eng.step(actions)
+        out = env.step_device(actions)
         obs = out["obs"][0]
         done = (out["term"][0] | out["trunc"][0]).bool()
         if bool(done.any()):

@@ -37,7 +37,7 @@ _SB3_NAMES = {"a2c", "dqn", "ppo", "sac", "td3"}  # what the reference's table a
 _REQUEST = [("task_id", str), ("total_timesteps", "int | None", None), ("algorithm", "str | None", None), ("seed", int, 1),
             ("n_envs", "int | None", None), ("eval_episodes", "int | None", None), ("eval_freq", int, 10_000), ("deterministic_eval", bool, True),
             ("policy", "str | None", None), ("run_name", "str | None", None), ("save_policy", bool, True), ("verbose", int, 1),
-            ("device", "str | None", None)]
+            ("device", "str | None", None), ("normalize", bool, False)]  # (normalize: engine-only extra -- VecNormalize around both vectors)
 _RESULT = [("task_id", str), ("algorithm", str), ("run_id", str), ("model_filename", str), ("model_path", str), ("run_dir", str),
            ("mean_reward", float), ("std_reward", float), ("eval_episodes", int), ("total_timesteps", int), ("metadata_path", str)]
 TrainConfig = dataclasses.make_dataclass("TrainConfig", [f if len(f) == 2 else (f[0], f[1], dataclasses.field(default=f[2])) for f in _REQUEST], frozen=True)
@@ -133,6 +133,7 @@ class _Run:
         self.zip_name = f"{task.policy_prefix}_{run_id}.zip"
         self.zip_path = POLICIES_DIR / self.zip_name
         self.metadata = self.root / "metadata.json"
+        self.vecnormalize = POLICIES_DIR / f"{task.policy_prefix}_{run_id}.vecnormalize.npz"  # written by runs with normalize=True only
 
 
 def train_task(config, *, callback=None, model_kwargs=None):
@@ -148,14 +149,20 @@ def train_task(config, *, callback=None, model_kwargs=None):
     episodes = int(config.eval_episodes or task.eval_episodes)
     run = _Run(task, config.run_name or f"{task.id}_{algo}_{time.strftime('%Y%m%d_%H%M%S')}_{secrets.token_hex(4)}")
     with contextlib.ExitStack() as stack:
-        def opened(n, seed_shift, mon=None):
+        def opened(n, seed_shift, mon=None, training=True):
             e = make_vector_env(task.id, n_envs=n, seed=config.seed + seed_shift, monitor_dir=mon, device=config.device)
+            if config.normalize:  # (closing the wrapper frees its statistics and closes the vector it wraps: one close per vector either way)
+                from .vec_normalize import VecNormalize
+
+                e = VecNormalize(e, training=training)
             stack.callback(e.close)
             return e
 
         # the eval vector is seeded 10 000 past the training seed (the reference: ONE env, episodes one after the other on the host; here the
         # episodes are spread over up to EVAL_ENVS device envs stepped together -- evaluation.py, SB3's even split of episodes over envs)
-        venv, eval_env = opened(n_envs, 0, run.monitor), opened(max(1, min(EVAL_ENVS, episodes)), 10_000)
+        # With config.normalize, SB3's recipe: VecNormalize around the training vector; the evaluation vector gets a frozen one (training=False)
+        # whose statistics are synced from the training one before each evaluation (EvalCallback; below for the final one).
+        venv, eval_env = opened(n_envs, 0, run.monitor), opened(max(1, min(EVAL_ENVS, episodes)), 10_000, training=False)
         hp = {**model_defaults(algo, task, n_envs), "tensorboard_log": str(run.tb), "verbose": config.verbose, **(model_kwargs or {})}
         model = ALGORITHMS[algo](config.policy or "MlpPolicy", venv, seed=config.seed, **hp)
         ev = dict(n_eval_episodes=episodes, deterministic=config.deterministic_eval)
@@ -165,6 +172,11 @@ def train_task(config, *, callback=None, model_kwargs=None):
         model.learn(total_timesteps=budget, callback=CallbackList(hooks), progress_bar=False)
         if config.save_policy:
             model.save(run.zip_path)
+        if config.normalize:
+            from .vec_normalize import sync_envs_normalization
+
+            venv.save(run.vecnormalize)  # beside the policy zip: evaluate_model loads it
+            sync_envs_normalization(venv, eval_env)
         returns, lengths = evaluate_policy(model, eval_env, return_episode_rewards=True, **ev)
         mean, std = statistics.fmean(returns), statistics.pstdev(returns)
         from . import __version__
@@ -174,6 +186,7 @@ def train_task(config, *, callback=None, model_kwargs=None):
                       model_path=str(run.zip_path), mean_reward=mean, std_reward=std, episode_rewards=[float(r) for r in returns],
                       episode_lengths=[int(n) for n in lengths], train_log=model.logger_values,
                       data_parallel=dict(world_size=getattr(model, "world_size", 1), allreduce_path=getattr(model, "allreduce_path", "none")),
+                      **({"normalize": True, "vecnormalize_path": str(run.vecnormalize)} if config.normalize else {}),
                       software=dict(three_mlagents_amd=__version__, engine="libtma_hip.so (gfx950)"), created_at=time.strftime("%Y-%m-%dT%H:%M:%S%z"))
         with open(run.metadata, "w", encoding="utf-8") as fh:
             json.dump(record, fh, indent=2, default=str)
@@ -205,7 +218,19 @@ def evaluate_model(task_id, name_or_path, *, episodes=None, deterministic=True, 
     path = find_policy(task, name_or_path)
     model = ALGORITHMS[_algorithm_from_metadata(path)].load(path)
     n = int(episodes or task.eval_episodes)
-    with contextlib.closing(make_vector_env(task.id, n_envs=max(1, min(EVAL_ENVS, n)), seed=seed)) as env:
+    env = make_vector_env(task.id, n_envs=max(1, min(EVAL_ENVS, n)), seed=seed)
+    stats = Path(str(path)[:-len(".zip")] + ".vecnormalize.npz") if str(path).endswith(".zip") else None
+    if stats is not None and stats.is_file():  # the run trained with normalize=True: the policy expects normalised observations
+        from .vec_normalize import VecNormalize
+
+        try:
+            wrapped = VecNormalize.load(stats, env)
+        except BaseException:
+            env.close()
+            raise
+        wrapped.training = False
+        env = wrapped  # (closing the wrapper frees its statistics and closes the vector it wraps)
+    with contextlib.closing(env):
         returns, lengths = evaluate_policy(model, env, n_eval_episodes=n, deterministic=deterministic, return_episode_rewards=True)
     return dict(task_id=task.id, model=str(path), episodes=n, mean_reward=statistics.fmean(returns), std_reward=statistics.pstdev(returns),
                 episode_rewards=[float(r) for r in returns], episode_lengths=[int(k) for k in lengths])

@@ -346,6 +346,14 @@ class PPO:
         env = self.env
         if not isinstance(env, HipVecEnv):
             raise ValueError("env must be a three_mlagents_amd HipVecEnv (use training.make_vector_env)")
+        from .vec_normalize import VecNormalize
+
+        # a VecNormalize (a HipVecEnv subclass) selects the normalised rollout driver; a plain HipVecEnv takes the unchanged path
+        self._vecnorm = env if isinstance(env, VecNormalize) else None
+        if self._vecnorm is not None and self.world_size > 1:
+            raise ValueError("VecNormalize with world_size > 1 is not supported: global statistics across ranks are not built")
+        if self._vecnorm is not None and getattr(self, "ALGORITHM", "ppo") == "a2c":
+            raise ValueError("A2C with a VecNormalize env is not supported: its native iteration loop has no normalised form yet")
         eng = env.engine
         self.device = eng.device
         self.n_envs = env.num_envs
@@ -592,8 +600,12 @@ class PPO:
         """SB3 OnPolicyAlgorithm.collect_rollouts: n_steps vector steps through the native driver, then GAE."""
         L, T, eng = _lib.lib(), self.n_steps, self.env.engine
         self.policy._sync_if_stepped()  # (a torch optimizer stepped policy.parameters(): rebuild the derived copies the drivers read)
+        vn = self._vecnorm
         if not self._last_obs_valid:
-            eng.reset(self.buf["obs"][0])
+            if vn is not None:
+                vn.reset_device(self.buf["obs"][0])
+            else:
+                eng.reset(self.buf["obs"][0])
             self._last_obs_valid = True
         else:
             self.buf["obs"][0].copy_(self.buf["obs"][T])
@@ -602,9 +614,12 @@ class PPO:
         keep_going = True
         while t < T and keep_going:
             te = min(T, t + chunk)
-            _lib.check(L.tma_rollout_collect(eng._h, _lib.ptr(self.policy.params), C.byref(self.policy.dims), C.byref(self._rb), t, te, T,
-                                             self.seed & 0xFFFFFFFF, (self._rollout_counter * T) & 0xFFFFFFFF, eng.env_offset & 0xFFFFFFFF,
-                                             self.gamma, 1, 0, self._stream()))
+            if vn is not None:  # the per-step composition with one VecNormalize step behind every env step: the buffer holds normalised values
+                vn.collect(self.policy.params, self.policy.dims, self._rb, t, te, T, self.seed, self._rollout_counter * T, self.gamma, True, False)
+            else:
+                _lib.check(L.tma_rollout_collect(eng._h, _lib.ptr(self.policy.params), C.byref(self.policy.dims), C.byref(self._rb), t, te, T,
+                                                 self.seed & 0xFFFFFFFF, (self._rollout_counter * T) & 0xFFFFFFFF, eng.env_offset & 0xFFFFFFFF,
+                                                 self.gamma, 1, 0, self._stream()))
             if callback is not None:
                 # one call per native chunk (callbacks.BaseCallback.on_steps: a per-step loop unless the callback knows how to take the
                 # steps in bulk -- EvalCallback does; 1024 Python round trips per rollout are 2.5 ms at 4096 envs)

@@ -255,7 +255,7 @@ class HipVecEnv:
         return [seed + i for i in range(self.num_envs)]
 
     def reset(self) -> np.ndarray:
-        obs = self.engine.reset().cpu().numpy()
+        obs = self.reset_device().cpu().numpy()
         self.reset_infos = [{} for _ in range(self.num_envs)]
         return obs
 
@@ -273,7 +273,7 @@ class HipVecEnv:
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
 
     def step_wait(self):
-        out = self.engine.step(self._actions_to_device(self._actions))
+        out = self.step_device(self._actions_to_device(self._actions))
         obs = out["obs"][0].cpu().numpy()
         rew = out["rew"][0].cpu().numpy()
         term = out["term"][0].cpu().numpy().astype(bool)
