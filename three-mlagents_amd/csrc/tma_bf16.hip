@@ -65,18 +65,18 @@ static int launch_bf_leaf(const GradBfPlan &p, bf16_t *dz1, Launch launch) {
     return fail(TMA_ERR_INVALID, "internal: bf16 gradient plan %d has no kernel for this head and width", (int)p.id);
 }
 
-int tma_launch_grad_wide_bf(const float *params, const PLayout &L, const Rollout &R, const Minibatch &M, const HParams &hpar, const float *ws_adv,
-                            float *slabs, double *slots, char *ws, const GradBfPlan &p, hipStream_t s) {
+int tma_launch_grad_wide_bf(const float *params, const Rollout &R, const Minibatch &M, const HParams &hpar, const Workspace &ws, const GradBfPlan &p,
+                            hipStream_t s) {
+    const PLayout &L = ws.L;
+    float *const slabs = ws.slabs();
     if (p.zero_w1) {  // runtime observation width: dW1 accumulates in place in the slab
         const int zrc = tma_launch_slab_zero_w1(slabs, p.n_pi, L, s);
         if (zrc) return zrc;
     }
-    // the dz1 cache of the two-pass layouts: behind the slabs, the sample offsets, the epoch's advantage partials and the sum-of-squares slots
-    bf16_t *const dz1 = p.pass == BfPass::Cached
-        ? reinterpret_cast<bf16_t *>(ws + WS_SLABS + (int64_t)slab_cap(L) * L.P * 4 + OFFS_CAP * 4 + EPOCH_PART_BYTES + WIDE_SQ_SLOTS * 8) : nullptr;
+    bf16_t *const dz1 = p.pass == BfPass::Cached ? ws.dz1_cache<bf16_t>() : nullptr;  // two-pass layouts
     auto launch = [&](auto k, bf16_t *dz) -> int {
         TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
-        k<<<dim3((unsigned)(p.n_pi + p.n_vf)), dim3((unsigned)p.block), p.lds, s>>>(params, L, R, M, hpar, ws_adv, slabs, slots, p.n_pi, dz, DZ1_CAP * L.H);
+        k<<<dim3((unsigned)(p.n_pi + p.n_vf)), dim3((unsigned)p.block), p.lds, s>>>(params, L, R, M, hpar, ws.adv(), slabs, ws.stats(), p.n_pi, dz, DZ1_CAP * L.H);
         return TMA_OK;
     };
     auto with_ntw = [&](auto cont) -> int {

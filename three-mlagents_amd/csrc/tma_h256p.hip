@@ -60,7 +60,7 @@ constexpr int L_B3 = L_B2 + 32;                 // [16] zero beyond NOUT
 constexpr int L_W3S = L_B3 + 16;                // [32 k][16] W3t[32c + k][a], zero beyond NOUT
 constexpr int L_RED = L_W3S + 32 * 16;          // double[8 waves][6]
 constexpr int L_FLOATS = L_RED + 2 * 8 * 6;
-// persistent region (bytes from ws + WS_SLABS)
+// persistent region (bytes from WorkspaceHeader::persist_region())
 constexpr int R_SYNC = 0;           // u32 words, 32 apart (one 128-byte line each): see SW_*
 constexpr int SW_CLAIM = 0;         // +net: XCD + 1 of the net
 constexpr int SW_ROLES = 2;         // +net: roles taken
@@ -940,23 +940,21 @@ bool tma_epoch_h256p_eligible(const PLayout &L, int64_t batch_size, int64_t tota
     if (off || L.bf16 || L.fr_pi < 0 || L.H != QH || L.cont || L.A > 16 || L.D > 32 || batch_size != QB) return false;
     if (total < 2 * batch_size || total % batch_size != 0) return false;
     const int64_t n_mb = total / batch_size;
-    return n_mb <= 65535 && R_TABLE + n_mb * 8 <= (int64_t)slab_cap(L) * L.P * 4;
+    return n_mb <= 65535 && R_TABLE + n_mb * 8 <= Workspace::slab_bytes(L);
 }
 
-int tma_launch_epoch_h256p(float *params, const PLayout &L, const Rollout &R, const HParams &hp, const int32_t *offs, const double *adv_part,
-                           int adv_stride, int64_t total, int64_t batch_size, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr,
-                           double beta1, double beta2, double eps, double max_grad_norm, char *ws, hipStream_t s) {
+int tma_launch_epoch_h256p(const EpochJob &job, const Rollout &R, const HParams &hp, int64_t total, int64_t first_step, const AdamArgs &opt) {
     static const int ticks = getenv("TMA_H256P_TICKS") ? 1 : 0;
+    const PLayout &L = job.L;
+    const Workspace &ws = job.ws;
+    hipStream_t s = job.s;
     Epoch256Args a;
-    a.params = params, a.exp_avg = exp_avg, a.exp_avg_sq = exp_avg_sq;
+    a.params = job.params, a.exp_avg = opt.exp_avg, a.exp_avg_sq = opt.exp_avg_sq;
     a.L = L, a.rb = R, a.hp = hp;
-    a.offs = offs, a.adv_part = adv_part, a.adv_stride = adv_stride;
-    a.n_mb = (int)(total / batch_size);
-    a.beta1 = (float)beta1, a.beta2 = (float)beta2, a.eps = (float)eps, a.max_norm = (float)max_grad_norm;
-    a.region = ws + WS_SLABS;
-    a.stat_slots = reinterpret_cast<double *>(ws + WS_STATS);
-    a.norm_out = reinterpret_cast<double *>(ws + WS_NORM_OUT);
-    a.err_out = reinterpret_cast<int *>(ws + WS_PERSIST_ERR);
+    a.offs = ws.offsets(), a.adv_part = ws.epoch_partials(), a.adv_stride = Workspace::adv_stride(job.batch_size);
+    a.n_mb = (int)(total / job.batch_size);
+    a.beta1 = (float)opt.beta1, a.beta2 = (float)opt.beta2, a.eps = (float)opt.eps, a.max_norm = (float)opt.max_grad_norm;
+    a.region = ws.persist_region(), a.stat_slots = ws.stats(), a.norm_out = ws.norm_out(), a.err_out = ws.persist_err();
     a.ticks = ticks;
     const int n_small = 64 + 33 * (L.A > 1 ? L.A : 1);  // scalar small-tensor entries of a slice (b1, b2, W3, b3): <= 592
     const int nsm = (n_small + QT - 1) / QT;
@@ -966,8 +964,8 @@ int tma_launch_epoch_h256p(float *params, const PLayout &L, const Rollout &R, co
     const char *force_fail = getenv("TMA_PERSIST_FORCE_FAIL");
     if (force_fail != nullptr && strcmp(force_fail, "late") != 0)  // test hook: the launch finds its abort word set, commits nothing and reports the failure
         TMA_HIP(hipMemsetAsync(a.region + R_SYNC + 32 * SW_ABORT * 4, 1, 1, s));
-    adam_table256_kernel<<<dim3((unsigned)((a.n_mb + 255) / 256)), dim3(256), 0, s>>>(reinterpret_cast<float2 *>(a.region + R_TABLE), a.n_mb, first_step, lr,
-                                                                                      beta1, beta2);
+    adam_table256_kernel<<<dim3((unsigned)((a.n_mb + 255) / 256)), dim3(256), 0, s>>>(reinterpret_cast<float2 *>(a.region + R_TABLE), a.n_mb, first_step, opt.lr,
+                                                                                      opt.beta1, opt.beta2);
     TMA_LAUNCH_CHECK();
     auto launch = [&](auto k) -> int {
         static bool attr_set = false;  // (one static per instantiation of this lambda's operator(): the attribute call costs ~0.1 ms and is sticky per device function)
@@ -994,6 +992,6 @@ int tma_launch_epoch_h256p(float *params, const PLayout &L, const Rollout &R, co
 extern "C" int tma_debug_h256p_ticks(void *workspace, unsigned long long *out24) {
     if (!workspace || !out24) return TMA_ERR_INVALID;
     TMA_HIP(hipDeviceSynchronize());
-    TMA_HIP(hipMemcpy(out24, static_cast<char *>(workspace) + WS_SLABS + R_TICKS, sizeof(unsigned long long) * 24, hipMemcpyDeviceToHost));
+    TMA_HIP(hipMemcpy(out24, WorkspaceHeader(workspace).persist_region() + R_TICKS, sizeof(unsigned long long) * 24, hipMemcpyDeviceToHost));
     return TMA_OK;
 }

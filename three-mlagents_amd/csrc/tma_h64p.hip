@@ -587,23 +587,22 @@ bool tma_epoch_h64p_eligible(const PLayout &L, int64_t batch_size, int64_t total
     const bool off = getenv("TMA_NO_PERSIST") != nullptr;  // (read per call: tests switch paths inside one process)
     if (off || L.img_pi < 0 || batch_size != 256 || total < 2 * batch_size) return false;
     const int64_t n_mb = (total + batch_size - 1) / batch_size;
-    return n_mb <= 65535 && HP_TABLE + n_mb * 8 <= (int64_t)slab_cap(L) * L.P * 4;
+    return n_mb <= 65535 && HP_TABLE + n_mb * 8 <= Workspace::slab_bytes(L);
 }
 
-int tma_launch_epoch_h64p(float *params, const PLayout &L, const Rollout &R, const HParams &hp, const int32_t *offs, const double *adv_part,
-                          int adv_stride, int64_t total, int64_t batch_size, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr,
-                          double beta1, double beta2, double eps, double max_grad_norm, char *ws, hipStream_t s) {
+int tma_launch_epoch_h64p(const EpochJob &job, const Rollout &R, const HParams &hp, int64_t total, int64_t first_step, const AdamArgs &opt) {
     static const int ticks = getenv("TMA_H64P_TICKS") ? 1 : 0;
+    const PLayout &L = job.L;
+    const Workspace &ws = job.ws;
+    const int64_t batch_size = job.batch_size;
+    hipStream_t s = job.s;
     EpochArgs a;
-    a.params = params, a.exp_avg = exp_avg, a.exp_avg_sq = exp_avg_sq;
+    a.params = job.params, a.exp_avg = opt.exp_avg, a.exp_avg_sq = opt.exp_avg_sq;
     a.L = L, a.rb = R, a.hp = hp;
-    a.offs = offs, a.adv_part = adv_part, a.adv_stride = adv_stride;
+    a.offs = ws.offsets(), a.adv_part = ws.epoch_partials(), a.adv_stride = Workspace::adv_stride(batch_size);
     a.total = total, a.batch = (int)batch_size, a.n_mb = (int)((total + batch_size - 1) / batch_size);
-    a.beta1 = (float)beta1, a.beta2 = (float)beta2, a.eps = (float)eps, a.max_norm = (float)max_grad_norm;
-    a.region = ws + WS_SLABS;
-    a.stat_slots = reinterpret_cast<double *>(ws + WS_STATS);
-    a.norm_out = reinterpret_cast<double *>(ws + WS_NORM_OUT);
-    a.err_out = reinterpret_cast<int *>(ws + WS_PERSIST_ERR);
+    a.beta1 = (float)opt.beta1, a.beta2 = (float)opt.beta2, a.eps = (float)opt.eps, a.max_norm = (float)opt.max_grad_norm;
+    a.region = ws.persist_region(), a.stat_slots = ws.stats(), a.norm_out = ws.norm_out(), a.err_out = ws.persist_err();
     a.ticks = ticks;
     const int nout_max = L.A > 1 ? L.A : 1, dump_imm = 51 * nout_max > 240 ? 51 * nout_max : 240;
     const NetPos qp = net_pos(L.D, nout_max);  // the policy net's position space (the value net's is no larger)
@@ -617,7 +616,7 @@ int tma_launch_epoch_h64p(float *params, const PLayout &L, const Rollout &R, con
     if (force_fail != nullptr && strcmp(force_fail, "late") != 0)  // test hook: the launch finds its abort word set, commits nothing and reports the failure
         TMA_HIP(hipMemsetAsync(a.region + HP_SYNC + 160 * 4, 1, 1, s));
     adam_table_kernel<<<dim3((unsigned)((a.n_mb + 255) / 256)), dim3(256), 0, s>>>(reinterpret_cast<float2 *>(a.region + HP_TABLE), a.n_mb, first_step,
-                                                                                   lr, beta1, beta2);
+                                                                                   opt.lr, opt.beta1, opt.beta2);
     TMA_LAUNCH_CHECK();
     auto launch = [&](auto k) -> int {
         TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
@@ -637,7 +636,7 @@ int tma_launch_epoch_h64p(float *params, const PLayout &L, const Rollout &R, con
 extern "C" int tma_debug_h64p_ticks(void *workspace, unsigned long long *out10) {
     if (!workspace || !out10) return TMA_ERR_INVALID;
     TMA_HIP(hipDeviceSynchronize());
-    TMA_HIP(hipMemcpy(out10, static_cast<char *>(workspace) + WS_SLABS + HP_TICKS, sizeof(unsigned long long) * 10, hipMemcpyDeviceToHost));
+    TMA_HIP(hipMemcpy(out10, WorkspaceHeader(workspace).persist_region() + HP_TICKS, sizeof(unsigned long long) * 10, hipMemcpyDeviceToHost));
     return TMA_OK;
 }
 

@@ -544,7 +544,6 @@ __global__ __launch_bounds__(256) void ppo_grad_kernel(const float *__restrict__
 #ifndef TMA_HALF_RING
 #define TMA_HALF_RING 4
 #endif
-constexpr int W2_DEFER_ROWS = 1024;  // rows per image of the dW2 deferral buffer ([net][h1 | dz2][W2_DEFER_ROWS][H]: half-group minibatches of <= 1024 samples)
 #ifdef TMA_WIDE_PHASE_TICKS  // diagnostic build (make libtma_hip_wticks.so, tools/wide_ticks.py): cycles per phase of the f32 wide gradient kernel, wave 0 of block 0 of each net
 __device__ unsigned long long g_wide_ticks[2][16];
 #define TMA_WTICK(i)                                                      \
@@ -1831,23 +1830,6 @@ struct GradTimer {
     }
 };
 
-// where slab_reduce_kernel leaves its sum-of-squares partials (one per 64 parameters) for tma_ppo_adam_step_local
-// second half of the (parameters, exp_avg, exp_avg_sq) double buffer of the optimizer step folded into the H = 64 gradient launches
-// (AdamFold, tma_ppo_train_epoch_local): 3 x P floats behind everything else in the workspace
-static inline int64_t fold_state_offset(const PLayout &L) {
-    return (WS_SLABS + (int64_t)slab_cap(L) * L.P * 4 + OFFS_CAP * 4 + EPOCH_PART_BYTES + WIDE_SQ_SLOTS * 8 + dz1_cache_bytes(L) + 15) & ~(int64_t)15;
-}
-// (also the snapshot the persistent epoch kernels' fallback restores: H = 64 fast-path layouts and the 256-wide layouts tma_h256p.hip takes)
-static inline bool h256p_layout(const PLayout &L) { return !L.bf16 && L.fr_pi >= 0 && L.H == 256 && !L.cont && L.A <= 16 && L.D <= 32; }
-static inline int64_t fold_state_bytes(const PLayout &L) { return (L.img_pi >= 0 || h256p_layout(L)) ? 3 * (((int64_t)L.P + 3) & ~(int64_t)3) * 4 : 0; }
-
-static double *sq_partials(char *ws, const PLayout &L) {
-    const int n = (int)ceil_div(L.P, 64);
-    if (n <= 256) return reinterpret_cast<double *>(ws + WS_NORM_PART);
-    if (n > WIDE_SQ_SLOTS) return nullptr;
-    return reinterpret_cast<double *>(ws + WS_SLABS + (int64_t)slab_cap(L) * L.P * 4 + OFFS_CAP * 4 + EPOCH_PART_BYTES);
-}
-
 static int check_dims(const tma_policy_dims *d) {
     if (!d) return fail(TMA_ERR_INVALID, "policy dims is null");
     if (d->obs_dim < 1 || d->obs_dim > 4096) return fail(TMA_ERR_INVALID, "obs_dim out of range: %d", d->obs_dim);
@@ -2396,10 +2378,10 @@ static int refuse(const GradPlan &p) { return fail(TMA_ERR_INVALID, "policy too 
 
 // grad (+)= the sum of the slabs in a fixed order, and its sum-of-squares partials.  n_vf < 0: every parameter over n_pi slabs (the H = 64 kernel's
 // block pairs); else the value net's parameters over the first n_vf of them
-static int launch_slab_reduce(const float *slabs, int n_pi, int n_vf, const PLayout &L, float *grad, char *ws, hipStream_t s, int overwrite = 0,
-                              const PeerPush *push = nullptr) {
-    slab_reduce_kernel<<<dim3((unsigned)ceil_div(L.P, 64)), dim3(256), 0, s>>>(slabs, n_pi, L.P, grad, n_vf, n_vf < 0 ? 0 : L.vW1t, n_vf < 0 ? 0 : L.log_std,
-                                                                               sq_partials(ws, L), overwrite, push ? *push : PeerPush{});
+static int launch_slab_reduce(int n_pi, int n_vf, float *grad, const Workspace &ws, hipStream_t s, int overwrite = 0, const PeerPush *push = nullptr) {
+    const PLayout &L = ws.L;
+    slab_reduce_kernel<<<dim3((unsigned)ws.n_sq_partials()), dim3(256), 0, s>>>(ws.slabs(), n_pi, L.P, grad, n_vf, n_vf < 0 ? 0 : L.vW1t, n_vf < 0 ? 0 : L.log_std,
+                                                                                ws.sq_partials(), overwrite, push ? *push : PeerPush{});
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
@@ -2407,11 +2389,12 @@ static int launch_slab_reduce(const float *slabs, int n_pi, int n_vf, const PLay
 // The f32 column-parallel gradient kernel of a plan: the one place its (kt1, half, eight, dz1_cached) become the KT1C / PASS / NQ1C / HALF / NW
 // template arguments.  aux: eight waves -- the dW2 deferral buffer (or null); four -- the dz1 cache of the two-pass kernels (or null: recompute)
 template <bool C, int NTW>
-static int launch_grad_wide(const GradPlan &p, const float *params, const PLayout &L, const Rollout &R, const Minibatch &M, const HParams &hpar,
-                            const float *ws_adv, float *slabs, double *slots, float *aux, hipStream_t s) {
+static int launch_grad_wide(const GradPlan &p, const float *params, const Rollout &R, const Minibatch &M, const HParams &hpar, const Workspace &ws, float *aux,
+                            hipStream_t s) {
+    const PLayout &L = ws.L;
     auto launch = [&](auto k, float *aux_k) -> int {
         TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
-        k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, s>>>(params, L, R, M, hpar, ws_adv, slabs, slots, p.n_pi, aux_k,
+        k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, s>>>(params, L, R, M, hpar, ws.adv(), ws.slabs(), ws.stats(), p.n_pi, aux_k,
                                                                p.eight ? (int64_t)2 * W2_DEFER_ROWS * L.H : DZ1_CAP * L.H);
         return TMA_OK;
     };
@@ -2437,6 +2420,62 @@ static int launch_grad_wide(const GradPlan &p, const float *params, const PLayou
     return launch(ppo_grad_wide_kernel<C, NTW, 0>, nullptr);
 }
 
+// the planes every gradient kernel reads (`who`: prefix of the message)
+static int check_rollout_view(const tma_rollout *rb, const char *who = "") {
+    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->advantages || !rb->returns) return fail(TMA_ERR_INVALID, "%srollout view has a null buffer", who);
+    return TMA_OK;
+}
+// The kernels' view of a caller's rollout.  Whether the sample records go along is the CALLER's rule and differs: the per-minibatch launches
+// pass them only for shapes that have records (rec_floats(L) > 0), the persistent epoch launches pass whatever pointer the caller gave.
+static Rollout rollout_of(const tma_rollout *rb, bool with_packed) {
+    return Rollout{rb->obs, rb->actions, rb->log_probs, rb->advantages, rb->returns, rb->T, rb->N, with_packed ? rb->packed : nullptr};
+}
+
+static int clear_stats(const WorkspaceHeader &ws, hipStream_t s) {
+    TMA_HIP(hipMemsetAsync(ws.stats(), 0, WorkspaceHeader::STATS_BYTES, s));
+    return TMA_OK;
+}
+
+// what minibatch_grad_impl takes beyond tma_ppo_minibatch_grad's arguments
+struct GradExtras {
+    const AdamFold *fold = nullptr;  // H = 64 fast path: the previous minibatch's optimizer step, in this launch's prologue
+    int overwrite = 0;               // the slab reduction stores the gradient instead of adding to it
+    const PeerPush *push = nullptr;  // ... and stores it into every rank's inbox as well (fused peer exchange)
+    const PrepNext *next = nullptr;  // the next minibatch's pre-pass, carried by this launch (eight-wave H = 64 kernel only)
+    int64_t ordered_tiles = 0;       // generic kernel, minibatches of up to this many 16-row tiles: one wave per net (see A2C_ORDERED_TILES)
+};
+
+// The optimizer steps folded into the H = 64 gradient launches: the (parameters, exp_avg, exp_avg_sq) state ping-pongs between the caller's
+// buffers and Workspace::fold_state(); gradient launch k + 1 takes fold_for(step of minibatch k) and, once queued, advance() swaps the
+// halves; finish() is the chain's last step as the ordinary optimizer launch, which reads whichever half is current and leaves everything
+// (derived copies and images included) in the caller's buffers.
+struct FoldChain {
+    const EpochJob &job;
+    const AdamArgs &opt;
+    float *bufs[2][3];
+    int cur = 0;
+    FoldChain(const EpochJob &j, const AdamArgs &o) : job(j), opt(o) {
+        float *own[3] = {j.params, o.exp_avg, o.exp_avg_sq};
+        for (int q = 0; q < 3; q++) bufs[0][q] = own[q], bufs[1][q] = j.ws.fold_state() + q * j.ws.fold_stride();
+    }
+    AdamFold fold_for(int64_t step) const {
+        const AdamArgs::Step t = opt.at(step);
+        return AdamFold{job.grad, job.ws.sq_partials(), job.ws.n_sq_partials(), bufs[cur][0], bufs[cur][1], bufs[cur][2], bufs[cur ^ 1][0], bufs[cur ^ 1][1],
+                        bufs[cur ^ 1][2], (float)opt.max_grad_norm, t.lr_step, (float)opt.beta1, (float)opt.beta2, t.bc2_sqrt, (float)opt.eps, job.ws.norm_out(),
+                        (float)opt.grad_scale};
+    }
+    void advance() { cur ^= 1; }
+    int finish(int64_t step) {
+        const AdamArgs::Step t = opt.at(step);
+        opt_scatter_h64_kernel<<<dim3((unsigned)ceil_div(job.L.P, 256)), dim3(256), 0, job.s>>>(
+            job.params, job.grad, job.L, job.ws.sq_partials(), job.ws.n_sq_partials(), (float)opt.max_grad_norm, job.ws.norm_out(), (float)opt.grad_scale, bufs[cur][0],
+            AdamFastRule{opt.exp_avg, opt.exp_avg_sq, bufs[cur][1], bufs[cur][2], (float)opt.beta1, (float)opt.beta2, t.bc2_sqrt, (float)opt.eps, t.lr_step});
+        TMA_LAUNCH_CHECK();
+        cur = 0;  // (the optimizer launch left the state in the caller's buffers)
+        return TMA_OK;
+    }
+};
+
 }  // namespace tma
 
 using namespace tma;
@@ -2452,9 +2491,8 @@ int tma_check_policy_dims(const tma_policy_dims *d) { return check_dims(d); }
 extern "C" {
 
 int64_t tma_ppo_workspace_bytes(const tma_policy_dims *d) {
-    if (!d || check_dims(d)) return WS_BYTES;
-    const PLayout L = layout_of(d);
-    return fold_state_offset(L) + fold_state_bytes(L);
+    if (!d || check_dims(d)) return WorkspaceHeader::BYTES;
+    return Workspace(nullptr, layout_of(d)).bytes();
 }
 
 int tma_policy_param_count(const tma_policy_dims *d, int64_t *n_trainable, int64_t *n_total) {
@@ -2550,24 +2588,23 @@ int tma_policy_bootstrap(const float *params, const tma_policy_dims *d, const fl
     return launch_fwd<2>(params, d, terminal_obs, n, 0, 0, 0, 1, nullptr, nullptr, nullptr, truncated, (float)gamma, rewards_inout, (hipStream_t)stream);
 }
 
-// fold (H = 64 fast path only): the previous minibatch's optimizer step, done in the prologue of this gradient launch (AdamFold)
+// x.fold (H = 64 fast path only): the previous minibatch's optimizer step, done in the prologue of this gradient launch (AdamFold)
 static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_minibatch *mbi, const tma_ppo_hparams *hp,
-                               float *grad, void *workspace, void *stream, const AdamFold *fold, int overwrite, const PeerPush *push = nullptr,
-                               const PrepNext *next = nullptr /* the next minibatch's pre-pass, carried by this launch (eight-wave H = 64 kernel only) */,
-                               int64_t ordered_tiles = 0 /* generic kernel, minibatches of up to this many 16-row tiles: one wave per net (see A2C_ORDERED_TILES) */) {
+                               float *grad, void *workspace, void *stream, const GradExtras &x = GradExtras{}) {
     g_disp_grad = TMA_DISPATCH_NONE;
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !rb || !mbi || !hp || !grad || !workspace) return fail(TMA_ERR_INVALID, "tma_ppo_minibatch_grad: null argument");
-    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->advantages || !rb->returns) return fail(TMA_ERR_INVALID, "rollout view has a null buffer");
+    if ((rc = check_rollout_view(rb))) return rc;
     if (rb->T < 1 || rb->N < 1) return fail(TMA_ERR_INVALID, "rollout view: T and N must be >= 1");
     const int64_t total = (int64_t)rb->T * rb->N;
     if (total > 0x7fffffffLL) return fail(TMA_ERR_INVALID, "rollout of %lld samples exceeds the 2^31 minibatch index range", (long long)total);
     if (mbi->count < 1 || mbi->start < 0 || mbi->start + mbi->count > total)
         return fail(TMA_ERR_INVALID, "minibatch [%lld, +%lld) outside the %lld-sample rollout", (long long)mbi->start, (long long)mbi->count, (long long)total);
     hipStream_t s = (hipStream_t)stream;
-    const PLayout L = layout_of(d);
-    Rollout R{rb->obs, rb->actions, rb->log_probs, rb->advantages, rb->returns, rb->T, rb->N, rec_floats(L) > 0 ? rb->packed : nullptr};
+    const Workspace ws(workspace, layout_of(d));
+    const PLayout &L = ws.L;
+    const Rollout R = rollout_of(rb, rec_floats(L) > 0);  // (the sample records only for the shapes that have them: a stray pointer is dropped here)
     Minibatch M{mbi->indices, mbi->perm_seed, mbi->perm_epoch, mbi->start, mbi->count, total, nullptr, mbi->count, nullptr, 0};
     const bool prepared = mbi->prepared_batch > 0;
     if (mbi->stats_count != 0) {
@@ -2582,36 +2619,28 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
     const DispatchSwitches sw = read_switches(L, mbi->count, true);
     GradPlan p = plan_grad(L, d->continuous != 0, mbi->count, prepared, hp->normalize_advantage != 0, sw);
     g_disp_grad = p.id;
-    if (p.family == GradFamily::Generic && ceil_div(mbi->count, 16) <= ordered_tiles)  // the same kernel on ONE workgroup of one wave per net: its tiles in turn
+    if (p.family == GradFamily::Generic && ceil_div(mbi->count, 16) <= x.ordered_tiles)  // the same kernel on ONE workgroup of one wave per net: its tiles in turn
         p.grid = 2, p.block = 64, p.lds = grad_smem_bytes(L, 1);
     HParams hpar{(float)hp->clip_range, (float)hp->ent_coef, (float)hp->vf_coef, p.normalize ? 1 : 0, sw.bf_debug};
-    char *ws = static_cast<char *>(workspace);
-    float *ws_adv = reinterpret_cast<float *>(ws + WS_ADV);
-    double *slots = reinterpret_cast<double *>(ws + WS_STATS);
-    double *adv_part = reinterpret_cast<double *>(ws + WS_ADV_PART);
-    int nbk = (int)ceil_div(mbi->count, 1024);
-    if (nbk > ADV_BLOCKS) nbk = ADV_BLOCKS;
-    const int64_t offs_base = WS_SLABS + (int64_t)slab_cap(L) * L.P * 4;
+    double *adv_part = ws.adv_partials();
+    const int nbk = Workspace::adv_stride(mbi->count);
     if (prepared) {  // tma_ppo_epoch_prepare left this minibatch's partials and the epoch's offsets in the workspace
-        int stride = (int)ceil_div(mbi->prepared_batch, 1024);
-        if (stride > ADV_BLOCKS) stride = ADV_BLOCKS;
-        adv_part = reinterpret_cast<double *>(ws + offs_base + OFFS_CAP * 4) + 2 * (mbi->start / mbi->prepared_batch) * stride;
-        M.offs = reinterpret_cast<int32_t *>(ws + offs_base) + mbi->start;
+        adv_part = ws.epoch_partials() + 2 * (mbi->start / mbi->prepared_batch) * Workspace::adv_stride(mbi->prepared_batch);
+        M.offs = ws.offsets() + mbi->start;
     }
     if (p.adv_partial) {
-        int32_t *offs = p.offs_cache ? reinterpret_cast<int32_t *>(ws + offs_base) : nullptr;
+        int32_t *offs = p.offs_cache ? ws.offsets() : nullptr;
         adv_partial_kernel<<<dim3(nbk), dim3(256), 0, s>>>(rb->advantages, M, rb->T, rb->N, adv_part, offs);
         TMA_LAUNCH_CHECK();
         M.offs = offs;
     }
     M.adv_part = adv_part, M.adv_n_part = nbk;
     if (p.adv_final) {
-        adv_final_kernel<<<dim3(1), dim3(64), 0, s>>>(adv_part, nbk, M.stats_n, ws_adv);
+        adv_final_kernel<<<dim3(1), dim3(64), 0, s>>>(adv_part, nbk, M.stats_n, ws.adv());
         TMA_LAUNCH_CHECK();
     }
     const bool h64 = p.family == GradFamily::H64Small || p.family == GradFamily::H64;
-    if (!h64 && (fold || overwrite || push || next)) return fail(TMA_ERR_INVALID, "internal: folded optimizer step outside the H = 64 fast path");
-    float *slabs = reinterpret_cast<float *>(ws + WS_SLABS);
+    if (!h64 && (x.fold || x.overwrite || x.push || x.next)) return fail(TMA_ERR_INVALID, "internal: folded optimizer step outside the H = 64 fast path");
     int n_pi = p.n_pi, n_vf = p.n_vf, lrc = TMA_OK;  // slabs the reduction sums (the inner launchers say how many they wrote)
     switch (p.family) {  // the dominant kernel, between the GradTimer's events
     case GradFamily::Refused: return refuse(p);
@@ -2619,41 +2648,40 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
     case GradFamily::H64: {
         GradTimer timer(s);
         n_vf = -1;
-        lrc = tma_launch_grad_h64(params, L, R, M, hpar, adv_part, nbk, slabs, slots, &n_pi, s, fold, next);
+        lrc = tma_launch_grad_h64(params, L, R, M, hpar, adv_part, nbk, ws.slabs(), ws.stats(), &n_pi, s, x.fold, x.next);
     } break;
     case GradFamily::BF16: {
         if ((int64_t)rb->T * rb->N * L.D >= (int64_t)1 << 31)  // (its observation gather indexes the buffer with 32-bit arithmetic)
             return fail(TMA_ERR_INVALID, "bf16 update: T * N * obs_dim = %lld exceeds 2^31", (long long)((int64_t)rb->T * rb->N * L.D));
         GradTimer timer(s);
-        lrc = tma_launch_grad_wide_bf(params, L, R, M, hpar, ws_adv, slabs, slots, ws, p.bf, s);
+        lrc = tma_launch_grad_wide_bf(params, R, M, hpar, ws, p.bf, s);
     } break;
     case GradFamily::BF16X3: {
         GradTimer timer(s);
-        lrc = tma_launch_grad_split3(params, L, R, M, hpar, slabs, slots, &n_pi, &n_vf, s);
+        lrc = tma_launch_grad_split3(params, L, R, M, hpar, ws.slabs(), ws.stats(), &n_pi, &n_vf, s);
     } break;
     case GradFamily::WideF32: {
         if (p.kt1 == 7 && !p.defer_w2) return fail(TMA_ERR_INVALID, "internal: the kt1 = 7 half-group kernel needs the dW2 deferral buffer (%lld samples)", (long long)mbi->count);
-        if (p.kt1 == 0 && (lrc = tma_launch_slab_zero_w1(slabs, p.n_pi, L, s))) return lrc;
-        float *const aux = p.defer_w2 ? slabs + (int64_t)64 * L.P  // behind slab 64 of the workspace's slab area
-                         : (p.dz1_cached ? reinterpret_cast<float *>(ws + offs_base + OFFS_CAP * 4 + EPOCH_PART_BYTES + WIDE_SQ_SLOTS * 8) : nullptr);
+        if (p.kt1 == 0 && (lrc = tma_launch_slab_zero_w1(ws.slabs(), p.n_pi, L, s))) return lrc;
+        float *const aux = p.defer_w2 ? ws.defer_w2() : (p.dz1_cached ? ws.dz1_cache<float>() : nullptr);
         {
             GradTimer timer(s);
             lrc = with_cont_ntw(p.cont, p.ntw, [&](auto c, auto ntw) -> int {
-                return launch_grad_wide<decltype(c)::value, decltype(ntw)::value>(p, params, L, R, M, hpar, ws_adv, slabs, slots, aux, s);
+                return launch_grad_wide<decltype(c)::value, decltype(ntw)::value>(p, params, R, M, hpar, ws, aux, s);
             });
         }
         if (lrc) return lrc;
         TMA_LAUNCH_CHECK();
         if (p.reduce == GradReduce::WideSmall) {
-            wide_small_reduce_kernel<<<dim3((unsigned)(128 + ceil_div(L.P - 2 * L.H * L.H, 64))), dim3(1024), 0, s>>>(slabs, n_pi, n_vf, L, aux, (int)(p.groups * 16), grad,
-                                                                                                                  sq_partials(ws, L));
+            wide_small_reduce_kernel<<<dim3((unsigned)(128 + ceil_div(L.P - 2 * L.H * L.H, 64))), dim3(1024), 0, s>>>(ws.slabs(), n_pi, n_vf, L, aux, (int)(p.groups * 16), grad,
+                                                                                                                  ws.sq_partials());
             TMA_LAUNCH_CHECK();
         }
     } break;
     case GradFamily::Generic: {
         auto launch = [&](auto k) -> int {
             if (p.lds > LDS_OPT_IN) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
-            k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, s>>>(params, L, R, M, hpar, ws_adv, grad, slots);
+            k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, s>>>(params, L, R, M, hpar, ws.adv(), grad, ws.stats());
             TMA_LAUNCH_CHECK();
             return TMA_OK;
         };
@@ -2661,13 +2689,13 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
     } break;
     }
     if (lrc || p.reduce != GradReduce::Slab) return lrc;
-    return launch_slab_reduce(slabs, n_pi, n_vf, L, grad, ws, s, overwrite, push);
+    return launch_slab_reduce(n_pi, n_vf, grad, ws, s, x.overwrite, x.push);
 }
 
-// count a persistent-epoch fallback in the workspace (WS_PERSIST_ERR + 8: int64) and say so once per process
+// count a persistent-epoch fallback in the workspace and say so once per process
 __global__ void persist_count_kernel(long long *ctr) { *ctr += 1; }
-static int persist_fallback_note(char *ws, hipStream_t s) {
-    persist_count_kernel<<<dim3(1), dim3(1), 0, s>>>(reinterpret_cast<long long *>(ws + WS_PERSIST_ERR + 8));
+static int persist_fallback_note(const WorkspaceHeader &ws, hipStream_t s) {
+    persist_count_kernel<<<dim3(1), dim3(1), 0, s>>>(ws.persist_fallbacks());
     static bool said = false;
     if (!said) {
         said = true;
@@ -2683,7 +2711,7 @@ int tma_ppo_persist_fallbacks(void *workspace, int64_t *count_out, void *stream)
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, workspace) == hipSuccess) (void)hipSetDevice(attr.device);
     long long v = 0;
-    TMA_HIP(hipMemcpyAsync(&v, static_cast<char *>(workspace) + WS_PERSIST_ERR + 8, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    TMA_HIP(hipMemcpyAsync(&v, WorkspaceHeader(workspace).persist_fallbacks(), sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
     TMA_HIP(hipStreamSynchronize((hipStream_t)stream));
     *count_out = (int64_t)v;
     return TMA_OK;
@@ -2691,7 +2719,7 @@ int tma_ppo_persist_fallbacks(void *workspace, int64_t *count_out, void *stream)
 
 int tma_ppo_minibatch_grad(const float *params, const tma_policy_dims *d, const tma_rollout *rb, const tma_minibatch *mbi, const tma_ppo_hparams *hp,
                            float *grad, void *workspace, void *stream) {
-    return minibatch_grad_impl(params, d, rb, mbi, hp, grad, workspace, stream, nullptr, 0);
+    return minibatch_grad_impl(params, d, rb, mbi, hp, grad, workspace, stream);
 }
 
 // The persistent epoch kernels (tma_h64p.hip: H = 64; tma_h256p.hip: the reference's default 256 x 256 policy) over `n_epochs` consecutive
@@ -2701,64 +2729,55 @@ int tma_ppo_minibatch_grad(const float *params, const tma_policy_dims *d, const 
 // between epochs.  *ran = 1: everything is committed (parameters, moments, derived images, statistics).  *ran = 0: the shape is not
 // eligible, or the launch could not place / synchronise its workgroups: the state is what it was before the call (snapshot restored,
 // the event counted) and the caller runs the epochs through the per-minibatch launches.
-static int persistent_epochs(float *params, const tma_policy_dims *d, const tma_rollout *rb, const PLayout &L, uint32_t perm_seed, uint32_t perm_epoch0,
-                             int n_epochs, int64_t batch_size, const tma_ppo_hparams *hp, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr,
-                             double beta1, double beta2, double eps, double max_grad_norm, void *workspace, void *stream, int *ran) {
+static int persistent_epochs(const EpochJob &job, uint32_t perm_epoch0, int n_epochs, int64_t first_step, const AdamArgs &opt, int *ran) {
     *ran = 0;
-    const int64_t total = (int64_t)rb->T * rb->N, all = total * n_epochs;
+    const tma_rollout *rb = job.rb;
+    const PLayout &L = job.L;
+    const Workspace &ws = job.ws;
+    const int64_t batch_size = job.batch_size, total = (int64_t)rb->T * rb->N, all = total * n_epochs;
     if (n_epochs < 1 || all > OFFS_CAP || batch_size < 256 || total % batch_size != 0) return TMA_OK;
     const bool p64 = tma_epoch_h64p_eligible(L, batch_size, all);
     const bool p256 = !p64 && h256p_layout(L) && tma_epoch_h256p_eligible(L, batch_size, all);
     if (!p64 && !p256) return TMA_OK;
-    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->advantages || !rb->returns) return fail(TMA_ERR_INVALID, "rollout view has a null buffer");
-    char *ws = static_cast<char *>(workspace);
-    hipStream_t ps = (hipStream_t)stream;
-    const int64_t offs_base = WS_SLABS + (int64_t)slab_cap(L) * L.P * 4;
-    int stride = (int)ceil_div(batch_size, 1024);
-    if (stride > ADV_BLOCKS) stride = ADV_BLOCKS;
+    int rc = check_rollout_view(rb);
+    if (rc) return rc;
+    hipStream_t ps = job.s;
+    const int stride = Workspace::adv_stride(batch_size);
     const int64_t n_mb = total / batch_size;
     for (int e = 0; e < n_epochs; e++) {  // (tma_ppo_epoch_prepare's launch, epoch e at its place)
-        Minibatch M{nullptr, perm_seed, perm_epoch0 + (uint32_t)e, 0, total, total, nullptr, total, nullptr, 0};
-        adv_partial_kernel<<<dim3(stride, (unsigned)n_mb), dim3(256), 0, ps>>>(rb->advantages, M, rb->T, rb->N,
-                                                                               reinterpret_cast<double *>(ws + offs_base + OFFS_CAP * 4) + 2 * e * n_mb * stride,
-                                                                               reinterpret_cast<int32_t *>(ws + offs_base) + e * total, batch_size);
+        Minibatch M{nullptr, job.perm_seed, perm_epoch0 + (uint32_t)e, 0, total, total, nullptr, total, nullptr, 0};
+        adv_partial_kernel<<<dim3(stride, (unsigned)n_mb), dim3(256), 0, ps>>>(rb->advantages, M, rb->T, rb->N, ws.epoch_partials() + 2 * e * n_mb * stride,
+                                                                               ws.offsets() + e * total, batch_size);
         TMA_LAUNCH_CHECK();
     }
-    const Rollout R{rb->obs, rb->actions, rb->log_probs, rb->advantages, rb->returns, rb->T, rb->N, rb->packed};
-    const HParams hpar{(float)hp->clip_range, (float)hp->ent_coef, (float)hp->vf_coef, hp->normalize_advantage ? 1 : 0, 0};
+    const Rollout R = rollout_of(rb, true);  // (the persistent kernels get the caller's sample records as they come, whatever the shape: as ever)
+    const HParams hpar{(float)job.hp->clip_range, (float)job.hp->ent_coef, (float)job.hp->vf_coef, job.hp->normalize_advantage ? 1 : 0, 0};
     // Snapshot of what the launch may commit (trainable parameters, both moments, its 64 statistic slots) in the idle half of the AdamFold
     // double buffer: "commit nothing after an abort" is a per-block decision inside the kernel, so a block that gives up on its LAST wait
     // can raise the abort word after another block has already written its net -- the fallback restores the snapshot first and is
     // therefore the same results whatever the kernel managed to write (4 small device copies per launch).
-    const int64_t Pp = ((int64_t)L.P + 3) & ~(int64_t)3;
-    float *snap = reinterpret_cast<float *>(ws + fold_state_offset(L));
-    TMA_HIP(hipMemcpyAsync(snap, params, (size_t)L.P * 4, hipMemcpyDeviceToDevice, ps));
-    TMA_HIP(hipMemcpyAsync(snap + Pp, exp_avg, (size_t)L.P * 4, hipMemcpyDeviceToDevice, ps));
-    TMA_HIP(hipMemcpyAsync(snap + 2 * Pp, exp_avg_sq, (size_t)L.P * 4, hipMemcpyDeviceToDevice, ps));
-    TMA_HIP(hipMemcpyAsync(ws + WS_PERSIST_SNAP, ws + WS_STATS, 8 * 8 * 8, hipMemcpyDeviceToDevice, ps));
-    int rc = (p64 ? tma_launch_epoch_h64p : tma_launch_epoch_h256p)(params, L, R, hpar, reinterpret_cast<const int32_t *>(ws + offs_base),
-                                                                    reinterpret_cast<const double *>(ws + offs_base + OFFS_CAP * 4), stride, all, batch_size,
-                                                                    exp_avg, exp_avg_sq, first_step, lr, beta1, beta2, eps, max_grad_norm, ws, ps);
+    float *const state[3] = {job.params, opt.exp_avg, opt.exp_avg_sq};
+    for (int q = 0; q < 3; q++) TMA_HIP(hipMemcpyAsync(ws.fold_state() + q * ws.fold_stride(), state[q], (size_t)L.P * 4, hipMemcpyDeviceToDevice, ps));
+    TMA_HIP(hipMemcpyAsync(ws.persist_stats_snap(), ws.stats(), Workspace::SNAP_BYTES, hipMemcpyDeviceToDevice, ps));
+    rc = (p64 ? tma_launch_epoch_h64p : tma_launch_epoch_h256p)(job, R, hpar, all, first_step, opt);
     if (rc) return rc;
     // The persistent kernels need their workgroups resident together on one XCD per group (H = 64: eight on one; 256-wide: 32 on each of
     // two); a concurrent kernel, a CU mask or a preempted wave can deny that, in which case they give up on a bounded wait and commit
     // NOTHING.  Check per launch (one 4-byte read-back: the launch is ~10^5 times longer) and, on failure, hand the epochs back to the
     // per-minibatch launches -- training goes on, the event is counted (tma_ppo_persist_fallbacks) and reported once on stderr.
     int persist_err = 0;
-    TMA_HIP(hipMemcpyAsync(&persist_err, ws + WS_PERSIST_ERR, sizeof(int), hipMemcpyDeviceToHost, ps));
+    TMA_HIP(hipMemcpyAsync(&persist_err, ws.persist_err(), sizeof(int), hipMemcpyDeviceToHost, ps));
     TMA_HIP(hipStreamSynchronize(ps));
     if (const char *ff = getenv("TMA_PERSIST_FORCE_FAIL"))  // test hook "late": the launch ran and committed EVERYTHING, then is declared failed
         if (!strcmp(ff, "late")) persist_err = 1;
     if (!persist_err) {
         *ran = 1;
-        return p256 ? launch_sync(params, L, ps) : TMA_OK;  // (the 256-wide kernel writes the trainable region; its derived images follow here)
+        return p256 ? launch_sync(job.params, L, ps) : TMA_OK;  // (the 256-wide kernel writes the trainable region; its derived images follow here)
     }
-    TMA_HIP(hipMemsetAsync(ws + WS_PERSIST_ERR, 0, sizeof(int), ps));
-    TMA_HIP(hipMemcpyAsync(params, snap, (size_t)L.P * 4, hipMemcpyDeviceToDevice, ps));
-    TMA_HIP(hipMemcpyAsync(exp_avg, snap + Pp, (size_t)L.P * 4, hipMemcpyDeviceToDevice, ps));
-    TMA_HIP(hipMemcpyAsync(exp_avg_sq, snap + 2 * Pp, (size_t)L.P * 4, hipMemcpyDeviceToDevice, ps));
-    TMA_HIP(hipMemcpyAsync(ws + WS_STATS, ws + WS_PERSIST_SNAP, 8 * 8 * 8, hipMemcpyDeviceToDevice, ps));
-    rc = launch_sync(params, L, ps);  // derived copies and weight images of the restored parameters
+    TMA_HIP(hipMemsetAsync(ws.persist_err(), 0, sizeof(int), ps));
+    for (int q = 0; q < 3; q++) TMA_HIP(hipMemcpyAsync(state[q], ws.fold_state() + q * ws.fold_stride(), (size_t)L.P * 4, hipMemcpyDeviceToDevice, ps));
+    TMA_HIP(hipMemcpyAsync(ws.stats(), ws.persist_stats_snap(), Workspace::SNAP_BYTES, hipMemcpyDeviceToDevice, ps));
+    rc = launch_sync(job.params, L, ps);  // derived copies and weight images of the restored parameters
     if (rc) return rc;
     if (n_epochs == 1) persist_fallback_note(ws, ps);  // (a multi-epoch launch that failed is retried epoch by epoch: each of those counts for itself)
     return TMA_OK;
@@ -2779,7 +2798,7 @@ static bool h64_fold_eligible(const PLayout &L, int64_t total, int64_t batch_siz
 // AdamFold: the optimizer step of minibatch k runs in the prologue of gradient launch k + 1 (every workgroup redoes it for its net and
 // builds its weight image from the results), so a minibatch costs two launches (gradient, slab reduction) instead of three; the state
 // ping-pongs between (params, exp_avg, exp_avg_sq) and the workspace copy, and the last step is the ordinary optimizer launch, which leaves
-// everything (derived copies and images included) in the caller's buffers.  Same arithmetic on the same inputs as the unfolded sequence.
+// everything (derived copies and images included) in the caller's buffers (FoldChain).  Same arithmetic on the same inputs as the unfolded sequence.
 // PrepNext (minibatches of more than 2 048 rows: the eight-wave kernel): no tma_ppo_epoch_prepare launch in front of an epoch -- gradient
 // launch k carries the pre-pass of minibatch k + 1 (the epoch's last one: of minibatch 0 of the next epoch) in the idle tail of its value
 // blocks; launch k reads region k of the offsets / partials and writes region k + 1 (n_mb >= 2: never the same), the kernel boundary
@@ -2787,36 +2806,26 @@ static bool h64_fold_eligible(const PLayout &L, int64_t total, int64_t batch_siz
 // rows), get adv_partial_kernel over that minibatch alone.  Every epoch still ends in the ordinary optimizer launch: folding that step
 // into the next epoch's first gradient launch as well was built and did not show in the headline.
 // TMA_NO_PREP_FOLD=1 (read per call): one prepare launch per epoch, the sequence before.  Bit-identical.
-static int h64_fold_epochs(float *params, const tma_policy_dims *d, const tma_rollout *rb, const PLayout &L, uint32_t perm_seed, uint32_t perm_epoch0, int n_epochs,
-                           int64_t batch_size, const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr,
-                           double beta1, double beta2, double eps, double max_grad_norm, void *workspace, void *stream) {
-    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->advantages || !rb->returns) return fail(TMA_ERR_INVALID, "rollout view has a null buffer");
-    const int64_t total = (int64_t)rb->T * rb->N, n_mb = ceil_div(total, batch_size);
-    char *ws = static_cast<char *>(workspace);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t Pp = ((int64_t)L.P + 3) & ~(int64_t)3;
-    float *alt = reinterpret_cast<float *>(ws + fold_state_offset(L));
-    float *bufs[2][3] = {{params, exp_avg, exp_avg_sq}, {alt, alt + Pp, alt + 2 * Pp}};
-    int cur = 0;
-    const double *sqp = sq_partials(ws, L);
+static int h64_fold_epochs(const EpochJob &job, uint32_t perm_epoch0, int n_epochs, int64_t first_step, const AdamArgs &opt) {
+    const tma_rollout *rb = job.rb;
+    int rc = check_rollout_view(rb);
+    if (rc) return rc;
+    const int64_t batch_size = job.batch_size, total = (int64_t)rb->T * rb->N, n_mb = ceil_div(total, batch_size);
+    hipStream_t s = job.s;
+    FoldChain chain_opt(job, opt);
     const bool chain = getenv("TMA_NO_PREP_FOLD") == nullptr && tma_grad_h64_carries_prep(batch_size);
-    const int64_t offs_base = WS_SLABS + (int64_t)slab_cap(L) * L.P * 4;  // the regions tma_ppo_epoch_prepare fills
-    int32_t *offs_all = reinterpret_cast<int32_t *>(ws + offs_base);
-    double *part_all = reinterpret_cast<double *>(ws + offs_base + OFFS_CAP * 4);
-    int stride = (int)ceil_div(batch_size, 1024);
-    if (stride > ADV_BLOCKS) stride = ADV_BLOCKS;
-    auto prep_of = [&](int e, int64_t k) {  // minibatch k of epoch e and where its offsets and partials belong
+    const int stride = Workspace::adv_stride(batch_size);
+    auto prep_of = [&](int e, int64_t k) {  // minibatch k of epoch e and where its offsets and partials belong (the regions tma_ppo_epoch_prepare fills)
         const int64_t start = k * batch_size, count = start + batch_size <= total ? batch_size : total - start;
-        return PrepNext{rb->advantages, offs_all + start, part_all + 2 * k * stride, perm_seed, perm_epoch0 + (uint32_t)e, start, count, total, rb->N, rb->T,
-                        hp->normalize_advantage ? 1 : 0};
+        return PrepNext{rb->advantages, job.ws.offsets() + start, job.ws.epoch_partials() + 2 * k * stride, job.perm_seed, perm_epoch0 + (uint32_t)e, start, count,
+                        total, rb->N, rb->T, job.hp->normalize_advantage ? 1 : 0};
     };
     bool ready = false;  // the coming minibatch's pre-pass rides on the gradient launch before it
     int64_t step = first_step;
-    int rc;
     for (int e = 0; e < n_epochs; e++) {
         if (!chain) {
-            const tma_minibatch ep{nullptr, perm_seed, perm_epoch0 + (uint32_t)e, 0, total, 0, 0};
-            rc = tma_ppo_epoch_prepare(rb, &ep, batch_size, d, workspace, stream);
+            const tma_minibatch ep{nullptr, job.perm_seed, perm_epoch0 + (uint32_t)e, 0, total, 0, 0};
+            rc = tma_ppo_epoch_prepare(rb, &ep, batch_size, job.d, job.ws.base, job.s);
             if (rc) return rc;
             g_prep_standalone++;
         }
@@ -2824,9 +2833,7 @@ static int h64_fold_epochs(float *params, const tma_policy_dims *d, const tma_ro
             const PrepNext me = prep_of(e, k);
             if (chain && !ready) {  // nobody carried it: the pre-pass over this minibatch alone
                 const Minibatch M{nullptr, me.perm_seed, me.perm_epoch, me.start, me.count, total, nullptr, me.count, nullptr, 0};
-                int nbk = (int)ceil_div(me.count, 1024);
-                if (nbk > ADV_BLOCKS) nbk = ADV_BLOCKS;
-                adv_partial_kernel<<<dim3(nbk), dim3(256), 0, s>>>(rb->advantages, M, rb->T, rb->N, me.partials_out, me.offs_out);
+                adv_partial_kernel<<<dim3(Workspace::adv_stride(me.count)), dim3(256), 0, s>>>(rb->advantages, M, rb->T, rb->N, me.partials_out, me.offs_out);
                 TMA_LAUNCH_CHECK();
                 g_prep_standalone++;
             }
@@ -2837,24 +2844,15 @@ static int h64_fold_epochs(float *params, const tma_policy_dims *d, const tma_ro
                 ready = tma_grad_h64_carries_prep(me.count) && tma_grad_h64_carries_prep(nx.count);  // both sides on the eight-wave kernel
                 if (ready) g_prep_folded++;
             }
-            const tma_minibatch mb{nullptr, perm_seed, me.perm_epoch, me.start, me.count, batch_size, 0};
-            AdamFold f{};
-            if (k > 0) {  // the step of the previous minibatch (index step - 1)
-                const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
-                f = AdamFold{grad, sqp, (int)ceil_div(L.P, 64), bufs[cur][0], bufs[cur][1], bufs[cur][2], bufs[cur ^ 1][0], bufs[cur ^ 1][1],
-                             bufs[cur ^ 1][2], (float)max_grad_norm, (float)(lr / bc1), (float)beta1, (float)beta2, (float)sqrt(bc2), (float)eps,
-                             reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f};
-            }
-            rc = minibatch_grad_impl(params, d, rb, &mb, hp, grad, workspace, stream, k > 0 ? &f : nullptr, k > 0 ? 1 : 0, nullptr, ready ? &nx : nullptr);
+            const tma_minibatch mb{nullptr, job.perm_seed, me.perm_epoch, me.start, me.count, batch_size, 0};
+            const AdamFold f = k > 0 ? chain_opt.fold_for(step - 1) : AdamFold{};  // the step of the previous minibatch
+            GradExtras x;
+            x.fold = k > 0 ? &f : nullptr, x.overwrite = k > 0 ? 1 : 0, x.next = ready ? &nx : nullptr;
+            rc = minibatch_grad_impl(job.params, job.d, rb, &mb, job.hp, job.grad, job.ws.base, job.s, x);
             if (rc) return rc;
-            if (k > 0) cur ^= 1;
+            if (k > 0) chain_opt.advance();
         }
-        const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
-        opt_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
-            params, grad, L, sqp, (int)ceil_div(L.P, 64), (float)max_grad_norm, reinterpret_cast<double *>(ws + WS_NORM_OUT), 1.0f, bufs[cur][0],
-            AdamFastRule{exp_avg, exp_avg_sq, bufs[cur][1], bufs[cur][2], (float)beta1, (float)beta2, (float)sqrt(bc2), (float)eps, (float)(lr / bc1)});
-        TMA_LAUNCH_CHECK();
-        cur = 0;  // (the optimizer launch left the state in the caller's buffers)
+        if ((rc = chain_opt.finish(step - 1))) return rc;
     }
     return TMA_OK;
 }
@@ -2865,9 +2863,38 @@ int tma_debug_last_prep_fold(int *folded_out, int *standalone_out) {
     return TMA_OK;
 }
 
-static int train_epoch_local_impl(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch, int64_t batch_size,
-                                  const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr, double beta1,
-                                  double beta2, double eps, double max_grad_norm, void *workspace, void *stream);
+// one epoch: the single-epoch persistent launch where the shape has one, else the H = 64 fold chain, else a gradient and an optimizer call per minibatch
+static int train_epoch_local_impl(const EpochJob &job, uint32_t perm_epoch, int64_t first_step, const AdamArgs &opt) {
+    const tma_rollout *rb = job.rb;
+    const int64_t batch_size = job.batch_size, total = (int64_t)rb->T * rb->N;
+    const bool prepared = total <= OFFS_CAP && batch_size >= 256;
+    int rc;
+    if (prepared) {
+        // the reference's literal batch_size = 256: the whole epoch as one persistent launch (H = 64: tma_h64p.hip; the reference's default
+        // 256 x 256 policy: tma_h256p.hip)
+        int ran = 0;
+        rc = persistent_epochs(job, perm_epoch, 1, first_step, opt, &ran);
+        if (rc) return rc;
+        if (ran) return TMA_OK;
+        if (h64_fold_eligible(job.L, total, batch_size))  // H = 64 fast path: optimizer steps (and, from 2 049 rows a minibatch, pre-passes) inside the gradient launches
+            return h64_fold_epochs(job, perm_epoch, 1, first_step, opt);
+        const tma_minibatch ep{nullptr, job.perm_seed, perm_epoch, 0, total, 0, 0};
+        rc = tma_ppo_epoch_prepare(rb, &ep, batch_size, job.d, job.ws.base, job.s);
+        if (rc) return rc;
+        g_prep_standalone++;
+    }
+    int64_t step = first_step;
+    for (int64_t start = 0; start < total; start += batch_size, step++) {
+        const int64_t count = start + batch_size <= total ? batch_size : total - start;
+        const tma_minibatch mb{nullptr, job.perm_seed, perm_epoch, start, count, prepared ? batch_size : 0, 0};
+        rc = tma_ppo_minibatch_grad(job.params, job.d, rb, &mb, job.hp, job.grad, job.ws.base, job.s);
+        if (rc) return rc;
+        rc = tma_ppo_adam_step_local(job.params, job.grad, opt.exp_avg, opt.exp_avg_sq, job.d, step, opt.lr, opt.beta1, opt.beta2, opt.eps, opt.max_grad_norm,
+                                     job.ws.base, job.s, count);
+        if (rc) return rc;
+    }
+    return TMA_OK;
+}
 
 int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch0, int n_epochs,
                                int64_t batch_size, const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr,
@@ -2879,6 +2906,8 @@ int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tm
         return fail(TMA_ERR_INVALID, "tma_ppo_train_epochs_local: T, N, batch_size, first_step and n_epochs must be >= 1");
     const int64_t total = (int64_t)rb->T * rb->N, n_mb = ceil_div(total, batch_size);
     const PLayout L = layout_of(d);
+    const EpochJob job{params, d, L, rb, perm_seed, batch_size, hp, grad, Workspace(workspace, L), (hipStream_t)stream};
+    const AdamArgs opt{exp_avg, exp_avg_sq, lr, beta1, beta2, eps, max_grad_norm, 1.0};
     g_prep_folded = g_prep_standalone = 0;
     int e = 0;
     // as many epochs per persistent launch as the offsets cache holds (all of them for the reference's own 1- and 8-env schedules: 4 or 32
@@ -2887,8 +2916,7 @@ int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tm
     while (per >= 1 && e < n_epochs) {
         const int n = n_epochs - e < per ? n_epochs - e : per;
         int ran = 0;
-        rc = persistent_epochs(params, d, rb, L, perm_seed, perm_epoch0 + (uint32_t)e, n, batch_size, hp, exp_avg, exp_avg_sq, first_step + e * n_mb, lr, beta1, beta2,
-                               eps, max_grad_norm, workspace, stream, &ran);
+        rc = persistent_epochs(job, perm_epoch0 + (uint32_t)e, n, first_step + e * n_mb, opt, &ran);
         if (rc) return rc;
         if (!ran) break;
         e += n;
@@ -2896,60 +2924,27 @@ int tma_ppo_train_epochs_local(float *params, const tma_policy_dims *d, const tm
     // H = 64 fast path at minibatches the eight-wave gradient kernel takes (never a persistent-kernel shape: those are batch_size 256): the
     // remaining epochs as ONE chain of gradient launches, each carrying the next minibatch's pre-pass -- across the epoch boundaries too
     if (e < n_epochs && h64_fold_eligible(L, total, batch_size) && tma_grad_h64_carries_prep(batch_size))
-        return h64_fold_epochs(params, d, rb, L, perm_seed, perm_epoch0 + (uint32_t)e, n_epochs - e, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step + e * n_mb, lr,
-                               beta1, beta2, eps, max_grad_norm, workspace, stream);
+        return h64_fold_epochs(job, perm_epoch0 + (uint32_t)e, n_epochs - e, first_step + e * n_mb, opt);
     for (; e < n_epochs; e++) {  // not eligible (or handed back): epoch by epoch (which tries the single-epoch persistent launch first, then the launches)
-        rc = train_epoch_local_impl(params, d, rb, perm_seed, perm_epoch0 + (uint32_t)e, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step + e * n_mb, lr,
-                                       beta1, beta2, eps, max_grad_norm, workspace, stream);
+        rc = train_epoch_local_impl(job, perm_epoch0 + (uint32_t)e, first_step + e * n_mb, opt);
         if (rc) return rc;
     }
     return TMA_OK;
 }
 
+// (NOT tma_ppo_train_epochs_local with n_epochs = 1: after a failed persistent launch that entry point hands the epoch to this path, which
+// tries the launch again -- the merged call would try, and count the fallback, twice an epoch)
 int tma_ppo_train_epoch_local(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch, int64_t batch_size,
                               const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr, double beta1,
                               double beta2, double eps, double max_grad_norm, void *workspace, void *stream) {
     g_prep_folded = g_prep_standalone = 0;
-    return train_epoch_local_impl(params, d, rb, perm_seed, perm_epoch, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step, lr, beta1, beta2, eps, max_grad_norm,
-                                  workspace, stream);
-}
-
-static int train_epoch_local_impl(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch, int64_t batch_size,
-                                  const tma_ppo_hparams *hp, float *grad, float *exp_avg, float *exp_avg_sq, int64_t first_step, double lr, double beta1,
-                                  double beta2, double eps, double max_grad_norm, void *workspace, void *stream) {
     int rc = enter(d);
     if (rc) return rc;
     if (!params || !rb || !hp || !grad || !exp_avg || !exp_avg_sq || !workspace) return fail(TMA_ERR_INVALID, "tma_ppo_train_epoch_local: null argument");
     if (rb->T < 1 || rb->N < 1 || batch_size < 1 || first_step < 1) return fail(TMA_ERR_INVALID, "tma_ppo_train_epoch_local: T, N, batch_size and first_step must be >= 1");
-    const int64_t total = (int64_t)rb->T * rb->N;
-    const bool prepared = total <= OFFS_CAP && batch_size >= 256;
     const PLayout L = layout_of(d);
-    if (prepared) {
-        // the reference's literal batch_size = 256: the whole epoch as one persistent launch (H = 64: tma_h64p.hip; the reference's default
-        // 256 x 256 policy: tma_h256p.hip)
-        int ran = 0;
-        rc = persistent_epochs(params, d, rb, L, perm_seed, perm_epoch, 1, batch_size, hp, exp_avg, exp_avg_sq, first_step, lr, beta1, beta2, eps, max_grad_norm,
-                               workspace, stream, &ran);
-        if (rc) return rc;
-        if (ran) return TMA_OK;
-        if (h64_fold_eligible(L, total, batch_size))  // H = 64 fast path: optimizer steps (and, from 2 049 rows a minibatch, pre-passes) inside the gradient launches
-            return h64_fold_epochs(params, d, rb, L, perm_seed, perm_epoch, 1, batch_size, hp, grad, exp_avg, exp_avg_sq, first_step, lr, beta1, beta2, eps,
-                                   max_grad_norm, workspace, stream);
-        const tma_minibatch ep{nullptr, perm_seed, perm_epoch, 0, total, 0, 0};
-        rc = tma_ppo_epoch_prepare(rb, &ep, batch_size, d, workspace, stream);
-        if (rc) return rc;
-        g_prep_standalone++;
-    }
-    int64_t step = first_step;
-    for (int64_t start = 0; start < total; start += batch_size, step++) {
-        const int64_t count = start + batch_size <= total ? batch_size : total - start;
-        const tma_minibatch mb{nullptr, perm_seed, perm_epoch, start, count, prepared ? batch_size : 0, 0};
-        rc = tma_ppo_minibatch_grad(params, d, rb, &mb, hp, grad, workspace, stream);
-        if (rc) return rc;
-        rc = tma_ppo_adam_step_local(params, grad, exp_avg, exp_avg_sq, d, step, lr, beta1, beta2, eps, max_grad_norm, workspace, stream, count);
-        if (rc) return rc;
-    }
-    return TMA_OK;
+    const EpochJob job{params, d, L, rb, perm_seed, batch_size, hp, grad, Workspace(workspace, L), (hipStream_t)stream};
+    return train_epoch_local_impl(job, perm_epoch, first_step, AdamArgs{exp_avg, exp_avg_sq, lr, beta1, beta2, eps, max_grad_norm, 1.0});
 }
 
 int tma_ppo_train_epoch_dp(float *params, const tma_policy_dims *d, const tma_rollout *rb, uint32_t perm_seed, uint32_t perm_epoch, int64_t batch_size,
@@ -2964,6 +2959,8 @@ int tma_ppo_train_epoch_dp(float *params, const tma_policy_dims *d, const tma_ro
     if (stats_world < 0 || (stats_world > 0 && prepared_batch == 0)) return fail(TMA_ERR_INVALID, "tma_ppo_train_epoch_dp: global statistics need a prepared epoch");
     const int64_t total = (int64_t)rb->T * rb->N;
     const PLayout L = layout_of(d);
+    const EpochJob job{params, d, L, rb, perm_seed, batch_size, hp, grad, Workspace(workspace, L), (hipStream_t)stream};
+    const AdamArgs opt{exp_avg, exp_avg_sq, lr, beta1, beta2, eps, max_grad_norm, grad_scale};
     // (The optimizer step is NOT folded into the next gradient launch here, as tma_ppo_train_epoch_local does: the clip norm must come from the
     // all-reduced gradient, and taking it in every workgroup's prologue -- 147 64-lane f64 shuffle trees through the LDS crossbar of each CU --
     // measured 3.4 us per minibatch SLOWER than the sum-of-squares + optimizer launches it would replace: DESIGN.md section 10.)
@@ -2979,14 +2976,10 @@ int tma_ppo_train_epoch_dp(float *params, const tma_policy_dims *d, const tma_ro
     const int64_t tail = total % batch_size;
     static const bool no_dp_fold = getenv("TMA_DP_NO_FOLD") != nullptr || getenv("TMA_NO_ADAM_FOLD") != nullptr;  // A/B switch: the round-4 chain
     if (L.img_pi >= 0 && L.P <= 64 * 256 && prepared_batch == batch_size && batch_size >= 256 && (tail == 0 || tail >= 256) && total > batch_size && !no_dp_fold) {
-        char *ws = static_cast<char *>(workspace);
-        hipStream_t s = (hipStream_t)stream;
-        const int64_t Pp = ((int64_t)L.P + 3) & ~(int64_t)3;
-        float *alt = reinterpret_cast<float *>(ws + fold_state_offset(L));
-        float *bufs[2][3] = {{params, exp_avg, exp_avg_sq}, {alt, alt + Pp, alt + 2 * Pp}};
-        int cur = 0;
-        double *sqp = sq_partials(ws, L);
-        const int n_part = (int)ceil_div(L.P, 64);
+        hipStream_t s = job.s;
+        FoldChain chain(job, opt);
+        double *sqp = job.ws.sq_partials();
+        const int n_part = job.ws.n_sq_partials();
         // the library's own communicator with its peer exchange on (tma_comm_p2p_enable) and bound to this stream: fuse the exchange
         static const bool no_p2p_fuse = getenv("TMA_P2P_NO_FUSE") != nullptr;  // A/B switch: push / pull as launches of their own (tma_comm_allreduce)
         tma_comm *comm = allreduce == &tma_comm_allreduce_cb ? static_cast<tma_comm *>(ctx) : nullptr;
@@ -2994,42 +2987,32 @@ int tma_ppo_train_epoch_dp(float *params, const tma_policy_dims *d, const tma_ro
         for (int64_t start = 0; start < total; start += batch_size, step++) {
             const int64_t count = start + batch_size <= total ? batch_size : total - start;
             const tma_minibatch mb{nullptr, perm_seed, perm_epoch, start, count, prepared_batch, stats_world > 0 ? count * stats_world : 0};
-            AdamFold f{};
-            if (start > 0) {  // the step of the previous minibatch (index step - 1)
-                const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
-                f = AdamFold{grad, sqp, n_part, bufs[cur][0], bufs[cur][1], bufs[cur][2], bufs[cur ^ 1][0], bufs[cur ^ 1][1],
-                             bufs[cur ^ 1][2], (float)max_grad_norm, (float)(lr / bc1), (float)beta1, (float)beta2, (float)sqrt(bc2), (float)eps,
-                             reinterpret_cast<double *>(ws + WS_NORM_OUT), (float)grad_scale};
-            }
+            const AdamFold f = start > 0 ? chain.fold_for(step - 1) : AdamFold{};  // the step of the previous minibatch
+            GradExtras x;
+            x.fold = start > 0 ? &f : nullptr, x.overwrite = 1;
+            // peer exchange, fused: slab_reduce_kernel stores this rank's reduced gradient into every rank's inbox, the sum-of-squares pass
+            // reads the rank-ordered sum out of this rank's own -- no collective launch between the two
+            PeerPush push;
+            PeerPull pull;
             if (fused) {
-                // peer exchange, fused: slab_reduce_kernel stores this rank's reduced gradient into every rank's inbox, the sum-of-squares pass
-                // reads the rank-ordered sum out of this rank's own -- no collective launch between the two
-                PeerPush push;
-                PeerPull pull;
-                rc = tma_comm_p2p_next(comm, L.P, &push, &pull);
-                if (rc) return rc;
-                rc = minibatch_grad_impl(params, d, rb, &mb, hp, grad, workspace, stream, start > 0 ? &f : nullptr, 1, &push);
-                if (rc) return rc;
-                if (start > 0) cur ^= 1;
+                if ((rc = tma_comm_p2p_next(comm, L.P, &push, &pull))) return rc;
+                x.push = &push;
+            }
+            rc = minibatch_grad_impl(params, d, rb, &mb, hp, grad, workspace, stream, x);
+            if (rc) return rc;
+            if (start > 0) chain.advance();
+            if (fused) {
                 const int timed = tma_comm_time_begin(comm, s);
                 grad_pull_sumsq64_kernel<<<dim3((unsigned)n_part), dim3(64), 0, s>>>(grad, L.P, (float)grad_scale, sqp, pull);
                 TMA_LAUNCH_CHECK();
                 if (timed) tma_comm_time_end(comm, s);
                 continue;
             }
-            rc = minibatch_grad_impl(params, d, rb, &mb, hp, grad, workspace, stream, start > 0 ? &f : nullptr, 1);
-            if (rc) return rc;
-            if (start > 0) cur ^= 1;
             if (allreduce(ctx, grad, L.P) != 0) return fail(TMA_ERR_INVALID, "tma_ppo_train_epoch_dp: the all-reduce callback failed");
             grad_sumsq64_kernel<<<dim3((unsigned)n_part), dim3(64), 0, s>>>(grad, L.P, (float)grad_scale, sqp);
             TMA_LAUNCH_CHECK();
         }
-        const double bc1 = 1.0 - pow(beta1, (double)(step - 1)), bc2 = 1.0 - pow(beta2, (double)(step - 1));
-        opt_scatter_h64_kernel<<<dim3((unsigned)ceil_div(L.P, 256)), dim3(256), 0, s>>>(
-            params, grad, L, sqp, n_part, (float)max_grad_norm, reinterpret_cast<double *>(ws + WS_NORM_OUT), (float)grad_scale, bufs[cur][0],
-            AdamFastRule{exp_avg, exp_avg_sq, bufs[cur][1], bufs[cur][2], (float)beta1, (float)beta2, (float)sqrt(bc2), (float)eps, (float)(lr / bc1)});
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
+        return chain.finish(step - 1);
     }
     for (int64_t start = 0; start < total; start += batch_size, step++) {
         const int64_t count = start + batch_size <= total ? batch_size : total - start;
@@ -3084,7 +3067,7 @@ int tma_ppo_pack_samples(const tma_rollout *rb, const tma_policy_dims *d, float 
     const int rs = rec_floats(L);
     if (rs == 0) return fail(TMA_ERR_INVALID, "tma_ppo_pack_samples: this policy shape has no packed sample records (tma_ppo_packed_floats == 0)");
     const int64_t total = (int64_t)rb->T * rb->N;
-    const Rollout R{rb->obs, rb->actions, rb->log_probs, rb->advantages, rb->returns, rb->T, rb->N, nullptr};
+    const Rollout R = rollout_of(rb, false);
     pack_samples_kernel<<<dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream>>>(R, L.D, rs, total, packed_out);
     TMA_LAUNCH_CHECK();
     return TMA_OK;
@@ -3100,16 +3083,12 @@ int tma_ppo_epoch_prepare(const tma_rollout *rb, const tma_minibatch *epoch, int
     if (total > OFFS_CAP) return fail(TMA_ERR_INVALID, "epoch of %lld samples exceeds the %lld-entry offsets cache", (long long)total, (long long)OFFS_CAP);
     if (batch_size < 256) return fail(TMA_ERR_INVALID, "tma_ppo_epoch_prepare needs batch_size >= 256 (got %lld)", (long long)batch_size);
     if (epoch->start != 0 || epoch->count != total) return fail(TMA_ERR_INVALID, "epoch descriptor must cover [0, T*N)");
-    const PLayout L = layout_of(d);
-    char *ws = static_cast<char *>(workspace);
-    const int64_t offs_base = WS_SLABS + (int64_t)slab_cap(L) * L.P * 4;
-    int stride = (int)ceil_div(batch_size, 1024);
-    if (stride > ADV_BLOCKS) stride = ADV_BLOCKS;
+    const Workspace ws(workspace, layout_of(d));
     const int64_t n_mb = ceil_div(total, batch_size);
     if (n_mb > 65535) return fail(TMA_ERR_INVALID, "too many minibatches per epoch (%lld)", (long long)n_mb);
     Minibatch M{epoch->indices, epoch->perm_seed, epoch->perm_epoch, 0, total, total, nullptr, total, nullptr, 0};
-    adv_partial_kernel<<<dim3(stride, (unsigned)n_mb), dim3(256), 0, (hipStream_t)stream>>>(
-        rb->advantages, M, rb->T, rb->N, reinterpret_cast<double *>(ws + offs_base + OFFS_CAP * 4), reinterpret_cast<int32_t *>(ws + offs_base), batch_size);
+    adv_partial_kernel<<<dim3(Workspace::adv_stride(batch_size), (unsigned)n_mb), dim3(256), 0, (hipStream_t)stream>>>(rb->advantages, M, rb->T, rb->N, ws.epoch_partials(),
+                                                                                                                   ws.offsets(), batch_size);
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
@@ -3120,13 +3099,9 @@ int tma_ppo_epoch_adv_sums(void *workspace, const tma_policy_dims *d, int64_t ba
     if (!workspace || !sums) return fail(TMA_ERR_INVALID, "tma_ppo_epoch_adv_sums: null argument");
     if (batch_size < 256 || total < 1 || total > OFFS_CAP) return fail(TMA_ERR_INVALID, "tma_ppo_epoch_adv_sums: same limits as tma_ppo_epoch_prepare");
     if (direction != 0 && direction != 1) return fail(TMA_ERR_INVALID, "direction must be 0 (export) or 1 (import)");
-    const PLayout L = layout_of(d);
-    char *ws = static_cast<char *>(workspace);
-    const int64_t offs_base = WS_SLABS + (int64_t)slab_cap(L) * L.P * 4;
-    int stride = (int)ceil_div(batch_size, 1024);
-    if (stride > ADV_BLOCKS) stride = ADV_BLOCKS;
+    const int stride = Workspace::adv_stride(batch_size);
     const unsigned n_mb = (unsigned)ceil_div(total, batch_size);
-    double *partials = reinterpret_cast<double *>(ws + offs_base + OFFS_CAP * 4);
+    double *partials = Workspace(workspace, layout_of(d)).epoch_partials();
     if (direction == 0) adv_epoch_sums_kernel<false><<<dim3(n_mb), dim3(64), 0, (hipStream_t)stream>>>(partials, stride, batch_size, total, sums);
     else adv_epoch_sums_kernel<true><<<dim3(n_mb), dim3(64), 0, (hipStream_t)stream>>>(partials, stride, batch_size, total, sums);
     TMA_LAUNCH_CHECK();
@@ -3139,13 +3114,13 @@ int tma_ppo_epoch_adv_sums(void *workspace, const tma_policy_dims *d, int64_t ba
 // that have them, behind the norm partials of the (all-reduced, scaled) gradient -- which a _local call that does not fall through finds where the
 // gradient's reduction left them.  scatter_rule / flat_rule: the update rule (tma_mlp.h) of the scatter kernels and of the other two.
 template <class ScatterRule, class FlatRule>
-static int launch_opt(const OptPlan &p, bool local, float *params, float *grad, const PLayout &L, const ScatterRule &scatter_rule, const FlatRule &flat_rule,
-                      double max_grad_norm, double grad_scale, char *ws, hipStream_t s) {
-    double *partials = reinterpret_cast<double *>(ws + WS_NORM_PART);
-    double *norm_out = reinterpret_cast<double *>(ws + WS_NORM_OUT);
+static int launch_opt(const OptPlan &p, bool local, float *params, float *grad, const ScatterRule &scatter_rule, const FlatRule &flat_rule, double max_grad_norm,
+                      double grad_scale, const Workspace &ws, hipStream_t s) {
+    const PLayout &L = ws.L;
+    double *partials = ws.norm_partials(), *norm_out = ws.norm_out();
     if (p.kernels == OptKernels::ScatterH64 || p.kernels == OptKernels::ScatterWide) {
-        double *sqp = sq_partials(ws, L);
-        const int n_part = (int)ceil_div(L.P, 64);
+        double *sqp = ws.sq_partials();
+        const int n_part = ws.n_sq_partials();
         if (!local || p.falls_through) {
             grad_sumsq64_kernel<<<dim3((unsigned)n_part), dim3(64), 0, s>>>(grad, L.P, (float)grad_scale, sqp);
             TMA_LAUNCH_CHECK();
@@ -3174,13 +3149,11 @@ static int launch_opt(const OptPlan &p, bool local, float *params, float *grad, 
 
 extern "C" {
 
-static int launch_opt_adam(const OptPlan &p, bool local, float *params, float *grad, float *exp_avg, float *exp_avg_sq, const PLayout &L, int64_t step, double lr,
-                           double beta1, double beta2, double eps, double max_grad_norm, double grad_scale, char *ws, hipStream_t s) {
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
-    const AdamFastRule fast{exp_avg, exp_avg_sq, exp_avg, exp_avg_sq, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, (float)step_size};
-    const AdamRule ieee{exp_avg, exp_avg_sq, (float)beta1, (float)beta2, (float)bc2_sqrt, (float)eps, (float)step_size};
-    return launch_opt(p, local, params, grad, L, fast, ieee, max_grad_norm, grad_scale, ws, s);
+static int launch_opt_adam(const OptPlan &p, bool local, float *params, float *grad, int64_t step, const AdamArgs &o, const Workspace &ws, hipStream_t s) {
+    const AdamArgs::Step t = o.at(step);
+    const AdamFastRule fast{o.exp_avg, o.exp_avg_sq, o.exp_avg, o.exp_avg_sq, (float)o.beta1, (float)o.beta2, t.bc2_sqrt, (float)o.eps, t.lr_step};
+    const AdamRule ieee{o.exp_avg, o.exp_avg_sq, (float)o.beta1, (float)o.beta2, t.bc2_sqrt, (float)o.eps, t.lr_step};
+    return launch_opt(p, local, params, grad, fast, ieee, o.max_grad_norm, o.grad_scale, ws, s);
 }
 
 int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg_sq, const tma_policy_dims *d, int64_t step, double lr, double beta1,
@@ -3193,7 +3166,7 @@ int tma_ppo_adam_step(float *params, float *grad, float *exp_avg, float *exp_avg
     const PLayout L = layout_of(d);
     const OptPlan p = plan_opt(L, false, 0, DispatchSwitches{});  // (the global step reads no switch)
     g_disp_opt = p.id;
-    return launch_opt_adam(p, false, params, grad, exp_avg, exp_avg_sq, L, step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, static_cast<char *>(workspace),
+    return launch_opt_adam(p, false, params, grad, step, AdamArgs{exp_avg, exp_avg_sq, lr, beta1, beta2, eps, max_grad_norm, grad_scale}, Workspace(workspace, L),
                            (hipStream_t)stream);
 }
 
@@ -3207,7 +3180,7 @@ int tma_ppo_adam_step_local(float *params, float *grad, float *exp_avg, float *e
     const PLayout L = layout_of(d);
     const OptPlan p = plan_opt(L, true, last_count, read_switches(L, last_count, false));
     g_disp_opt = p.id;
-    return launch_opt_adam(p, true, params, grad, exp_avg, exp_avg_sq, L, step, lr, beta1, beta2, eps, max_grad_norm, 1.0, static_cast<char *>(workspace),
+    return launch_opt_adam(p, true, params, grad, step, AdamArgs{exp_avg, exp_avg_sq, lr, beta1, beta2, eps, max_grad_norm, 1.0}, Workspace(workspace, L),
                            (hipStream_t)stream);
 }
 
@@ -3218,11 +3191,6 @@ static int check_rmsprop(const char *who, double lr, double alpha, double eps) {
     return TMA_OK;
 }
 
-static int launch_opt_rmsprop(const OptPlan &p, bool local, float *params, float *grad, float *square_avg, const PLayout &L, double lr, double alpha, double eps,
-                              double max_grad_norm, double grad_scale, char *ws, hipStream_t s) {
-    const RmspropRule rule{square_avg, (float)alpha, (float)eps, 1.0 - alpha, lr, max_grad_norm};
-    return launch_opt(p, local, params, grad, L, rule, rule, max_grad_norm, grad_scale, ws, s);
-}
 constexpr int32_t OPT_RMSPROP_ID = TMA_DISPATCH_OPT_RMSPROP_SCATTER_H64 - TMA_DISPATCH_OPT_SCATTER_H64;  // the RMSprop ids follow the Adam ids in their order
 
 int tma_rmsprop_step(float *params, float *grad, float *square_avg, const tma_policy_dims *d, double lr, double alpha, double eps, double max_grad_norm,
@@ -3235,7 +3203,8 @@ int tma_rmsprop_step(float *params, float *grad, float *square_avg, const tma_po
     const PLayout L = layout_of(d);
     const OptPlan p = plan_opt(L, false, 0, DispatchSwitches{});
     g_disp_opt = p.id + OPT_RMSPROP_ID;
-    return launch_opt_rmsprop(p, false, params, grad, square_avg, L, lr, alpha, eps, max_grad_norm, grad_scale, static_cast<char *>(workspace), (hipStream_t)stream);
+    const RmspropRule rule{square_avg, (float)alpha, (float)eps, 1.0 - alpha, lr, max_grad_norm};
+    return launch_opt(p, false, params, grad, rule, rule, max_grad_norm, grad_scale, Workspace(workspace, L), (hipStream_t)stream);
 }
 
 int tma_rmsprop_step_local(float *params, float *grad, float *square_avg, const tma_policy_dims *d, double lr, double alpha, double eps, double max_grad_norm,
@@ -3248,7 +3217,8 @@ int tma_rmsprop_step_local(float *params, float *grad, float *square_avg, const 
     const PLayout L = layout_of(d);
     const OptPlan p = plan_opt(L, true, last_count, read_switches(L, last_count, false));
     g_disp_opt = p.id + OPT_RMSPROP_ID;
-    return launch_opt_rmsprop(p, true, params, grad, square_avg, L, lr, alpha, eps, max_grad_norm, 1.0, static_cast<char *>(workspace), (hipStream_t)stream);
+    const RmspropRule rule{square_avg, (float)alpha, (float)eps, 1.0 - alpha, lr, max_grad_norm};
+    return launch_opt(p, true, params, grad, rule, rule, max_grad_norm, 1.0, Workspace(workspace, L), (hipStream_t)stream);
 }
 
 // SB3's A2C `train/policy_loss`, -(advantages * log_prob).mean(), as a SUM over the rollout into statistic slot [0][A2C_POLICY_LOSS_SLOT] (the gradient
@@ -3289,15 +3259,17 @@ int tma_a2c_grad(const float *params, const tma_policy_dims *d, const tma_rollou
     int rc = check_dims(d);
     if (rc) return rc;
     if (!params || !rb || !hp || !grad || !workspace) return fail(TMA_ERR_INVALID, "tma_a2c_grad: null argument");
-    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->advantages || !rb->returns) return fail(TMA_ERR_INVALID, "tma_a2c_grad: rollout view has a null buffer");
+    if ((rc = check_rollout_view(rb, "tma_a2c_grad: "))) return rc;
     if (rb->T < 1 || rb->N < 1) return fail(TMA_ERR_INVALID, "tma_a2c_grad: T and N must be >= 1");
     const int64_t total = (int64_t)rb->T * rb->N;
     const tma_ppo_hparams php{(double)A2C_NO_CLIP, hp->ent_coef, hp->vf_coef, hp->normalize_advantage};
     const tma_minibatch mb{nullptr, 0, 0, 0, total, 0, 0};  // every sample once: the order of the on-device permutation (a sum: SB3's order is the buffer's)
-    rc = minibatch_grad_impl(params, d, rb, &mb, &php, grad, workspace, stream, nullptr, 0, nullptr, nullptr, A2C_ORDERED_TILES);
+    GradExtras x;
+    x.ordered_tiles = A2C_ORDERED_TILES;
+    rc = minibatch_grad_impl(params, d, rb, &mb, &php, grad, workspace, stream, x);
     if (rc) return rc;
     a2c_policy_loss_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(rb->advantages, rb->log_probs, total, hp->normalize_advantage,
-                                                                           reinterpret_cast<double *>(static_cast<char *>(workspace) + WS_STATS));
+                                                                           WorkspaceHeader(workspace).stats());
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
@@ -3338,8 +3310,8 @@ int tma_a2c_iterations_local(tma_env *env, float *params, const tma_policy_dims 
                                 returns, stream)))
             return rc;
         if (records && (rc = tma_ppo_pack_samples(&view, d, packed, stream))) return rc;
-        if (it == n_iterations - 1)  // the statistics a caller reads after the call are those of the call's LAST update, as SB3 logs them
-            TMA_HIP(hipMemsetAsync(static_cast<char *>(workspace) + WS_STATS, 0, sizeof(double) * MAX_GRAD_BLOCKS * 8, s));
+        if (it == n_iterations - 1 && (rc = clear_stats(WorkspaceHeader(workspace), s)))  // the statistics a caller reads after the call are those of the call's LAST update, as SB3 logs them
+            return rc;
         if ((rc = tma_a2c_update_local(params, d, &view, hp, grad, square_avg, lr, alpha, eps, max_grad_norm, workspace, stream))) return rc;
     }
     return TMA_OK;
@@ -3347,8 +3319,7 @@ int tma_a2c_iterations_local(tma_env *env, float *params, const tma_policy_dims 
 
 int tma_ppo_stats_clear(void *workspace, void *stream) {
     if (!workspace) return fail(TMA_ERR_INVALID, "tma_ppo_stats_clear: null argument");
-    TMA_HIP(hipMemsetAsync(static_cast<char *>(workspace) + WS_STATS, 0, sizeof(double) * MAX_GRAD_BLOCKS * 8, (hipStream_t)stream));
-    return TMA_OK;
+    return clear_stats(WorkspaceHeader(workspace), (hipStream_t)stream);
 }
 
 int tma_a2c_stats_fold(const void *staging_host, double *out8_host) {
@@ -3430,14 +3401,13 @@ int tma_ppo_stats_enqueue(void *workspace, void *staging_host, void *stream) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, workspace) == hipSuccess) (void)hipSetDevice(attr.device);
     hipStream_t s = (hipStream_t)stream;
-    char *ws = static_cast<char *>(workspace);
-    double *tmp = static_cast<double *>(staging_host);
-    TMA_HIP(hipMemcpyAsync(tmp, ws + WS_STATS, sizeof(double) * MAX_GRAD_BLOCKS * 8, hipMemcpyDeviceToHost, s));
-    TMA_HIP(hipMemcpyAsync(tmp + MAX_GRAD_BLOCKS * 8, ws + WS_NORM_OUT, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
-    TMA_HIP(hipMemcpyAsync(tmp + MAX_GRAD_BLOCKS * 8 + 2, ws + WS_PERSIST_ERR, sizeof(int), hipMemcpyDeviceToHost, s));
-    TMA_HIP(hipMemsetAsync(ws + WS_PERSIST_ERR, 0, sizeof(int), s));
-    TMA_HIP(hipMemsetAsync(ws + WS_STATS, 0, sizeof(double) * MAX_GRAD_BLOCKS * 8, s));
-    return TMA_OK;
+    const WorkspaceHeader ws(workspace);
+    double *tmp = static_cast<double *>(staging_host);  // {statistic slots | norm_out[2] | persist error word}
+    TMA_HIP(hipMemcpyAsync(tmp, ws.stats(), WorkspaceHeader::STATS_BYTES, hipMemcpyDeviceToHost, s));
+    TMA_HIP(hipMemcpyAsync(tmp + MAX_GRAD_BLOCKS * 8, ws.norm_out(), sizeof(double) * 2, hipMemcpyDeviceToHost, s));
+    TMA_HIP(hipMemcpyAsync(tmp + MAX_GRAD_BLOCKS * 8 + 2, ws.persist_err(), sizeof(int), hipMemcpyDeviceToHost, s));
+    TMA_HIP(hipMemsetAsync(ws.persist_err(), 0, sizeof(int), s));
+    return clear_stats(ws, s);
 }
 
 int tma_ppo_stats_fold(const void *staging_host, double *out8_host) {
@@ -3458,28 +3428,11 @@ int tma_ppo_stats_fold(const void *staging_host, double *out8_host) {
 
 int tma_ppo_pop_stats(void *workspace, double *out8_host, void *stream) {
     if (!workspace || !out8_host) return fail(TMA_ERR_INVALID, "null argument");
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, workspace) == hipSuccess) (void)hipSetDevice(attr.device);  // callers may be worker threads
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<double> tmpv(MAX_GRAD_BLOCKS * 8 + 2);
-    double *tmp = tmpv.data();
-    char *ws = static_cast<char *>(workspace);
-    TMA_HIP(hipMemcpyAsync(tmp, ws + WS_STATS, sizeof(double) * MAX_GRAD_BLOCKS * 8, hipMemcpyDeviceToHost, s));
-    TMA_HIP(hipMemcpyAsync(tmp + MAX_GRAD_BLOCKS * 8, ws + WS_NORM_OUT, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
-    int persist_err = 0;
-    TMA_HIP(hipMemcpyAsync(&persist_err, ws + WS_PERSIST_ERR, sizeof(int), hipMemcpyDeviceToHost, s));
-    TMA_HIP(hipMemsetAsync(ws + WS_PERSIST_ERR, 0, sizeof(int), s));
-    TMA_HIP(hipMemsetAsync(ws + WS_STATS, 0, sizeof(double) * MAX_GRAD_BLOCKS * 8, s));
-    TMA_HIP(hipStreamSynchronize(s));
-    if (persist_err)
-        return fail(TMA_ERR_HIP, "the persistent epoch kernel could not place / synchronise its workgroups on one XCD; parameters of that epoch "
-                                      "were not updated (set TMA_NO_PERSIST=1 to use the per-minibatch launches)");
-    for (int q = 0; q < 6; q++) out8_host[q] = 0.0;
-    for (int b = 0; b < MAX_GRAD_BLOCKS; b++)
-        for (int q = 0; q < 6; q++) out8_host[q] += tmp[b * 8 + q];
-    out8_host[6] = tmp[MAX_GRAD_BLOCKS * 8];
-    out8_host[7] = tmp[MAX_GRAD_BLOCKS * 8 + 1];
-    return TMA_OK;
+    std::vector<char> staging((size_t)tma_ppo_stats_staging_bytes());
+    const int rc = tma_ppo_stats_enqueue(workspace, staging.data(), stream);  // (makes the workspace's device current: callers may be worker threads)
+    if (rc) return rc;
+    TMA_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return tma_ppo_stats_fold(staging.data(), out8_host);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // and pure host functions (no HIP call, no global, no environment read), so that the selection is checkable without a GPU
 // (tma_debug_plan_dispatch).  The launchers of tma_policy.hip (and tma_bf16.hip's, for plan_grad_bf) validate, call plan_*, record plan.id and
 // launch what the plan says: every threshold and cap of the selection is written here, once.
-// Included inside namespace tma by tma_policy.hip, after tma_ppo_types.h, W2_DEFER_ROWS and tma_wide_bf16.h.
+// Included inside namespace tma by tma_policy.hip, after tma_ppo_types.h and tma_wide_bf16.h.
 #pragma once
 
 // Every environment switch the three dispatchers read (filled by read_switches in tma_policy.hip; tools/test_switches.sh runs each of them)
@@ -46,8 +46,8 @@ inline int grad_wide_smem_bytes(const PLayout &L, int nw = 4) {
 inline bool wide_width(const PLayout &L) { return L.H == 128 || L.H == 192 || L.H == 256; }
 // shapes the f32 column-parallel gradient kernel can take (from how many samples on it does: plan_grad, plan_opt)
 inline bool grad_wide_f32_shape(const PLayout &L) { return !L.bf16 && wide_width(L) && grad_wide_smem_bytes(L) <= LDS_LIMIT; }
-// the dW2 deferral buffer ([net][h1 | dz2][W2_DEFER_ROWS][H] floats) lies behind slab 64 of the workspace's slab area: it must fit there
-inline bool w2_defer_fits(const PLayout &L) { return (int64_t)64 * L.P + 4 * (int64_t)W2_DEFER_ROWS * L.H <= (int64_t)slab_cap(L) * L.P; }
+// the dW2 deferral buffer overlays the upper slabs of the workspace's slab area (Workspace::defer_w2): it must fit there
+inline bool w2_defer_fits(const PLayout &L) { return Workspace::defer_w2_fits(L); }
 // slab_reduce_kernel / wide_small_reduce_kernel leave one sum-of-squares partial per 64 parameters where the workspace has slots for them
 inline bool sq_partials_fit(const PLayout &L) { return ceil_div(L.P, 64) <= WIDE_SQ_SLOTS; }
 

@@ -1,40 +1,14 @@
-// tma_ppo_types.h -- types and workspace layout shared by the translation units of the PPO update (tma_policy.hip, tma_h64.hip).
+// tma_ppo_types.h -- types shared by the translation units of the PPO update (tma_policy.hip, tma_h64.hip, ...); the workspace's layout and
+// the capacities that size it are tma_workspace.h's.
 #pragma once
-#include "tma_mlp.h"
+#include "tma_workspace.h"
+
+#include <cmath>
 
 namespace tma {
 
-constexpr int WS_ADV = 0;             // float[2]: minibatch advantage mean, std
-constexpr int WS_NORM_PART = 64;      // byte offset of double[256] grad sum-of-squares partials
-constexpr int WS_NORM_OUT = 64 + 256 * 8;  // double[2]: total grad norm, clip coefficient
-constexpr int WS_PERSIST_ERR = 2176;  // int32: set when the persistent epoch kernel (tma_h64p.hip) gave up on a wait; read + cleared by tma_ppo_pop_stats
-constexpr int WS_PERSIST_SNAP = 2560;  // double[8][8]: the persistent epoch launch's statistic slots before the launch (restored on fallback)
-constexpr int WS_ADV_PART = 4096;     // byte offset of double[128][2] advantage (sum, sumsq) partials
-constexpr int WS_STATS = 8192;        // byte offset of double[MAX_GRAD_BLOCKS][8] loss statistic slots
-constexpr int MAX_GRAD_BLOCKS = 2048;
-constexpr int64_t WS_SLABS = WS_STATS + (int64_t)MAX_GRAD_BLOCKS * 8 * 8;  // byte offset of float[H64_BLOCKS][P] partial-gradient slabs
-constexpr int H64_BLOCKS = 128;  // block PAIRS (policy block + value block): 256 blocks = one per CU, a single round
-constexpr int64_t WS_BYTES = WS_SLABS;
-constexpr int BF_SLABS = 160;  // column-parallel kernels: up to 160 policy-net blocks (+ value-net blocks sharing the first slabs)
-constexpr int64_t OFFS_CAP = 1 << 22;
-constexpr int64_t EPOCH_PART_BYTES = ((OFFS_CAP / 1024) + (OFFS_CAP / 256)) * 16;  // advantage partials of every minibatch of an epoch
-constexpr int WIDE_SQ_SLOTS = 8192;  // sum-of-squares partials of slab_reduce_kernel for policies beyond the 256 slots at WS_NORM_PART  // sample offsets of one minibatch cached behind the slabs (int32 each) when count <= OFFS_CAP
-
-constexpr int64_t DZ1_CAP = 1 << 18;  // samples per minibatch whose dz1 images fit the workspace cache (bf16 two-pass layouts only)
-// (round 6: ... and 97 .. 128 observations with a Box head at H = 256 -- Ant-v5's 105 -- as four layer-1 k-steps)
-static inline bool bf_two_pass(const PLayout &L) {
-    return L.bf16 && ((L.D > 32 && L.D <= 64) || (L.D > 160 && L.D <= 192) || (L.D > 96 && L.D <= 128 && L.cont && L.H == 256));
-}
-// (round 6: ... and 97 .. 112 observations -- the reference's ant task, Ant-v5's 105 -- with Box heads at H = 256: seven k-tiles)
-static inline bool f32_two_pass(const PLayout &L) {
-    return !L.bf16 && L.fr_pi >= 0 && ((L.D > 160 && L.D <= 176) || (L.D > 96 && L.D <= 112 && L.cont && L.H == 256));
-}
-static inline int64_t dz1_cache_bytes(const PLayout &L) {  // both nets; bf16 images or f32 MFMA operands
-    return bf_two_pass(L) ? 2 * DZ1_CAP * L.H * 2 : (f32_two_pass(L) ? 2 * DZ1_CAP * L.H * 4 : 0);
-}
 // floats per packed sample record {obs padded to a multiple of 4 | log_prob, advantage, action bits, return}; 0: shape without them
 static inline int rec_floats(const PLayout &L) { return (L.img_pi >= 0 && L.D <= 8) ? ((L.D + 3) & ~3) + 4 : 0; }
-static inline int slab_cap(const PLayout &L) { return (L.bf16 || L.fr_pi >= 0) ? BF_SLABS : H64_BLOCKS; }  // partial-gradient slabs in the workspace
 
 // What the bf16 column-parallel gradient launches for a shape (plan_grad_bf in tma_policy_plan.h decides, tma_launch_grad_wide_bf launches):
 // ppo_grad_wide_bf_kernel<cont, H / 64, mt, kt1c, ks1c, PASS, waves>
@@ -68,7 +42,6 @@ __device__ __forceinline__ int64_t sample_offset(const Minibatch &mb, int64_t j,
 }
 
 // ---- advantage pre-pass: sample offsets + (sum, sum of squares) partials of one minibatch ----
-constexpr int ADV_BLOCKS = 128;  // partial blocks per minibatch at the most (1 024 rows each up to 131 072 rows, longer slices beyond)
 // Partial block `pb` of the `nb` a minibatch is split into: rows [pb * per, (pb + 1) * per) of it, thread tid < 256 takes rows j0 + tid,
 // + 256, ... in that order into ONE f64 (sum, sum of squares) pair; one shuffle tree per wave, the four waves' pairs as (0 + 1) + (2 + 3).
 // The ONE body of adv_partial_kernel (tma_policy.hip) and of the tail phase of the H = 64 gradient kernel's value blocks (tma_h64.hip),
@@ -130,7 +103,7 @@ __device__ __forceinline__ void adv_partial_block(const float *__restrict__ adv,
 struct PrepNext {
     const float *adv;             // the advantages plane [T][N]
     int32_t *offs_out;            // offs_out[j] = buffer offset of row j of that minibatch
-    double *partials_out;         // its (sum, sum of squares) partials: min(ceil(count / 1024), ADV_BLOCKS) pairs; untouched without want_sums
+    double *partials_out;         // its (sum, sum of squares) partials: Workspace::adv_stride(count) pairs; untouched without want_sums
     uint32_t perm_seed, perm_epoch;
     int64_t start, count, total;  // rows [start, start + count) of the (perm_seed, perm_epoch) permutation; count == 0: nothing to do
     int64_t N;
@@ -166,6 +139,32 @@ struct AdamFold {
     float max_norm, lr_step, beta1, beta2, bc2_sqrt, eps;  // (bc2_sqrt = sqrt(1 - beta2^t), lr_step = lr / (1 - beta1^t))
     double *norm_out;        // [2] total gradient norm, clip coefficient (statistics)
     float scale;             // factor on the gradient before the clip (1 on one GPU; 1 / world on the all-reduced SUM, tma_ppo_train_epoch_dp)
+};
+
+// The Adam arguments of an update driver, and the one place the bias-correction pair of a step is worked out (on the host, in double).
+struct AdamArgs {
+    float *exp_avg, *exp_avg_sq;
+    double lr, beta1, beta2, eps, max_grad_norm;
+    double grad_scale;  // factor on the gradient before the clip: 1 on one GPU, 1 / world on an all-reduced sum
+    struct Step { float lr_step, bc2_sqrt; };  // lr / (1 - beta1^t), sqrt(1 - beta2^t)
+    Step at(int64_t step) const {
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        return Step{(float)(lr / bc1), (float)sqrt(bc2)};
+    }
+};
+
+// What every epoch driver of tma_policy.hip works on (the extern "C" entry points unpack their flat arguments into one of these, once)
+struct EpochJob {
+    float *params;
+    const tma_policy_dims *d;
+    PLayout L;
+    const tma_rollout *rb;  // checked view (check_rollout_view); the kernels' Rollout is rollout_of(rb, ...)
+    uint32_t perm_seed;
+    int64_t batch_size;
+    const tma_ppo_hparams *hp;
+    float *grad;
+    Workspace ws;
+    hipStream_t s;
 };
 
 struct Net {
@@ -278,22 +277,18 @@ int tma_launch_grad_h64(const float *params, const tma::PLayout &L, const tma::R
 // true: a minibatch of `count` rows runs on the eight-wave kernel, whose value blocks can carry a PrepNext (and whose launch may be handed one)
 bool tma_grad_h64_carries_prep(int64_t count);
 
-// tma_h64p.hip: one whole epoch at batch_size = 256 as a single persistent launch (H = 64 fast-path layouts)
+// tma_h64p.hip: `total` samples (whole epochs, prepared in job.ws) at batch_size = 256 as a single persistent launch (H = 64 fast-path layouts)
 bool tma_epoch_h64p_eligible(const tma::PLayout &L, int64_t batch_size, int64_t total);
-int tma_launch_epoch_h64p(float *params, const tma::PLayout &L, const tma::Rollout &R, const tma::HParams &hp, const int32_t *offs,
-                          const double *adv_part, int adv_stride, int64_t total, int64_t batch_size, float *exp_avg, float *exp_avg_sq,
-                          int64_t first_step, double lr, double beta1, double beta2, double eps, double max_grad_norm, char *ws, hipStream_t s);
+int tma_launch_epoch_h64p(const tma::EpochJob &job, const tma::Rollout &R, const tma::HParams &hp, int64_t total, int64_t first_step, const tma::AdamArgs &opt);
 
 // tma_h256p.hip: the same for the reference's default 256 x 256 policy (exact f32, Discrete heads, observations <= 32): 2 x 32 workgroups on two XCDs
 bool tma_epoch_h256p_eligible(const tma::PLayout &L, int64_t batch_size, int64_t total);
-int tma_launch_epoch_h256p(float *params, const tma::PLayout &L, const tma::Rollout &R, const tma::HParams &hp, const int32_t *offs,
-                           const double *adv_part, int adv_stride, int64_t total, int64_t batch_size, float *exp_avg, float *exp_avg_sq,
-                           int64_t first_step, double lr, double beta1, double beta2, double eps, double max_grad_norm, char *ws, hipStream_t s);
+int tma_launch_epoch_h256p(const tma::EpochJob &job, const tma::Rollout &R, const tma::HParams &hp, int64_t total, int64_t first_step, const tma::AdamArgs &opt);
 
-// tma_bf16.hip: the column-parallel bf16-MFMA gradient kernel (hidden 128 / 192 / 256); `ws` is the update workspace (dz1 cache).  It launches
-// what `plan` says (plan_grad_bf, tma_policy_plan.h) and decides nothing itself
-int tma_launch_grad_wide_bf(const float *params, const tma::PLayout &L, const tma::Rollout &R, const tma::Minibatch &M, const tma::HParams &hpar,
-                            const float *ws_adv, float *slabs, double *slots, char *ws, const tma::GradBfPlan &plan, hipStream_t s);
+// tma_bf16.hip: the column-parallel bf16-MFMA gradient kernel (hidden 128 / 192 / 256) on the update workspace `ws` (advantage statistics,
+// slabs, statistic slots, dz1 cache).  It launches what `plan` says (plan_grad_bf, tma_policy_plan.h) and decides nothing itself
+int tma_launch_grad_wide_bf(const float *params, const tma::Rollout &R, const tma::Minibatch &M, const tma::HParams &hpar, const tma::Workspace &ws,
+                            const tma::GradBfPlan &plan, hipStream_t s);
 // tma_bf16.hip: the three-term bf16 split of the 256-wide f32 update (mfma_dtype = 2; tma_split3.h) and the rebuild of its weight planes
 int tma_launch_grad_split3(const float *params, const tma::PLayout &L, const tma::Rollout &R, const tma::Minibatch &M, const tma::HParams &hpar, float *slabs,
                            double *slots, int *n_pi_out, int *n_vf_out, hipStream_t s);
