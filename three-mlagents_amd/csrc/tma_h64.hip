@@ -11,6 +11,22 @@ namespace tma {
 
 #ifdef TMA_H64_TICKS
 static __device__ unsigned long long g_h64_tail_ticks;  // diagnostic build: the value blocks' tail phase (tma_debug_h64_tail_ticks)
+// ... and the edges of a launch, block pair 0 (tma_debug_h64_ticks returns them behind g_h64_ticks).  Slots 0..4: wave 0's clock since the
+// kernel's start when (0) the first tile's records are issued -- its sample offset is back --, (1) its layer-2 block is updated -- its
+// optimizer state is back and consumed --, (2) the clip coefficient is published (first barrier), (3) the image stores are issued, (4) the advantage statistics are published (the
+// last barrier in front of the loop).  Slots 8..15: loop-end clock of wave w minus wave 0's (two's complement).  The prologue stamps stay
+// in registers until the loop starts: a stamp is one s_memtime, not a global read-add-write.
+static __device__ unsigned long long g_h64_edge_ticks[2][16];
+#ifndef TMA_H64_TICK_PAIR
+#define TMA_H64_TICK_PAIR 0  // the stamped block pair (pair 0 also writes the next optimizer state: -DTMA_H64_TICK_PAIR=1 shows a pair that does not)
+#endif
+struct ProTicks {
+    unsigned long long t[5];
+};
+#define H64_PRO_STAMP(pt, i) ((pt).t[i] = __builtin_amdgcn_s_memtime())
+#else
+struct ProTicks {};
+#define H64_PRO_STAMP(pt, i) do {} while (0)
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -329,132 +345,160 @@ __device__ __forceinline__ void flush_all_t(float *stage, int wave, int lane, Ne
 }
 
 
-// DIRECT (small minibatches): 4-wave blocks, one wave per SIMD, one tile per wave; the block reduction runs over four copies.
-// LDS image slots of parameter x of one net (flat [W1t | b1 | W2t | b2 | W3t | b3] order): the image part of scatter_derived_h64
-__device__ __forceinline__ void image_store_h64(float *wimg, int D, int n_out, int x, float val) {
-    constexpr int H = 64;
-    if (x < D * H) {
-        const int k = x >> 6, n = x & 63;
-        wimg[IMG_W1 + k * 64 + (n & 15) * 4 + (n >> 4)] = val;
-        return;
-    }
-    x -= D * H;
-    if (x < H) {
-        wimg[IMG_B1 + x] = val;
-        return;
-    }
-    x -= H;
-    if (x < H * H) {
-        const int k = x >> 6, n = x & 63;
-        wimg[IMG_W2F + k * 64 + (n & 15) * 4 + (n >> 4)] = val;
-        wimg[IMG_W2B + n * 64 + (k & 15) * 4 + (k >> 4)] = val;
-        return;
-    }
-    x -= H * H;
-    if (x < H) {
-        wimg[IMG_B2 + x] = val;
-        return;
-    }
-    x -= H;
-    if (x < H * n_out) {
-        const int k = x / n_out, a = x - k * n_out;
-        wimg[IMG_W3F + k * 16 + a] = val;
-        wimg[IMG_W3B + a * 64 + (k & 15) * 4 + (k >> 4)] = val;
-        return;
-    }
-    x -= H * n_out;
-    if (x < n_out) wimg[IMG_B3 + x] = val;
+// Workgroup barrier that orders LDS accesses only (s_waitcnt lgkmcnt(0) + s_barrier): what the prologue publishes -- the clip coefficient, the
+// advantage statistics, the weight image -- lives in LDS, and __syncthreads() would also wait out every global access in flight: in workgroup 0
+// of each net the 30 stores per thread of the next optimizer state, elsewhere the first tile's records.  Nothing in the kernel reads those
+// stores back; they drain under the first tile.
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
+
+// LDS image slots of parameter y of one net, y counting the flat [W1t | b1 | W2t | b2 | W3t | b3] order WITHOUT the W2t block (the image part of
+// scatter_derived_h64): s1 always, s2 (the head's input-gradient copy) or -1.  One select chain instead of a branch per region: the lanes of a wave
+// sit in different regions.  D and n_out are compile-time constants in the headline instantiation (the value net's n_out always is), so the head's
+// division is by a constant there.
+__device__ __forceinline__ void image_slots_h64(int D, int n_out, int y, int &s1, int &s2) {
+    const int w1e = D * 64, w3s = w1e + 128, z = y - w3s, zc = z < 0 ? 0 : z;
+    const int k1 = y >> 6, n1 = y & 63;
+    const int k3 = zc / n_out, a3 = zc - k3 * n_out;
+    const bool head = z >= 0 && z < 64 * n_out;
+    s1 = y < w1e ? IMG_W1 + k1 * 64 + (n1 & 15) * 4 + (n1 >> 4)
+                 : (z < 0 ? IMG_B1 + (y - w1e)  // b1, b2: IMG_B2 == IMG_B1 + 64
+                          : (head ? IMG_W3F + k3 * 16 + a3 : IMG_B3 + (z - 64 * n_out)));
+    s2 = head ? IMG_W3B + a3 * 64 + (k3 & 15) * 4 + (k3 >> 4) : -1;
+}
+static_assert(IMG_B2 == IMG_B1 + 64, "image_slots_h64 addresses b1 and b2 as one region");
 
 // The pending optimizer step of AdamFold for this workgroup's net, results into the LDS image (and, from workgroup 0 of the net, into the
 // next half of the state double buffer).  clip_grad_norm_ + Adam exactly as opt_scatter_h64_kernel: same fold of the norm partials, same
-// adam_update_h64.  Ownership is chosen for the LDS stores: threads 0..255 own one 4 x 4 block of W2t each -- rows kr + 16 jj, columns
-// nr + 16 j -- which is one float4 per row of the forward image ([k][n & 15][n >> 4]) and one float4 per column of the input-gradient image
-// ([n][k & 15][k >> 4]): 8 ds_write_b128 per thread instead of 32 scalar stores, half of them 64-way bank conflicts (a wave covers 8 nr x 8
-// kr, so a b128 store meets 8 lanes per bank group: twice the ideal 4 passes).  The other <= 2 192 parameters (W1t, the biases, the head)
-// go round-robin over the remaining threads (all of them in a 256-thread workgroup).  Every load is issued before the clip coefficient is
-// folded, so the prologue is one memory round trip.
-template <bool IS_PI>
-__device__ __forceinline__ void fold_adam_into_image(const AdamFold &f, const PLayout &L, float *wimg, int block_net) {
-    __shared__ double fold_red[4];
-    __shared__ float fold_coef;
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int base = IS_PI ? L.pW1t : L.vW1t, pn = (IS_PI ? L.vW1t : L.log_std) - base, n_out = IS_PI ? L.A : 1;
-    const int w2_off = L.D * 64 + 64, n_other = pn - 4096;
-    const bool own_w2 = tid < 256;
-    const int o_base = nthr > 256 ? 256 : 0, o_thr = nthr - o_base, o_tid = tid - o_base;
-    const int nr = ((tid >> 6) & 1) * 8 + (tid & 7), kr = ((tid >> 7) & 1) * 8 + ((tid >> 3) & 7);
-    constexpr int NO = 9;  // other parameters per thread (2 192 / 256 < 9)
-    float g2[4][4], m2[4][4], v2[4][4], p2[4][4], go[NO], mo[NO], vo[NO], po[NO];
-    if (own_w2) {
+// adam_update_h64.  Two halves: issue() only issues loads -- no address in it depends on a loaded value, so the caller puts it in front of
+// its first memory wait -- and finish() consumes them.
+// Ownership is even.  W2t: a wave covers 8 nr x 8 kr (tid & 7 -> nr, so a load instruction reads 32-byte runs of 8 rows); a thread owns
+// columns n = nr + 16 j, j < 4, of rows k = kr + 16 (KB h + jj), jj < KB.  NTHR = 512: KB = 2, h = tid >> 8 -- two ds_write_b128 into the
+// forward image ([k][n & 15][n >> 4]: row k, slot nr) and four ds_write_b64 into the input-gradient image ([n][k & 15][k >> 4]: row n, slot
+// kr, pair h).  NTHR = 256 (ppo_grad_h64_small_kernel): KB = 4, one 4 x 4 block per thread as before, eight ds_write_b128.  Banks by the LDS
+// table of MI355X_MICROARCH.md ((a / 4) mod 32 for both stores): a b128 store is served in groups of 8 contiguous lanes -- forward image: eight
+// distinct 16-byte slots nr * 4 of one row, conflict-free; a b64 store in groups of 16 contiguous lanes -- input-gradient image: 8 rows n (64
+// floats apart: one bank) x 2 slots kr, 8-way.  The same LDS cycles per CU as the 4 x 4 blocks on 256 of 512 threads spent (their b128
+// stores into that image were 8-way as well), on half the critical thread's work.  The conflict-free assignment (16 contiguous lanes on 16
+// distinct (kr, h)) puts every lane of a load instruction on a row of its own: built and stamped (profiles/r10_h64_ticks_scatter.txt; that
+// build also still drained the state in front of the first tile's records, so the file does not separate the two effects) and not pursued --
+// the transposed image makes one of the three, loads or either image's stores, uncoalesced or conflicted.
+// The other <= 2 192 parameters (W1t, the biases, the head) go round-robin over all threads: NO = 2 / 1 per thread (policy / value net) in
+// the headline instantiation, 5 / 9 at runtime widths (D = 16, A = 16) on 512 / 256 threads.
+// The norm partials are folded by wave 0 alone -- the four shuffle trees the first four waves used to run, combined in the same order --
+// so the clip coefficient needs no barrier in front of it: thread 0 forms it while the other waves' optimizer state is still on its way,
+// and the caller's advantage statistics (lane 0 of another wave) are published by the same barrier.
+template <bool IS_PI, int DT, int AT, int NTHR>
+struct AdamImageFold {
+    static_assert(NTHR == 512 || NTHR == 256, "eight-wave or four-wave workgroups");
+    static constexpr int KB = NTHR == 512 ? 2 : 4;  // W2t rows per thread
+    static constexpr int D_MAX = DT > 0 ? DT : 16, A_MAX = IS_PI ? (AT > 0 ? AT : 16) : 1;
+    static constexpr int NO = (D_MAX * 64 + 128 + 65 * A_MAX + NTHR - 1) / NTHR;  // other parameters per thread
+    float g2[KB][4], m2[KB][4], v2[KB][4], p2[KB][4], go[NO], mo[NO], vo[NO], po[NO];
+    double sq[4];
+    int base, D, n_out, w2_off, n_other, nr, kr, k0;
+
+    __device__ __forceinline__ void issue(const AdamFold &f, const PLayout &L) {
+        const int tid = threadIdx.x;
+        base = IS_PI ? L.pW1t : L.vW1t;
+        D = DT > 0 ? DT : L.D, n_out = IS_PI ? (AT > 0 ? AT : L.A) : 1;
+        w2_off = D * 64 + 64, n_other = D * 64 + 128 + 65 * n_out;
+        nr = ((tid >> 6) & 1) * 8 + (tid & 7), kr = ((tid >> 7) & 1) * 8 + ((tid >> 3) & 7), k0 = kr + 32 * (tid >> 8);  // (tid >> 8: h, 0 on 256 threads)
+        if (tid < 64) {  // (the early consumer first: vmcnt retires loads in order)
 #pragma unroll
-        for (int jj = 0; jj < 4; jj++)
+            for (int u = 0; u < 4; u++) sq[u] = f.sq_part[tid + 64 * u < f.n_part ? tid + 64 * u : 0];  // (clamped here, masked in clip_coef: a load under
+                                                                                                    //  a branch of its own makes the first wait drain everything)
+        }
+    }
+    __device__ __forceinline__ void issue_state(const AdamFold &f) {
+        const int tid = threadIdx.x;
+#pragma unroll
+        for (int jj = 0; jj < KB; jj++)
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const int e = base + w2_off + (kr + 16 * jj) * 64 + nr + 16 * j;
+                const int e = base + w2_off + (k0 + 16 * jj) * 64 + nr + 16 * j;
                 g2[jj][j] = f.grad[e], m2[jj][j] = f.m_cur[e], v2[jj][j] = f.v_cur[e], p2[jj][j] = f.p_cur[e];
             }
-    }
-    if (o_tid >= 0) {
 #pragma unroll
         for (int i = 0; i < NO; i++) {
-            const int y = o_tid + i * o_thr, x = y < w2_off ? y : y + 4096, e = base + (y < n_other ? x : 0);
+            const int y = tid + i * NTHR, x = y < w2_off ? y : y + 4096, e = base + (y < n_other ? x : 0);
             go[i] = f.grad[e], mo[i] = f.m_cur[e], vo[i] = f.v_cur[e], po[i] = f.p_cur[e];
         }
     }
-    if (tid < 256) {
-        double a = tid < f.n_part ? f.sq_part[tid] : 0.0;
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-        if ((tid & 63) == 0) fold_red[tid >> 6] = a;
-    }
     // image regions no parameter lands in (rows k >= D of W1, head columns >= n_out, padding) are zeros in the staged image; LDS is not
-    for (int e = tid; e < 1024; e += nthr) wimg[IMG_W1 + e] = 0.0f, wimg[IMG_W3F + e] = 0.0f, wimg[IMG_W3B + e] = 0.0f;
-    if (tid < 32) wimg[IMG_B3 + tid] = 0.0f;
-    __syncthreads();
-    if (tid == 0) {
-        const double tot = ((fold_red[0] + fold_red[1]) + fold_red[2]) + fold_red[3];
-        const float total_norm = (float)sqrt(tot);
-        float coef = f.max_norm / (total_norm + 1e-6f);
-        coef = coef > 1.0f ? 1.0f : coef;
-        if (f.max_norm <= 0.0f) coef = 1.0f;
-        fold_coef = coef;
-        if (IS_PI && block_net == 0) f.norm_out[0] = (double)total_norm, f.norm_out[1] = (double)coef;
-    }
-    __syncthreads();
-    const float coef = fold_coef, inv_bc2 = 1.0f / f.bc2_sqrt;
-    const bool keep = block_net == 0;
-    if (own_w2) {
+    __device__ __forceinline__ void zero_fill(float *wimg) const {
+        const int tid = threadIdx.x;
 #pragma unroll
-        for (int jj = 0; jj < 4; jj++)
+        for (int i = 0; i < 1024 / NTHR; i++) {  // (straight-line: a loop between the loads and their first wait makes the compiler drain them all)
+            const int e = tid + i * NTHR;
+            wimg[IMG_W1 + e] = 0.0f, wimg[IMG_W3F + e] = 0.0f, wimg[IMG_W3B + e] = 0.0f;
+        }
+        if (tid < 32) wimg[IMG_B3 + tid] = 0.0f;
+    }
+    // wave 0: the clip coefficient into *coef_out (published by the caller's barrier)
+    __device__ __forceinline__ void clip_coef(const AdamFold &f, int block_net, float *coef_out) const {
+        if (threadIdx.x < 64) {
+            double r[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                r[u] = (int)threadIdx.x + 64 * u < f.n_part ? sq[u] : 0.0;
+                for (int o = 32; o > 0; o >>= 1) r[u] += __shfl_down(r[u], o, 64);
+            }
+            if (threadIdx.x == 0) {
+                const double tot = ((r[0] + r[1]) + r[2]) + r[3];
+                const float total_norm = (float)sqrt(tot);
+                float coef = f.max_norm / (total_norm + 1e-6f);
+                coef = coef > 1.0f ? 1.0f : coef;
+                if (f.max_norm <= 0.0f) coef = 1.0f;
+                *coef_out = coef;
+                if (IS_PI && block_net == 0) f.norm_out[0] = (double)total_norm, f.norm_out[1] = (double)coef;
+            }
+        }
+    }
+    // behind the barrier that published the coefficient (and the zero fill): the step, the image, the next half of the state
+    __device__ __forceinline__ void finish(const AdamFold &f, float *wimg, int block_net, float coef, [[maybe_unused]] ProTicks &pt) {
+        const int tid = threadIdx.x;
+        const float inv_bc2 = 1.0f / f.bc2_sqrt;
+        const bool keep = block_net == 0;
+#pragma unroll
+        for (int jj = 0; jj < KB; jj++)
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const float gv = (g2[jj][j] * f.scale) * coef;
                 p2[jj][j] = adam_update_h64(p2[jj][j], gv, m2[jj][j], v2[jj][j], f.beta1, f.beta2, inv_bc2, f.eps, f.lr_step);
                 if (keep) {
-                    const int e = base + w2_off + (kr + 16 * jj) * 64 + nr + 16 * j;
+                    const int e = base + w2_off + (k0 + 16 * jj) * 64 + nr + 16 * j;
                     f.p_nxt[e] = p2[jj][j], f.m_nxt[e] = m2[jj][j], f.v_nxt[e] = v2[jj][j];
                 }
             }
+        H64_PRO_STAMP(pt, 1);  // (the layer-2 block is updated: this wave's optimizer state has been consumed)
 #pragma unroll
-        for (int jj = 0; jj < 4; jj++)  // forward image: row k = kr + 16 jj, slot [nr][j = 0..3]
-            *reinterpret_cast<float4 *>(wimg + IMG_W2F + (kr + 16 * jj) * 64 + nr * 4) = float4{p2[jj][0], p2[jj][1], p2[jj][2], p2[jj][3]};
+        for (int jj = 0; jj < KB; jj++)  // forward image: row k = k0 + 16 jj, slot [nr][j = 0..3]
+            *reinterpret_cast<float4 *>(wimg + IMG_W2F + (k0 + 16 * jj) * 64 + nr * 4) = float4{p2[jj][0], p2[jj][1], p2[jj][2], p2[jj][3]};
 #pragma unroll
-        for (int j = 0; j < 4; j++)  // input-gradient image: row n = nr + 16 j, slot [kr][jj = 0..3]
-            *reinterpret_cast<float4 *>(wimg + IMG_W2B + (nr + 16 * j) * 64 + kr * 4) = float4{p2[0][j], p2[1][j], p2[2][j], p2[3][j]};
-    }
-    if (o_tid >= 0) {
+        for (int j = 0; j < 4; j++) {  // input-gradient image: row n = nr + 16 j, slot [kr][k >> 4 = (k0 >> 4) + jj]
+            float *dst = wimg + IMG_W2B + (nr + 16 * j) * 64 + kr * 4 + (k0 >> 4);
+            if constexpr (KB == 2) *reinterpret_cast<float2 *>(dst) = float2{p2[0][j], p2[1][j]};
+            else *reinterpret_cast<float4 *>(dst) = float4{p2[0][j], p2[1][j], p2[2][j], p2[3][j]};
+        }
 #pragma unroll
         for (int i = 0; i < NO; i++) {
-            const int y = o_tid + i * o_thr, x = y < w2_off ? y : y + 4096;
+            const int y = tid + i * NTHR, x = y < w2_off ? y : y + 4096;
             if (y < n_other) {
                 const float gv = (go[i] * f.scale) * coef;
                 const float pnew = adam_update_h64(po[i], gv, mo[i], vo[i], f.beta1, f.beta2, inv_bc2, f.eps, f.lr_step);
-                image_store_h64(wimg, L.D, n_out, x, pnew);
+                int s1, s2;
+                image_slots_h64(D, n_out, y, s1, s2);
+                wimg[s1] = pnew;
+                if (s2 >= 0) wimg[s2] = pnew;
                 if (keep) f.p_nxt[base + x] = pnew, f.m_nxt[base + x] = mo[i], f.v_nxt[base + x] = vo[i];
             }
         }
     }
-}
+};
 
 template <bool IS_PI, int DT, bool DIRECT = false, int AT = 0>  // AT > 0: compile-time head width of the policy net, 0: runtime L.A
 __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params, const PLayout &L, const Rollout &rb, const Minibatch &mb,
@@ -483,7 +527,30 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
         const int64_t jc = j < mb.count ? j : 0;
         return mb.offs ? mb.offs[jc] : (int32_t)sample_offset(mb, mb.start + jc, rb.T, rb.N);
     };
+    // ---- prologue, one batch of loads: every load whose address depends on no loaded value is issued before the first wait, early consumers
+    // first (vmcnt retires loads in order) -- the advantage partials, the norm partials, the first two sample offsets, then the optimizer state.
+    // The lines were just written by slab_reduce_kernel, the previous launch or its tail on other XCDs: each wait in series is a miss.
+    constexpr int NTHR = DIRECT ? 256 : 512;
+    // the advantage statistics belong to lane 0 of the block's LAST wave (the fewest round-robin parameters), the clip coefficient to thread 0:
+    // two scalar sections on two SIMDs under one barrier
+    const bool adv_wave = IS_PI && hp.normalize_advantage && wave == NTHR / 64 - 1;
+    constexpr int ADV_U = ADV_BLOCKS / 64;  // partials per lane (n_part <= ADV_BLOCKS)
+    double ap_a[ADV_U], ap_b[ADV_U];
+    if (adv_wave && n_part > 0) {  // (clamped addresses, masked when folded)
+#pragma unroll
+        for (int u = 0; u < ADV_U; u++) {
+            const int k = lane + 64 * u < n_part ? lane + 64 * u : 0;
+            ap_a[u] = adv_part[2 * k], ap_b[u] = adv_part[2 * k + 1];
+        }
+    }
+    const bool folded = fold.grad != nullptr;  // (uniform) the previous minibatch's optimizer step rides in front of this launch
+    AdamImageFold<IS_PI, DT, AT, NTHR> af;
+    if (folded) af.issue(fold, L);
+    // (both offsets in front of the optimizer state: without cached offsets offset_of evaluates the permutation in loops, and the compiler
+    //  drains every load in flight in front of a loop)
     int32_t nx_off = offset_of((int64_t)block_net * wpb + wave);
+    const int32_t nx2_off = offset_of((int64_t)block_net * wpb + wave + tile_stride);
+    __builtin_amdgcn_sched_barrier(0);
     int32_t pf_off = 0;
     float pf_x[KS1C], pf_m0 = 0.0f, pf_m1 = 0.0f;
     int32_t pf_act = 0;
@@ -491,9 +558,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
     // one 64-byte line per sample and net instead of the planes' five
     const int XS = (D + 3) & ~3, RS = XS + 4;
     const float *const packed = rb.packed;
-    auto fetch = [&](int64_t tl) {
-        pf_off = nx_off;
-        nx_off = offset_of(tl + tile_stride);
+    auto fetch_rows = [&]() {
         const int64_t row = pf_off;
         if (packed) {
             const float *rec = packed + row * RS;
@@ -525,25 +590,61 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
             pf_m0 = rb.returns[row];
         }
     };
-    fetch((int64_t)block_net * wpb + wave);
-    if (fold.grad != nullptr) fold_adam_into_image<IS_PI>(fold, L, wimg, block_net);  // (uniform) the previous minibatch's optimizer step, then its weights
-    else stage_copy(params + (IS_PI ? L.img_pi : L.img_vf), wimg, IMG_FLOATS);
-    if (IS_PI && hp.normalize_advantage && threadIdx.x < 64) {  // fold the minibatch advantage partials (same order as adv_final_kernel)
-        double a = 0.0, bsum = 0.0;
-        for (int k = threadIdx.x; k < n_part; k += 64) a += adv_part[2 * k], bsum += adv_part[2 * k + 1];
-        for (int o = 32; o > 0; o >>= 1) {
-            a += __shfl_down(a, o, 64);
-            bsum += __shfl_down(bsum, o, 64);
+    auto fetch = [&](int64_t tl) {
+        pf_off = nx_off;
+        nx_off = offset_of(tl + tile_stride);
+        fetch_rows();
+    };
+    pf_off = nx_off, nx_off = nx2_off;
+    [[maybe_unused]] ProTicks pt;
+#ifdef TMA_H64_TICKS
+    for (int i = 0; i < 5; i++) pt.t[i] = kern_t0;
+#endif
+    __shared__ float fold_coef;
+    auto adv_stats = [&]() {
+        if (adv_wave) {  // fold the minibatch advantage partials (same order as adv_final_kernel)
+            double a = 0.0, bsum = 0.0;
+#pragma unroll
+            for (int u = 0; u < ADV_U; u++)
+                if (lane + 64 * u < n_part) a += ap_a[u], bsum += ap_b[u];
+            for (int o = 32; o > 0; o >>= 1) {
+                a += __shfl_down(a, o, 64);
+                bsum += __shfl_down(bsum, o, 64);
+            }
+            if (lane == 0) {
+                const double n = (double)mb.stats_n, mean = a / n;
+                double var = n > 1.0 ? (bsum - n * mean * mean) / (n - 1.0) : 0.0;
+                if (var < 0.0) var = 0.0;
+                adv_ms[0] = (float)mean;
+                adv_ms[1] = (float)sqrt(var);
+            }
         }
-        if (threadIdx.x == 0) {
-            const double n = (double)mb.stats_n, mean = a / n;
-            double var = n > 1.0 ? (bsum - n * mean * mean) / (n - 1.0) : 0.0;
-            if (var < 0.0) var = 0.0;
-            adv_ms[0] = (float)mean;
-            adv_ms[1] = (float)sqrt(var);
-        }
+    };
+    // Each arm holds its own copy of what follows the loads, the folded arm ending in code the other has not: where the arms join, the
+    // compiler's wait for an early load counts the loads behind it on the SHORTER arm -- joined early (or tail-merged), the first consumer
+    // would wait for the whole optimizer state.
+    if (folded) {
+        af.issue_state(fold);
+        af.zero_fill(wimg);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_rows();  // the first tile's records as soon as its offset is back
+        H64_PRO_STAMP(pt, 0);
+        adv_stats();
+        af.clip_coef(fold, block_net, &fold_coef);
+    } else {
+        fetch_rows();
+        H64_PRO_STAMP(pt, 0);
+        stage_copy(params + (IS_PI ? L.img_pi : L.img_vf), wimg, IMG_FLOATS);
+        adv_stats();
     }
-    __syncthreads();
+    if (folded) {
+        lds_barrier();  // the coefficient, the advantage statistics and the zero fill are published
+        H64_PRO_STAMP(pt, 2);
+        af.finish(fold, wimg, block_net, fold_coef, pt);
+        H64_PRO_STAMP(pt, 3);
+    }
+    lds_barrier();  // the image (and, without a folded step, the advantage statistics)
+    H64_PRO_STAMP(pt, 4);
     const float amean = (IS_PI && hp.normalize_advantage) ? adv_ms[0] : 0.0f;
     const float astd = (IS_PI && hp.normalize_advantage) ? adv_ms[1] : 1.0f;
     NetAcc acc;
@@ -558,10 +659,14 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
     if (wave >= 4)
         for (int q = 0; q < hp.debug; q++) __builtin_amdgcn_s_sleep(100);
 #ifdef TMA_H64_TICKS
-    const bool tick_on = block_net == 0 && wave == 0;
+    const bool tick_on = block_net == TMA_H64_TICK_PAIR && wave == 0;
     tk.on = tick_on, tk.prev = __builtin_amdgcn_s_memtime();
     const unsigned long long loop_t0 = tk.prev, loop_r0 = __builtin_amdgcn_s_memrealtime();
-    if (tick_on && lane == 0) g_h64_ticks[IS_PI ? 0 : 1][12] += loop_t0 - kern_t0;
+    if (tick_on && lane == 0) {
+        g_h64_ticks[IS_PI ? 0 : 1][12] += loop_t0 - kern_t0;
+        for (int i = 0; i < 5; i++) g_h64_edge_ticks[IS_PI ? 0 : 1][i] += pt.t[i] - kern_t0;
+    }
+    __shared__ unsigned long long wave_end[8];
 #endif
     for (int64_t tile = (int64_t)block_net * wpb + wave; tile < n_tiles; tile += tile_stride) {
         H64_TICK(15);
@@ -582,9 +687,13 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
         g_h64_ticks[IS_PI ? 0 : 1][11] += __builtin_amdgcn_s_memrealtime() - loop_r0;
     }
 #endif
+#ifdef TMA_H64_TICKS
+    if (lane == 0) wave_end[wave] = loop_t1;
+#endif
     __syncthreads();
 #ifdef TMA_H64_TICKS
     if (tick_on && lane == 0) g_h64_ticks[IS_PI ? 0 : 1][14] += __builtin_amdgcn_s_memtime() - loop_t1;  // waiting for the block's slowest wave
+    if (block_net == TMA_H64_TICK_PAIR && lane == 0) g_h64_edge_ticks[IS_PI ? 0 : 1][8 + wave] += loop_t1 - wave_end[0];  // (one writer per slot)
 #endif
     // loss statistics first (their LDS scratch sits behind the staging area; the barriers inside flush_all_t publish it), the slab
     // stores last: nothing waits behind a global store
@@ -691,6 +800,7 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
     PrepNext next{};
     if (nextp) next = *nextp;
     const int ver = grad_h64_version();
+    if (n_part > ADV_BLOCKS) return TMA_ERR_INVALID;  // the prologue holds ADV_BLOCKS / 64 advantage partials per lane
     if (ver == 1 && foldp && foldp->grad) return TMA_ERR_INVALID;  // the round-1 chain has no optimizer prologue: refuse instead of dropping the step
     if (next.count > 0 && !tma_grad_h64_carries_prep(M.count)) return TMA_ERR_INVALID;  // only the eight-wave kernel has the tail phase: refuse instead of dropping the pre-pass
     static const int stagger = getenv("TMA_H64_STAGGER") ? atoi(getenv("TMA_H64_STAGGER")) : 0;
@@ -741,12 +851,14 @@ extern "C" int tma_debug_h64_tail_ticks(unsigned long long *out, int reset) {
     }
     return TMA_OK;
 }
-extern "C" int tma_debug_h64_ticks(unsigned long long *out32, int reset) {
+extern "C" int tma_debug_h64_ticks(unsigned long long *out32, int reset) {  // out32: 64 values
     TMA_HIP(hipDeviceSynchronize());
     if (out32) TMA_HIP(hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_h64_ticks), sizeof(unsigned long long) * 32));
+    if (out32) TMA_HIP(hipMemcpyFromSymbol(out32 + 32, HIP_SYMBOL(g_h64_edge_ticks), sizeof(unsigned long long) * 32));  // [32..63]: the launch edges
     if (reset) {
         unsigned long long z[32] = {};
         TMA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_h64_ticks), z, sizeof(z)));
+        TMA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_h64_edge_ticks), z, sizeof(z)));
     }
     return TMA_OK;
 }

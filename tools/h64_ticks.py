@@ -19,9 +19,17 @@ def grad():
                                         _lib.ptr(m.grad), _lib.ptr(m.workspace), m._stream()))
 for _ in range(3):
     grad()
-out = (C.c_ulonglong * 32)()
+out = (C.c_ulonglong * 64)()  # [0..31]: the tile phases and launch sums of both nets; [32..63]: the launch edges (g_h64_edge_ticks)
 L.tma_debug_h64_ticks.argtypes = [C.c_void_p, C.c_int]
 L.tma_debug_h64_ticks(None, 1)
+def edges(n):
+    """The prologue split at its waits and barriers (cumulative, wave 0) and each wave's loop-end clock against wave 0's: block pair 0, per launch."""
+    for net, o in (("pi", 32), ("vf", 48)):
+        pro = [round(out[o + i] / n) for i in range(5)]
+        ends = [round(C.c_longlong(out[o + 8 + w]).value / n) for w in range(8)]
+        print("   ", net, "prologue, cycles since the kernel's start: first tile's records issued", pro[0], "| coefficient published (first barrier)", pro[2], "| layer-2 block updated (optimizer state consumed)", pro[1],
+              "| image stores issued", pro[3], "| advantage statistics published", pro[4])
+        print("   ", net, "loop end of waves 0..7 minus wave 0's:", ends, "-- waves 0-3 mean", round(sum(ends[:4]) / 4), "waves 4-7 mean", round(sum(ends[4:]) / 4), "latest", max(ends))
 reps = 10
 for _ in range(reps):
     grad()
@@ -65,7 +73,9 @@ if hasattr(L, "tma_debug_h64_tail_ticks"):
         print("train(), pre-passes", "in launches of their own (TMA_NO_PREP_FOLD=1)" if switch else "carried by the gradient launches", "-- cycles per launch:")
         for net, o in (("pi", 0), ("vf", 16)):
             pro, loop_c, epi = (out[o + i] / n for i in (12, 10, 13))
-            print("   ", net, "prologue", round(pro), "loop", round(loop_c), "epilogue", round(epi), "sum", round(pro + loop_c + epi))
+            print("   ", net, "prologue", round(pro), "loop", round(loop_c), "epilogue", round(epi), "sum", round(pro + loop_c + epi),
+                  "-- of the epilogue,", round(out[o + 14] / n), "the wait for the block's slowest wave")
+        edges(n)
         if not switch:
             print("    vf: end of the loop -> end of the tail phase", round(tail.value / carrying), "cycles per carrying launch: the phase itself",
                   round(tail.value / carrying - out[16 + 13] / n))
