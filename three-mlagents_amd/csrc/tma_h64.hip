@@ -500,7 +500,7 @@ struct AdamImageFold {
     }
 };
 
-template <bool IS_PI, int DT, bool DIRECT = false, int AT = 0>  // AT > 0: compile-time head width of the policy net, 0: runtime L.A
+template <bool IS_PI, int DT, bool DIRECT = false, int AT = 0, int FOLD = FOLD_BOTH>  // AT > 0: compile-time head width of the policy net, 0: runtime L.A; FOLD: h64t_tile's
 __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params, const PLayout &L, const Rollout &rb, const Minibatch &mb,
                                                const HParams &hp, const double *__restrict__ adv_part, int n_part, float *__restrict__ slab,
                                                double *__restrict__ stat_slot, float *smem, int n_blocks_net, int block_net, const AdamFold &fold,
@@ -516,7 +516,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
     constexpr int KS1C = DT > 0 ? (DT + 3) / 4 : 4;  // layer-1 k-steps held in registers (runtime D: up to 16 features)
     const int KS1 = (D + 3) >> 2;
     float *wimg = smem;  // this net's weight image, staged once per block
-    float *slotA = smem + IMG_FLOATS + wave * T_PER_WAVE, *slotB = slotA + 16 * LDT, *dz3t = slotB + 16 * LDT, *Xt = dz3t + 256;
+    float *slotA = smem + IMG_FLOATS + wave * T_PER_WAVE, *slotB = slotA + 16 * LDT, *slotC = slotB + 16 * LDT, *dz3t = slotC + 16 * LDT, *Xt = dz3t + 256;
     const float invB = 1.0f / (float)mb.count;
     const int NOUT = IS_PI ? A : 1;
     // (the first tile's two dependent global round trips -- sample offset, then its rows -- run under the image staging)
@@ -678,7 +678,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
         const float m0 = pf_m0, m1 = pf_m1;
         const int act = pf_act;
         fetch(tile + tile_stride);
-        h64t_tile<IS_PI, KS1C, AT>(wimg, slotA, slotB, dz3t, Xt, xb, m0, m1, act, valid, KS1, A, invB, amean, astd, hp, acc, st, tk, lane);
+        h64t_tile<IS_PI, KS1C, AT, FOLD>(wimg, slotA, slotB, slotC, dz3t, Xt, xb, m0, m1, act, valid, KS1, A, invB, amean, astd, hp, acc, st, tk, lane);
     }
 #ifdef TMA_H64_TICKS
     const unsigned long long loop_t1 = __builtin_amdgcn_s_memtime();
@@ -740,7 +740,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
     }
 }
 
-template <int DT, int VER, int AT = 0>  // AT > 0 (VER 2): compile-time head width -- <4, 2, 5> is the headline shape (GridWorld: 4 observations, 5 actions)
+template <int DT, int VER, int AT = 0, int FOLD = FOLD_BOTH>  // FOLD: h64t_tile's order of the small weight gradients; AT > 0 (VER 2): compile-time head width -- <4, 2, 5> is the headline shape (GridWorld: 4 observations, 5 actions)
 __global__ __launch_bounds__(512, 2) void ppo_grad_h64_kernel(const float *__restrict__ params, PLayout L, Rollout rb, Minibatch mb, HParams hp,
                                                               const double *__restrict__ adv_part, int n_part, float *__restrict__ slabs,
                                                               double *__restrict__ stat_slots, AdamFold fold, PrepNext next) {
@@ -755,13 +755,13 @@ __global__ __launch_bounds__(512, 2) void ppo_grad_h64_kernel(const float *__res
         if (pi_block) grad_h64_body<true, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair);
         else grad_h64_body<false, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair);
     } else {
-        if (pi_block) grad_h64t_body<true, DT, false, AT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
-        else grad_h64t_body<false, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
+        if (pi_block) grad_h64t_body<true, DT, false, AT, FOLD>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
+        else grad_h64t_body<false, DT, false, 0, FOLD>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
     }
 }
 
 // small minibatches (<= 128 tiles): 4-wave blocks, one wave per SIMD (no partner on the matrix pipe, 512 registers), one tile per wave
-template <int DT>
+template <int DT, int FOLD = FOLD_BOTH>
 __global__ __launch_bounds__(256, 1) void ppo_grad_h64_small_kernel(const float *__restrict__ params, PLayout L, Rollout rb, Minibatch mb, HParams hp,
                                                                     const double *__restrict__ adv_part, int n_part, float *__restrict__ slabs,
                                                                     double *__restrict__ stat_slots, AdamFold fold) {
@@ -769,8 +769,8 @@ __global__ __launch_bounds__(256, 1) void ppo_grad_h64_small_kernel(const float 
     const int pair = blockIdx.x >> 1, n_pairs = gridDim.x >> 1;
     float *slab = slabs + (int64_t)pair * L.P;
     double *slot = stat_slots + (int64_t)pair * 8;
-    if ((blockIdx.x & 1) == 0) grad_h64t_body<true, DT, true>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, PrepNext{});
-    else grad_h64t_body<false, DT, true>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, PrepNext{});
+    if ((blockIdx.x & 1) == 0) grad_h64t_body<true, DT, true, 0, FOLD>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, PrepNext{});
+    else grad_h64t_body<false, DT, true, 0, FOLD>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, PrepNext{});
 }
 
 }  // namespace tma
@@ -789,6 +789,15 @@ static int grad_h64_version() {
     static const int ver = getenv("TMA_H64_V1") ? 1 : 2;  // (development switch: the round-1 LDS-round-trip tile chain)
     return ver;
 }
+// A/B and test switch: unset = both small weight gradients folded under the big MFMA streams of their tile; 1 = each in a phase of its
+// own (the order of rounds 3-10); A / B = one fold alone (dW1 under dW2 / dW3 under the dh1 chain), in the headline kernel only
+int tma_h64_small_fold() {
+    static const int fold = [] {
+        const char *e = getenv("TMA_H64_SMALL_SERIAL");
+        return e == nullptr ? FOLD_BOTH : (e[0] == 'A' ? FOLD_W1 : (e[0] == 'B' ? FOLD_W3 : 0));
+    }();
+    return fold;
+}
 bool tma_grad_h64_carries_prep(int64_t count) { return grad_h64_version() == 2 && ceil_div(count, 16) > H64_BLOCKS; }
 
 // H = 64 persistent gradient kernel over one minibatch (>= 256 samples): 2 x n_pairs blocks of 8 waves, block pair p writes slab p.
@@ -805,6 +814,7 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
     if (next.count > 0 && !tma_grad_h64_carries_prep(M.count)) return TMA_ERR_INVALID;  // only the eight-wave kernel has the tail phase: refuse instead of dropping the pre-pass
     static const int stagger = getenv("TMA_H64_STAGGER") ? atoi(getenv("TMA_H64_STAGGER")) : 0;
     static const bool runtime_a = getenv("TMA_H64_RUNTIME_A") != nullptr;  // (A/B and test switch: the runtime-head-width kernel at every shape)
+    const int small_fold = tma_h64_small_fold();
     HParams hps = hpar;
     hps.debug = stagger;
     const int64_t tiles = ceil_div(M.count, 16);
@@ -816,7 +826,11 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
             k<<<dim3((unsigned)(2 * blocks)), dim3(256), smem, s>>>(params, L, R, M, hps, adv_part, n_part, slabs, slots, fold);
             return TMA_OK;
         };
-        const int rc = L.D == 4 ? launch_small(ppo_grad_h64_small_kernel<4>) : (L.D == 6 ? launch_small(ppo_grad_h64_small_kernel<6>) : launch_small(ppo_grad_h64_small_kernel<0>));
+        auto pick = [&](auto fold_c) -> int {
+            constexpr int F = decltype(fold_c)::value;
+            return L.D == 4 ? launch_small(ppo_grad_h64_small_kernel<4, F>) : (L.D == 6 ? launch_small(ppo_grad_h64_small_kernel<6, F>) : launch_small(ppo_grad_h64_small_kernel<0, F>));
+        };
+        const int rc = small_fold == FOLD_BOTH ? pick(std::integral_constant<int, FOLD_BOTH>{}) : pick(std::integral_constant<int, 0>{});
         if (rc) return rc;
         TMA_LAUNCH_CHECK();
         *n_slabs_out = (int)blocks;
@@ -832,8 +846,15 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
     };
     int rc;
     if (ver == 1) rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 1>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 1>) : launch(ppo_grad_h64_kernel<0, 1>));
-    else if (L.D == 4 && L.A == 5 && !runtime_a) rc = launch(ppo_grad_h64_kernel<4, 2, 5>);  // the headline shape: head width folded as well
-    else rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 2>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 2>) : launch(ppo_grad_h64_kernel<0, 2>));
+    else if (L.D == 4 && L.A == 5 && !runtime_a) {  // the headline shape: head width folded as well
+        rc = small_fold == FOLD_BOTH ? launch(ppo_grad_h64_kernel<4, 2, 5>)
+             : (small_fold == FOLD_W1 ? launch(ppo_grad_h64_kernel<4, 2, 5, FOLD_W1>)
+                                      : (small_fold == FOLD_W3 ? launch(ppo_grad_h64_kernel<4, 2, 5, FOLD_W3>) : launch(ppo_grad_h64_kernel<4, 2, 5, 0>)));
+    } else if (small_fold == FOLD_BOTH) {
+        rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 2>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 2>) : launch(ppo_grad_h64_kernel<0, 2>));
+    } else {
+        rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 2, 0, 0>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 2, 0, 0>) : launch(ppo_grad_h64_kernel<0, 2, 0, 0>));
+    }
     if (rc) return rc;
     TMA_LAUNCH_CHECK();
     *n_slabs_out = (int)blocks4;

@@ -3,6 +3,8 @@
 // Formulas: stable-baselines3 2.9.0 PPO.train / evaluate_actions, driven by model.learn() at
 // /root/reference/backend/mlagents/training.py:166-170.
 #pragma once
+#include <type_traits>
+
 #include "tma_ppo_types.h"
 
 namespace tma {
@@ -46,7 +48,7 @@ struct TileTicks {};
 #define H64_TICK(i) do {} while (0)
 #endif
 constexpr int LDT = 64;
-constexpr int T_PER_WAVE = 2 * 16 * LDT + 256 + 256;  // slot A, slot B, dz3 [16][16], X [16][16]
+constexpr int T_PER_WAVE = 3 * 16 * LDT + 256 + 256;  // slot A, slot B, slot C, dz3 [16][16], X [16][16]
 // Column swizzle of the [16][64] tiles: XOR with 16 (row & 1) + 4 ((row >> 1) & 3) + 32 (row >> 3).  Banks by the per-instruction rules of
 // MI355X_MICROARCH.md (LDS table): the chain's b128 stores (8 consecutive rows per lane group, modulo 32) land on eight distinct 16-byte
 // slots, the transposed b32 reads of the weight-gradient operands (rows 4s + g of two lane groups per half wave, modulo 32) on the two
@@ -134,27 +136,39 @@ __device__ __forceinline__ void chain64(const float *wrow, const f32x4 (&in)[4],
 // a pre-activation, or a delta from a back-propagated gradient) and is issued under the MFMAs of k-step (j - 1, r) -- only tile 0's four
 // elements are formed in front of the chain.  done(j) runs once tile j's four operands exist (the tile's LDS store).  Arithmetic and
 // accumulation order are chain64's: results are bit-identical, the matrix pipe just no longer idles through 16 activations.
-template <class ACT, class DONE>
-__device__ __forceinline__ void chain64_act(const float *wrow, f32x4 (&in)[4], f32x4 (&out)[4], ACT act, DONE done) {
+// issue(s) / fill(i): a rider on the chain (round 11).  issue(s) starts the LDS reads of rider item s two k-steps ahead, beside the weight
+// reads; fill(i) is its work on item i, dropped behind the four MFMAs of k-step i, where the vector issue slots are otherwise empty.
+template <class ACT, class DONE, class ISSUE, class FILL>
+__device__ __forceinline__ void chain64_fill(const float *wrow, f32x4 (&in)[4], f32x4 (&out)[4], ACT act, DONE done, ISSUE issue, FILL fill) {
     f32x4 wq[3];
     wq[0] = *reinterpret_cast<const f32x4 *>(wrow);
     wq[1] = *reinterpret_cast<const f32x4 *>(wrow + 64);
+    issue(0);
+    issue(1);
 #pragma unroll
     for (int r = 0; r < 4; r++) in[0][r] = act(0, r);
     done(0);
 #pragma unroll
     for (int i = 0; i < 16; i++) {
-        if (i + 2 < 16) wq[(i + 2) % 3] = *reinterpret_cast<const f32x4 *>(wrow + (16 * ((i + 2) >> 2) + ((i + 2) & 3)) * 64);
+        if (i + 2 < 16) {
+            wq[(i + 2) % 3] = *reinterpret_cast<const f32x4 *>(wrow + (16 * ((i + 2) >> 2) + ((i + 2) & 3)) * 64);
+            issue(i + 2);
+        }
         __builtin_amdgcn_sched_barrier(0);
         const f32x4 w = wq[i % 3];
 #pragma unroll
         for (int mt = 0; mt < 4; mt++) out[mt] = mfma16(w[mt], in[i >> 2][i & 3], out[mt]);
+        fill(i);
         if (i + 4 < 16) {
             in[(i + 4) >> 2][(i + 4) & 3] = act((i + 4) >> 2, (i + 4) & 3);
             if (((i + 4) & 3) == 3) done((i + 4) >> 2);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+template <class ACT, class DONE>
+__device__ __forceinline__ void chain64_act(const float *wrow, f32x4 (&in)[4], f32x4 (&out)[4], ACT act, DONE done) {
+    chain64_fill(wrow, in, out, act, done, [](int) {}, [](int) {});
 }
 
 #ifndef TMA_H64_PIPE
@@ -237,13 +251,18 @@ __device__ __forceinline__ f32x4 h64t_loss(const f32x4 &o0, const f32x4 &o1, flo
 
 // One tile.  Lane (g, r16) works for the tile's sample r16; xb[ks] = observation feature 4 ks + g of that sample (0 beyond D or for an
 // invalid row), m0 / m1 / act = (old log-prob, advantage, action) for the policy net, (return, -, -) for the value net.
-// wimg: this net's LDS weight image; slotA / slotB / dz3t / Xt: the wave's private [sample][feature] tiles (T_PER_WAVE floats in all).
+// wimg: this net's LDS weight image; slotA / slotB / slotC / dz3t / Xt: the wave's private [sample][feature] tiles (T_PER_WAVE floats in all).
 // AT > 0: compile-time head width of the policy net (as KS1C is the compile-time observation width), 0: runtime A_rt.  With the width known
 // the dW3 / dh2 chains below are straight-line code: no branch on the width, no dead MFMA path holding registers across the tile loop.
-template <bool IS_PI, int KS1C, int AT = 0>
-__device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float *slotB, float *dz3t, float *Xt, const float (&xb)[KS1C], float m0,
-                                          float m1, int act, bool valid, int KS1, int A_rt, float invB, float amean, float astd, const HParams &hp,
-                                          NetAcc &acc, TileStats &st, TileTicks &tk, int lane) {
+// FOLD (round 11): where the two small weight gradients of the 4x4x1 form run.  FOLD_W1: dW1 and the b1 sums ride on dW2's 64 MFMAs (dz1 is
+// formed and stored in front of them); FOLD_W3: dW3 and the b3 sum ride on the dh1 chain.  0: each in a phase of its own (rounds 3-10;
+// TMA_H64_SMALL_SERIAL=1).  Every accumulator sees the same operands in the same order either way: same bits.  dz2 has a slot of its own
+// (slot C), so that h2 (slot B) is still there when dW3 reads it during the chain that forms dz2.
+constexpr int FOLD_W1 = 1, FOLD_W3 = 2, FOLD_BOTH = 3;
+template <bool IS_PI, int KS1C, int AT = 0, int FOLD = FOLD_BOTH>
+__device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float *slotB, float *slotC, float *dz3t, float *Xt, const float (&xb)[KS1C],
+                                          float m0, float m1, int act, bool valid, int KS1, int A_rt, float invB, float amean, float astd,
+                                          const HParams &hp, NetAcc &acc, TileStats &st, TileTicks &tk, int lane) {
     const int r16 = lane & 15, g = lane >> 4;
     const int A = AT > 0 ? AT : A_rt;
     const int NOUT = IS_PI ? A : 1;
@@ -292,7 +311,6 @@ __device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float
         }
     }
     if constexpr (!TMA_H64_PIPE) store_tile_t(slotB, h2, r16, g);
-    H64_TICK(2);
     // ---- head: the A operand's row m = lane & 15 carries output a(m) = (m >> 2) + 4 (m & 3), so register r of lane group g' is output
     // g' + 4r: the n_out <= 8 real outputs sit in registers 0..1 and the head's input-gradient GEMM below needs ceil(n_out / 4) k-steps
     // instead of 4.  Two accumulators halve the dependent MFMA chain.
@@ -308,11 +326,11 @@ __device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float
             else o0 = mfma16(w, h2[j][r], o0);
         }
     if constexpr (TMA_H64_PIPE) store_tile_t(slotB, h2, r16, g);
-    H64_TICK(3);
+    H64_TICK(2);
     const f32x4 dz3 = h64t_loss<IS_PI, AT>(o0, o1, m0, m1, act, valid, A, invB, amean, astd, hp, st, lane);
-    H64_TICK(4);
+    H64_TICK(3);
     *reinterpret_cast<f32x4 *>(dz3t + r16 * 16 + 4 * g) = dz3;  // (column m = 4g + r of the tile <-> output a(m), undone by flush_segment)
-    H64_TICK(4);
+    H64_TICK(3);
     // ---- dh2^T = W3 . dz3^T: k-step r contracts over the outputs {g' + 4r}; registers r >= ceil(n_out / 4) of dz3 are zero ----
     f32x4 d[4];
 #pragma unroll
@@ -325,8 +343,13 @@ __device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float
             for (int mt = 0; mt < 4; mt++) d[mt] = mfma16(w[mt], dz3[r], d[mt]);
         }
     }
-    // dW3 (off the dependent path) right behind the chain's MFMAs: the pipe works on it while dh2 matures and dz2 is formed
-    if (w3_blocks(NOUT)) {  // (uniform)
+    // dW3 is off the dependent path; one of three ways (uniform).  ride: the 4x4x1 form folded (FOLD_W3), one sample per k-step of the dh1 chain
+    // below, so the dh2 MFMAs run straight into dz2.  Else the 4x4x1 form right behind them, in a phase of its own: the pipe works on it while
+    // dh2 matures.  Else (more than eight outputs) the 16x16x4 fallback, also a phase.  A policy net of runtime width keeps the phase: with
+    // both widths' riders beside the fallback the eight-wave kernels spill 61-86 registers where the parent spills 8-17.
+    constexpr bool W3_FOLD = (FOLD & FOLD_W3) != 0 && TMA_H64_PIPE && (!IS_PI || AT > 0);
+    const bool w3_small = w3_blocks(NOUT), ride = W3_FOLD && w3_small;
+    if (w3_small && !ride) {
         {
             float bf[4];
 #pragma unroll
@@ -349,47 +372,111 @@ __device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float
                 if (two) acc.w3[1][0] = mfma4(av[u], b1[u], acc.w3[1][0]);
             }
         }
-    } else {
+    } else if (!w3_small) {
         bwd_weight_acc_t<4, 1, true, false>(slotB, dz3t, acc.w3, acc.b3, lane);
     }
-    H64_TICK(5);
-    // ---- dz2 = dh2 * (1 - h2^2) over h2 (dW3 has read h2: LDS operations of one wave execute in order), dh1^T = W2 . dz2^T (chain),
-    // then dW2 (64 MFMAs, off the path) with dz1 = dh1 * (1 - h1^2) formed between its k-tiles ----
+    H64_TICK(4);
+    // ---- dz2 = dh2 * (1 - h2^2) into slot C (slot B keeps h2 for dW3), dh1^T = W2 . dz2^T (chain), then dW2 (64 MFMAs, off the path) ----
     f32x4 e[4];
 #pragma unroll
     for (int mt = 0; mt < 4; mt++) e[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     if constexpr (TMA_H64_PIPE) {
-        chain64_act(wimg + IMG_W2B + 4 * g * 64 + r16 * 4, h2, e, [&](int j, int r) { return d[j][r] * (1.0f - h2[j][r] * h2[j][r]); },
-                    [&](int j) { *reinterpret_cast<f32x4 *>(slotB + tsw(r16, 16 * j + 4 * g)) = h2[j]; });
-        H64_TICK(6);
+        const float *wrow = wimg + IMG_W2B + 4 * g * 64 + r16 * 4;
+        auto dz2 = [&](int j, int r) { return d[j][r] * (1.0f - h2[j][r] * h2[j][r]); };
+        auto st_dz2 = [&](int j) { *reinterpret_cast<f32x4 *>(slotC + tsw(r16, 16 * j + 4 * g)) = h2[j]; };
+        // the rider: sample s of dW3 in k-step s, its three operand words read two k-steps ahead (a ring of three, like the weight quads)
+        auto ride_w3 = [&](auto two_c) {
+            constexpr bool two = decltype(two_c)::value;
+            float bf[4], av[3], b0[3], b1[3];
+#pragma unroll
+            for (int sk = 0; sk < 4; sk++) bf[sk] = dz3t[(4 * sk + g) * 16 + r16];
+            chain64_fill(wrow, h2, e, dz2, st_dz2,
+                         [&](int s) {
+                             av[s % 3] = slotB[tsw(s, lane)];
+                             b0[s % 3] = dz3t[s * 16 + 4 * (lane & 3)];
+                             if (two) b1[s % 3] = dz3t[s * 16 + 4 * (lane & 3) + 1];
+                         },
+                         [&](int s) {
+                             if (s == 0) acc.b3[0] += (bf[0] + bf[1]) + (bf[2] + bf[3]);
+                             acc.w3[0][0] = mfma4(av[s % 3], b0[s % 3], acc.w3[0][0]);
+                             if (two) acc.w3[1][0] = mfma4(av[s % 3], b1[s % 3], acc.w3[1][0]);
+                         });
+        };
+        if (ride) {
+            if constexpr (W3_FOLD) {  // (ride is false without it: no rider is compiled)
+                if (NOUT > 4) ride_w3(std::true_type{});
+                else ride_w3(std::false_type{});
+            }
+        } else {
+            chain64_act(wrow, h2, e, dz2, st_dz2);
+        }
+        H64_TICK(5);
     } else {
 #pragma unroll
         for (int mt = 0; mt < 4; mt++)
 #pragma unroll
             for (int r = 0; r < 4; r++) h2[mt][r] = d[mt][r] * (1.0f - h2[mt][r] * h2[mt][r]);
-        store_tile_t(slotB, h2, r16, g);
-        H64_TICK(6);
+        store_tile_t(slotC, h2, r16, g);
+        H64_TICK(5);
         chain64(wimg + IMG_W2B + 4 * g * 64 + r16 * 4, h2, e);
     }
-    H64_TICK(7);
-    {
-        float bf[4][4];
+    // h1 is not kept in registers across the head / loss / layer-2 work: its LDS copy (slot A) is read back in the lane's own C-layout
+    // positions (the b128 pattern of the store: conflict-free); every read of slot A is issued before dz1 overwrites it below
+    constexpr bool W1_FOLD = (FOLD & FOLD_W1) != 0 && w1_blocks<KS1C>();
+    f32x4 hh[4];
+    auto read_hh = [&]() {
 #pragma unroll
-        for (int nt = 0; nt < 4; nt++) {
+        for (int mt = 0; mt < 4; mt++) hh[mt] = *reinterpret_cast<const f32x4 *>(slotA + tsw(r16, 16 * mt + 4 * g));
+    };
+    if constexpr (W1_FOLD) read_hh();  // (first: dz1 is formed in front of dW2)
+    float bf[4][4], av[4][4];
 #pragma unroll
-            for (int sk = 0; sk < 4; sk++) bf[nt][sk] = slotB[tsw(4 * sk + g, nt * 16 + r16)];
-            acc.b2[nt] += (bf[nt][0] + bf[nt][1]) + (bf[nt][2] + bf[nt][3]);
-        }
-        float av[4][4];
+    for (int nt = 0; nt < 4; nt++) {
+#pragma unroll
+        for (int sk = 0; sk < 4; sk++) bf[nt][sk] = slotC[tsw(4 * sk + g, nt * 16 + r16)];
+        acc.b2[nt] += (bf[nt][0] + bf[nt][1]) + (bf[nt][2] + bf[nt][3]);
+    }
+#pragma unroll
+    for (int kt = 0; kt < 4; kt++)
+#pragma unroll
+        for (int sk = 0; sk < 4; sk++) av[kt][sk] = slotA[tsw(4 * sk + g, kt * 16 + r16)];
+    if constexpr (!W1_FOLD) read_hh();
+    if constexpr (W1_FOLD) {
+        // dz1 = dh1 * (1 - h1^2) first (hh is the oldest read: it is back while the 32 operand words are still on their way), stored over h1
+        // behind the reads of slot A (LDS operations of one wave execute in order); then dW2's 16 k-steps carry dW1: the b1 words in front,
+        // sample s's words (dz1[s][n = lane], X[s][k = 4 blk + (lane & 3)]) read in k-step s, its 4x4x1 MFMAs two k-steps later
 #pragma unroll
         for (int kt = 0; kt < 4; kt++)
 #pragma unroll
-            for (int sk = 0; sk < 4; sk++) av[kt][sk] = slotA[tsw(4 * sk + g, kt * 16 + r16)];
-        // h1 is not kept in registers across the head / loss / layer-2 work: its LDS copy (slot A) is read back in the lane's own C-layout
-        // positions (the b128 pattern of the store: conflict-free); every read of slot A is issued before dz1 overwrites it below
-        f32x4 hh[4];
+            for (int r = 0; r < 4; r++) h1[kt][r] = e[kt][r] * (1.0f - hh[kt][r] * hh[kt][r]);
+        store_tile_t(slotA, h1, r16, g);
+        H64_TICK(6);
+        float cf[4][4], bv[3], xa[KS1C][3];
 #pragma unroll
-        for (int mt = 0; mt < 4; mt++) hh[mt] = *reinterpret_cast<const f32x4 *>(slotA + tsw(r16, 16 * mt + 4 * g));
+        for (int nt = 0; nt < 4; nt++)
+#pragma unroll
+            for (int sk = 0; sk < 4; sk++) cf[nt][sk] = slotA[tsw(4 * sk + g, nt * 16 + r16)];
+        auto w1_sample = [&](int s) {
+#pragma unroll
+            for (int blk = 0; blk < KS1C; blk++) acc.w1[0][blk] = mfma4(xa[blk][s % 3], bv[s % 3], acc.w1[0][blk]);
+        };
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            bv[i % 3] = slotA[tsw(i, lane)];
+#pragma unroll
+            for (int blk = 0; blk < KS1C; blk++) xa[blk][i % 3] = Xt[i * 16 + 4 * blk + (lane & 3)];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int nt = 0; nt < 4; nt++) acc.w2[i >> 2][nt] = mfma16(av[i >> 2][i & 3], bf[nt][i & 3], acc.w2[i >> 2][nt]);
+            if (i >= 2 && i < 6) acc.b1[i - 2] += (cf[i - 2][0] + cf[i - 2][1]) + (cf[i - 2][2] + cf[i - 2][3]);
+            if (i >= 2) w1_sample(i - 2);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        w1_sample(14);
+        w1_sample(15);
+        H64_TICK(7);
+    } else {
+        // dW2 with dz1 formed between its k-tiles, then dW1 in a phase of its own
 #pragma unroll
         for (int kt = 0; kt < 4; kt++) {
             __builtin_amdgcn_sched_barrier(0);
@@ -401,35 +488,35 @@ __device__ __forceinline__ void h64t_tile(const float *wimg, float *slotA, float
             for (int r = 0; r < 4; r++) h1[kt][r] = e[kt][r] * (1.0f - hh[kt][r] * hh[kt][r]);
         }
         __builtin_amdgcn_sched_barrier(0);
-    }
-    store_tile_t(slotA, h1, r16, g);  // dz1 over h1
-    H64_TICK(8);
-    if constexpr (w1_blocks<KS1C>()) {
+        store_tile_t(slotA, h1, r16, g);  // dz1 over h1
+        H64_TICK(6);
+        if constexpr (w1_blocks<KS1C>()) {
 #pragma unroll
-        for (int nt = 0; nt < 4; nt++) {
-            float bf[4];
+            for (int nt = 0; nt < 4; nt++) {
+                float cf[4];
 #pragma unroll
-            for (int sk = 0; sk < 4; sk++) bf[sk] = slotA[tsw(4 * sk + g, nt * 16 + r16)];
-            acc.b1[nt] += (bf[0] + bf[1]) + (bf[2] + bf[3]);
-        }
-#pragma unroll
-        for (int s0 = 0; s0 < 16; s0 += 8) {
-            float bv[8], xa[KS1C][8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                bv[u] = slotA[tsw(s0 + u, lane)];  // dz1[s][n = lane]
-#pragma unroll
-                for (int blk = 0; blk < KS1C; blk++) xa[blk][u] = Xt[(s0 + u) * 16 + 4 * blk + (lane & 3)];  // X[s][k = 4 blk + (lane & 3)]
+                for (int sk = 0; sk < 4; sk++) cf[sk] = slotA[tsw(4 * sk + g, nt * 16 + r16)];
+                acc.b1[nt] += (cf[0] + cf[1]) + (cf[2] + cf[3]);
             }
 #pragma unroll
-            for (int u = 0; u < 8; u++)
+            for (int s0 = 0; s0 < 16; s0 += 8) {
+                float bv[8], xa[KS1C][8];
 #pragma unroll
-                for (int blk = 0; blk < KS1C; blk++) acc.w1[0][blk] = mfma4(xa[blk][u], bv[u], acc.w1[0][blk]);
+                for (int u = 0; u < 8; u++) {
+                    bv[u] = slotA[tsw(s0 + u, lane)];  // dz1[s][n = lane]
+#pragma unroll
+                    for (int blk = 0; blk < KS1C; blk++) xa[blk][u] = Xt[(s0 + u) * 16 + 4 * blk + (lane & 3)];  // X[s][k = 4 blk + (lane & 3)]
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+#pragma unroll
+                    for (int blk = 0; blk < KS1C; blk++) acc.w1[0][blk] = mfma4(xa[blk][u], bv[u], acc.w1[0][blk]);
+            }
+        } else {
+            bwd_weight_acc_t<1, 4, false, true>(Xt, slotA, acc.w1, acc.b1, lane);
         }
-    } else {
-        bwd_weight_acc_t<1, 4, false, true>(Xt, slotA, acc.w1, acc.b1, lane);
+        H64_TICK(7);
     }
-    H64_TICK(9);
 }
 
 // ------------------------------------------------------------------------------------------

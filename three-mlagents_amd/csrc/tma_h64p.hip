@@ -187,7 +187,7 @@ __device__ __forceinline__ bool wait_ge(unsigned *ctr, unsigned want, unsigned *
     } while (0)
 
 // NM: float4 slots per thread for the small tensors (256 NM >= ceil(nmisc / 4) of the policy net)
-template <bool IS_PI, int DT, int NM>
+template <bool IS_PI, int DT, int NM, int FOLD>
 __device__ __forceinline__ void epoch_body(const EpochArgs &a, int j, float *smem) {
     constexpr int KS1C = DT > 0 ? (DT + 3) / 4 : 4;
     constexpr int NS = NM + 4;  // float4 slots per thread over the whole position space
@@ -204,7 +204,7 @@ __device__ __forceinline__ void epoch_body(const EpochArgs &a, int j, float *sme
     const int PN4 = q.P >> 2, QF = (PN4 + 3) >> 2, nm4 = q.oW2 >> 2;
     const int net = IS_PI ? 0 : 1, role = net * 4 + j;
     float *wimg = smem, *region = smem + IMG_FLOATS + wave * a.rw;
-    float *slotA = region, *slotB = slotA + 16 * LDT, *dz3t = slotB + 16 * LDT, *Xt = dz3t + 256;
+    float *slotA = region, *slotB = slotA + 16 * LDT, *slotC = slotB + 16 * LDT, *dz3t = slotC + 16 * LDT, *Xt = dz3t + 256;
     float *copies = smem + IMG_FLOATS;
     unsigned *sync = reinterpret_cast<unsigned *>(a.region + HP_SYNC);
     unsigned *cntA = sync + 32 * net, *abortw = sync + 160;
@@ -323,7 +323,7 @@ __device__ __forceinline__ void epoch_body(const EpochArgs &a, int j, float *sme
 #endif
         NetAcc acc;
         zero_acc(acc);
-        h64t_tile<IS_PI, KS1C>(wimg, slotA, slotB, dz3t, Xt, xb, m0, m1, act, valid, KS1, A, invB, amean, astd, a.hp, acc, st, tk, lane);
+        h64t_tile<IS_PI, KS1C, 0, FOLD>(wimg, slotA, slotB, slotC, dz3t, Xt, xb, m0, m1, act, valid, KS1, A, invB, amean, astd, a.hp, acc, st, tk, lane);
         HP_TICK(1);
 
         // ---- block sum: every wave scatters its accumulators into its own flat copy (its tile slots are dead), then each thread sums
@@ -542,7 +542,7 @@ __device__ __forceinline__ void epoch_body(const EpochArgs &a, int j, float *sme
     }
 }
 
-template <int DT, int NM>
+template <int DT, int NM, int FOLD>  // FOLD: h64t_tile's order of the small weight gradients
 __global__ __launch_bounds__(256, 1) void ppo_epoch_h64p_kernel(EpochArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ int role_s;
@@ -561,8 +561,8 @@ __global__ __launch_bounds__(256, 1) void ppo_epoch_h64p_kernel(EpochArgs a) {
         if (threadIdx.x == 0) *a.err_out = 1;
         return;
     }
-    if (role < 4) epoch_body<true, DT, NM>(a, role, smem);
-    else epoch_body<false, DT, NM>(a, role - 4, smem);
+    if (role < 4) epoch_body<true, DT, NM, FOLD>(a, role, smem);
+    else epoch_body<false, DT, NM, FOLD>(a, role - 4, smem);
     // a failed wait anywhere: record it for tma_ppo_pop_stats (parameters were left untouched by every block that saw the abort)
     if (threadIdx.x == 0 && __hip_atomic_load(sync + 160, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) *a.err_out = 1;
 }
@@ -623,10 +623,13 @@ int tma_launch_epoch_h64p(const EpochJob &job, const Rollout &R, const HParams &
         k<<<dim3(HP_GRID), dim3(256), smem, s>>>(a);
         return TMA_OK;
     };
-    int rc;
-    if (L.D == 4 && nm <= 2) rc = nm == 1 ? launch(ppo_epoch_h64p_kernel<4, 1>) : launch(ppo_epoch_h64p_kernel<4, 2>);
-    else if (L.D == 6 && nm <= 2) rc = nm == 1 ? launch(ppo_epoch_h64p_kernel<6, 1>) : launch(ppo_epoch_h64p_kernel<6, 2>);
-    else rc = launch(ppo_epoch_h64p_kernel<0, 3>);
+    auto pick = [&](auto fold_c) -> int {
+        constexpr int F = decltype(fold_c)::value;
+        if (L.D == 4 && nm <= 2) return nm == 1 ? launch(ppo_epoch_h64p_kernel<4, 1, F>) : launch(ppo_epoch_h64p_kernel<4, 2, F>);
+        if (L.D == 6 && nm <= 2) return nm == 1 ? launch(ppo_epoch_h64p_kernel<6, 1, F>) : launch(ppo_epoch_h64p_kernel<6, 2, F>);
+        return launch(ppo_epoch_h64p_kernel<0, 3, F>);
+    };
+    const int rc = tma_h64_small_fold() == FOLD_BOTH ? pick(std::integral_constant<int, FOLD_BOTH>{}) : pick(std::integral_constant<int, 0>{});
     if (rc) return rc;
     TMA_LAUNCH_CHECK();
     return TMA_OK;

@@ -276,6 +276,7 @@ int tma_launch_grad_h64(const float *params, const tma::PLayout &L, const tma::R
                         const tma::AdamFold *fold = nullptr, const tma::PrepNext *next = nullptr);
 // true: a minibatch of `count` rows runs on the eight-wave kernel, whose value blocks can carry a PrepNext (and whose launch may be handed one)
 bool tma_grad_h64_carries_prep(int64_t count);
+int tma_h64_small_fold();  // TMA_H64_SMALL_SERIAL, read once per process: the FOLD mask of h64t_tile the H = 64 update kernels run
 
 // tma_h64p.hip: `total` samples (whole epochs, prepared in job.ws) at batch_size = 256 as a single persistent launch (H = 64 fast-path layouts)
 bool tma_epoch_h64p_eligible(const tma::PLayout &L, int64_t batch_size, int64_t total);

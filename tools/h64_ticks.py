@@ -34,7 +34,12 @@ reps = 10
 for _ in range(reps):
     grad()
 L.tma_debug_h64_ticks(out, 0)
-names = ["L1+tanh1", "st h1+L2", "tanh2+st", "head", "loss", "st dz3+dW3", "dh2+dz2+st", "dW2", "dh1+dz1+st", "dW1", "", "", "", "", "", "loop top"]
+# the order of the small weight gradients in the headline kernel, from TMA_H64_SMALL_SERIAL as csrc/tma_h64.hip reads it: unset both folded,
+# A = dW1 under dW2 alone, B = dW3 under the dh1 chain alone, anything else = each in a phase of its own
+sw = os.environ.get("TMA_H64_SMALL_SERIAL")
+w1_fold, w3_fold = sw is None or sw[:1] == "A", sw is None or sw[:1] == "B"
+names = ["L1", "tanh1+st h1+L2", "tanh2+head+st h2", "loss+st dz3", "dh2" if w3_fold else "dh2+dW3", "dz2+st+dh1|dW3" if w3_fold else "dz2+st+dh1",
+         "dW2 reads+dz1+st" if w1_fold else "dW2+dz1+st", "dW2|dW1" if w1_fold else "dW1", "", "", "", "", "", "", "", "loop top"]
 tiles = max(1, reps * (B // 16) // (min(128, (B // 16 + 7) // 8) * 8))
 for net, o in (("pi", 0), ("vf", 16)):
     v = [out[o + i] / tiles for i in range(16)]
