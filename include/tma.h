@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 217
+#define TMA_VERSION 218
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -206,6 +206,25 @@ int64_t tma_policy_vjp_workspace_bytes(const tma_policy_dims *d, int64_t n);
 int tma_policy_evaluate_actions_backward(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
                                          const float *g_values, const float *g_logp, const float *g_entropy, float *grad_out, void *workspace,
                                          int64_t workspace_bytes, void *stream);
+/* ActorCriticPolicy.get_distribution(obs) (ABI 218): the policy net's head BEFORE any distribution arithmetic -- head_out f32[n][act_dim], dense
+ * (row stride act_dim): the raw logits (action_net's output, not normalised) of a Discrete policy, the mean of a Box policy -- and, where
+ * values_out is not NULL, values f32[n].  The kernels are the ones tma_policy_act runs, in a further mode (same specialisation for a shape, same
+ * layer code and k order, same grid caps; tma_debug_last_dispatch reports the same TMA_DISPATCH_FWD_* id): `values` is bit-identical to
+ * tma_policy_act's, a Box head_out to the actions of tma_policy_act(deterministic = 1), and the first maximal column of a Discrete head_out row is
+ * its deterministic action.  The head tile is stored coalesced; rows behind n are never stored.  Every mfma_dtype: 1 gives the bf16 kernels' own
+ * head, 2 runs the exact-f32 code.  Bad dims, null params / obs / head_out and n < 1 are refused (TMA_ERR_INVALID) before any HIP call. */
+int tma_policy_head(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *head_out, float *values_out, void *stream);
+/* VJP of tma_policy_head with respect to the trainable parameters (ABI 218): what torch autograd computes behind a loss on SB3's
+ * policy.get_distribution(obs) (KL between policies, distillation) --
+ *   grad_out[n_trainable] = sum_i sum_j g_head[i][j] dhead_ij/dtheta + sum_i g_values[i] dV_i/dtheta.
+ * g_head f32[n][act_dim] (dense) and g_values f32[n] may each be NULL (= zeros), not both.  grad_out is OVERWRITTEN, every element -- the log_std
+ * segment of a Box policy with zeros: the head does not depend on log_std (a distribution's dependence on it is the caller's own arithmetic).
+ * Parameter layout, `workspace` (tma_policy_vjp_workspace_bytes(d, n) bytes), chunking, TMA_VJP_CHUNK_ROWS and the determinism contract are
+ * tma_policy_evaluate_actions_backward's: the same two launches per chunk, the first taking a row's head cotangent from g_head instead of forming
+ * it from three cotangents, the second unchanged.  mfma_dtype 1 (bf16) is refused as there.  Bad dims, null params / obs / grad_out, n < 1, two
+ * NULL cotangents and a workspace below what the bytes function reports are refused (TMA_ERR_INVALID) before any HIP call. */
+int tma_policy_head_backward(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, const float *g_head, const float *g_values,
+                             float *grad_out, void *workspace, int64_t workspace_bytes, void *stream);
 /* ActorCriticPolicy.predict_values */
 int tma_policy_values(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *values_out, void *stream);
 /* collect_rollouts timeout bootstrap: rewards[i] += gamma * V(terminal_obs[i]) where truncated[i] */

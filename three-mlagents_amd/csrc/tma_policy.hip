@@ -118,7 +118,25 @@ __global__ void sync_transposed_kernel(float *params, PLayout L) {
 //         the row's action from `actions_out` (i32[n] / f32[n][A]) instead of drawing one, and also forms the entropy; `rewards` is entropy_out.
 //         values_out / logp_out / entropy_out may each be null.  A Discrete action outside [0, A) matches no column (it never indexes memory):
 //         that row's log-prob is NaN by a select, its value and entropy are unaffected.  Same for the H = 64 and wide kernels below.
+//       4 the head itself (tma_policy_head; SB3 get_distribution): the layers and heads of MODE 0 in the same k order; the epilogue stores the
+//         head tile -- Discrete: the logits before any softmax, Box: the mean -- to `actions_out` (f32[n][A]) and neither samples nor scores.
+//         values_out may be null.  Same for the H = 64 and wide kernels below.
 // ------------------------------------------------------------------------------------------
+// MODE 4: a wave's [16][A] head tile (acc[j][r]: row 4 g + r, column 16 j + r16) through its LDS scratch `stage` (16 * A floats) to rows
+// [row0, row0 + 16) of head[n][A]: contiguous addresses lane after lane.  Rows behind n are not stored.
+template <int NJ>
+__device__ __forceinline__ void store_head_tile(const f32x4 (&acc)[NJ], int A, float *stage, float *__restrict__ head, int64_t row0, int64_t n, int lane) {
+    const int r16 = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < NJ; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            if (16 * j + r16 < A) stage[(4 * g + r) * A + 16 * j + r16] = acc[j][r];
+    const int valid = n - row0 < 16 ? (int)(n - row0) : 16;  // (<= 0: a row tile behind the batch)
+    float *dst = head + row0 * A;
+    for (int e = lane; e < valid * A; e += 64) dst[e] = stage[e];
+}
+
 template <bool CONT, int MODE>
 __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict__ params, PLayout L, const float *__restrict__ obs, int64_t n,
                                                          uint32_t rng_seed, uint32_t rng_step, uint32_t env_offset, int deterministic,
@@ -170,22 +188,26 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict
                 }
             continue;
         }
-        if constexpr (MODE == 0 || MODE == 3) {
-            constexpr bool EVAL = MODE == 3;
+        if constexpr (MODE == 0 || MODE == 3 || MODE == 4) {
+            constexpr bool EVAL = MODE == 3, HEAD = MODE == 4;
             float *const entropy_out = rewards;  // (MODE 3)
-            if constexpr (EVAL) {
+            if constexpr (EVAL || HEAD) {
                 if (r16 == 0 && values_out != nullptr)
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         const int64_t row = row0 + g * 4 + r;
                         if (row < n) values_out[row] = vacc[0][r];
                     }
-                if (logp_out == nullptr && entropy_out == nullptr) continue;
+                if (EVAL && logp_out == nullptr && entropy_out == nullptr) continue;
             }
             const Net P = pi_net(params, L);
             dense_tanh(X, ldx, D, P.W1t, P.b1, H, h1, ld, lane);
             dense_tanh(h1, ld, H, P.W2t, P.b2, H, h2, ld, lane);
-            if constexpr (!CONT) {
+            if constexpr (HEAD) {  // (h1 is free once layer 2 has read it: the head tile's scratch)
+                f32x4 acc[CONT ? 2 : 1];
+                dense_head<CONT ? 2 : 1>(h2, ld, H, P.W3t, P.b3, A, acc, lane);
+                store_head_tile(acc, A, h1, static_cast<float *>(actions_out), row0, n, lane);
+            } else if constexpr (!CONT) {
                 f32x4 acc[1];
                 dense_head<1>(h2, ld, H, P.W3t, P.b3, A, acc, lane);
 #pragma unroll
@@ -1874,6 +1896,7 @@ static thread_local int32_t g_disp_fwd = TMA_DISPATCH_NONE, g_disp_grad = TMA_DI
 // tma_policy_sync maintains), B operands by ds_read_b128.  MODE 0 also folds the timeout bootstrap of the PREVIOUS vector
 // step (rewards_prev[i] += gamma * V(terminal_obs_prev[i]) where truncated_prev[i]) into the same launch.
 // MODE 3 (evaluate_actions, see policy_fwd_kernel): `actions_out` is read, `boot_rewards` is entropy_out.
+// MODE 4 (the head, see policy_fwd_kernel): `actions_out` is head_out f32[n][A]; H64_HEAD_STAGE floats of LDS per wave behind the images.
 // ------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(256) void policy_fwd_h64_kernel(const float *__restrict__ params, PLayout L, const float *__restrict__ obs, int64_t n,
@@ -1891,7 +1914,7 @@ __global__ __launch_bounds__(256) void policy_fwd_h64_kernel(const float *__rest
     const int D = L.D, A = L.A, KS1 = (D + 3) >> 2;
     float *vimg = smem, *pimg = smem + FWD_IMG;
     stage_fwd_image(params + L.img_vf, vimg);
-    if constexpr (MODE == 0 || MODE == 3) stage_fwd_image(params + L.img_pi, pimg);
+    if constexpr (MODE == 0 || MODE == 3 || MODE == 4) stage_fwd_image(params + L.img_pi, pimg);
     __syncthreads();
     const int64_t n_tiles = (n + 15) >> 4;
     auto features = [&](const float *src, int64_t row, bool ok, float (&xb)[4]) {  // (clamped addresses, masked values: no load sits behind a branch)
@@ -1910,7 +1933,18 @@ __global__ __launch_bounds__(256) void policy_fwd_h64_kernel(const float *__rest
             features(obs, row, ok, xb);
             f32x4 o0, o1;
             h64t_forward<4>(vimg, vimg + IMG_FWD_FLOATS, vimg + IMG_FWD_FLOATS + 64, vimg + IMG_FWD_FLOATS + 128, xb, KS1, o0, o1, lane);
-            if (ok && g == 0 && (MODE != 3 || values_out != nullptr)) values_out[row] = o0[0] + o1[0];
+            if (ok && g == 0 && ((MODE != 3 && MODE != 4) || values_out != nullptr)) values_out[row] = o0[0] + o1[0];
+            if constexpr (MODE == 4) {  // logit a = g + 4 r of row r16 in register r (h64t_act_n's x[r]): through this wave's scratch, then contiguous
+                h64t_forward<4>(pimg, pimg + IMG_FWD_FLOATS, pimg + IMG_FWD_FLOATS + 64, pimg + IMG_FWD_FLOATS + 128, xb, KS1, o0, o1, lane);
+                float *stage = smem + 2 * FWD_IMG + wave * H64_HEAD_STAGE;
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+                    if (g + 4 * r < A) stage[r16 * A + g + 4 * r] = o0[r] + o1[r];
+                const int64_t row0 = tile << 4;
+                const int valid = n - row0 < 16 ? (int)(n - row0) : 16;
+                float *dst = reinterpret_cast<float *>(actions_out) + row0 * A;
+                for (int e = lane; e < valid * A; e += 64) dst[e] = stage[e];
+            }
             if constexpr (MODE == 3) {
                 float *const entropy_out = boot_rewards;
                 if (logp_out == nullptr && entropy_out == nullptr) continue;
@@ -1998,7 +2032,7 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
     // forward pass must reproduce these log-probabilities).
     constexpr int KS2B = H / 32, KS1R = 6;
     const int KS1b = Kp1 >> 5;
-    const bool blk_pi = (MODE == 0 || MODE == 3) && (blockIdx.x & 1) == 1;
+    const bool blk_pi = (MODE == 0 || MODE == 3 || MODE == 4) && (blockIdx.x & 1) == 1;
     bf16x8 w1r[BF ? NTW : 1][BF ? KS1R : 1], w2r[BF ? NTW : 1][BF ? KS2B : 1];
     float b1r[NTW], b2r[NTW];
     if constexpr (BF) {
@@ -2135,12 +2169,18 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
     // 128 row groups, so this fills all 256 CUs and halves the dependent chain of a vector step.
     // MODE 3 (evaluate_actions, see policy_fwd_kernel) splits the nets the same way; `actions_out` is read, `rewards` is entropy_out, and a
     // block whose outputs were all passed as null has nothing to do.
-    constexpr int NR = (MODE == 0 || MODE == 3) ? 2 : 1;
-    constexpr bool EVAL = MODE == 3;
-    const int role = (MODE == 0 || MODE == 3) ? (int)(blockIdx.x & 1) : 0;
+    // MODE 4 (the head, see policy_fwd_kernel): the same split; `actions_out` is head_out, and waves 0 / 1 stage their head tile in the h1 / A1
+    // region, which nothing reads once layer 2 is behind the barrier.
+    constexpr bool TWO = MODE == 0 || MODE == 3 || MODE == 4;
+    constexpr int NR = TWO ? 2 : 1;
+    constexpr bool EVAL = MODE == 3, HEAD = MODE == 4;
+    const int role = TWO ? (int)(blockIdx.x & 1) : 0;
     float *const entropy_out = rewards;  // (MODE 3)
     if constexpr (EVAL) {
         if (role == 0 ? values_out == nullptr : (logp_out == nullptr && entropy_out == nullptr)) return;  // (block-uniform, in front of every barrier)
+    }
+    if constexpr (HEAD) {
+        if (role == 0 && values_out == nullptr) return;  // (block-uniform, in front of every barrier)
     }
     for (int64_t grp = blockIdx.x / NR; grp < n_groups; grp += gridDim.x / NR) {
         const int64_t row0 = grp * M;
@@ -2186,7 +2226,7 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
                 else dense_head<1>(h2 + mt * 16 * ld, ld, H, V.W3t, V.b3, 1, vacc, lane);
             }
         }
-        if constexpr (MODE == 1 || MODE == 0 || MODE == 3) {
+        if constexpr (MODE == 1 || TWO) {
             if (role == 0 && wave < 2 && r16 == 0)
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
@@ -2204,12 +2244,18 @@ __global__ __launch_bounds__(256) void policy_fwd_wide_kernel(const float *__res
                     }
                 }
         }
-        if constexpr (MODE == 0 || MODE == 3) if (role == 1) {
+        if constexpr (TWO) if (role == 1) {
             const Net P = pi_net(params, L);
             hidden(P, true);
             if (wave < 2) {
                 const float *hh = h2 + mt * 16 * ld;
-                if constexpr (!CONT) {
+                if constexpr (HEAD) {
+                    f32x4 acc[CONT ? 2 : 1];
+                    if constexpr (BF) bf_head<CONT ? 2 : 1>(A2, lda, 16 * mt, H / 32, bf_net_ptr(params, L, true).fW3, P.b3, A, acc, lane);
+                    else dense_head<CONT ? 2 : 1>(hh, ld, H, P.W3t, P.b3, A, acc, lane);
+                    float *stage = (BF ? reinterpret_cast<float *>(A1) : h1) + mt * 16 * 32;
+                    store_head_tile(acc, A, stage, static_cast<float *>(actions_out), row0 + mt * 16, n, lane);
+                } else if constexpr (!CONT) {
                     f32x4 acc[1];
                     if constexpr (BF) bf_head<1>(A2, lda, 16 * mt, H / 32, bf_net_ptr(params, L, true).fW3, P.b3, A, acc, lane);
                     else dense_head<1>(hh, ld, H, P.W3t, P.b3, A, acc, lane);
@@ -2332,7 +2378,7 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
     case FwdFamily::Refused: return refuse(L, p);  // before any launch
     case FwdFamily::H64:
         if constexpr (MODE == 2) return launch_fwd_h64<2>(p, params, L, nullptr, n, 0, 0, 0, 1, nullptr, nullptr, nullptr, obs, trunc, gamma, rewards, s);
-        else if constexpr (MODE == 3) return launch_fwd_h64<3>(p, params, L, obs, n, 0, 0, 0, 1, actions, values, logp, nullptr, nullptr, 0.0f, rewards, s);
+        else if constexpr (MODE == 3 || MODE == 4) return launch_fwd_h64<MODE>(p, params, L, obs, n, 0, 0, 0, 1, actions, values, logp, nullptr, nullptr, 0.0f, rewards, s);
         else return launch_fwd_h64<MODE>(p, params, L, obs, n, seed, step, env_offset, deterministic, actions, values, logp, nullptr, nullptr, 0.0f, nullptr, s);
     case FwdFamily::WideF32:
     case FwdFamily::WideBF16:
@@ -2567,6 +2613,17 @@ int tma_policy_evaluate_actions(const float *params, const tma_policy_dims *d, c
     rc = enter(d);
     if (rc) return rc;
     return launch_fwd<3>(params, d, obs, n, 0, 0, 0, 1, const_cast<void *>(actions), values_out, logp_out, nullptr, 0.0f, entropy_out, (hipStream_t)stream);
+}
+
+int tma_policy_head(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *head_out, float *values_out, void *stream) {
+    g_disp_fwd = TMA_DISPATCH_NONE;
+    int rc = check_dims(d);  // (every refusal comes back before the first HIP call: enter() is what makes the device current)
+    if (rc) return rc;
+    if (!params || !obs || !head_out) return fail(TMA_ERR_INVALID, "tma_policy_head: null buffer");
+    if (n < 1) return fail(TMA_ERR_INVALID, "tma_policy_head: n must be >= 1");
+    rc = enter(d);
+    if (rc) return rc;
+    return launch_fwd<4>(params, d, obs, n, 0, 0, 0, 1, head_out, values_out, nullptr, nullptr, 0.0f, nullptr, (hipStream_t)stream);
 }
 
 int tma_policy_values(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *values_out, void *stream) {

@@ -25,6 +25,7 @@ constexpr int LDS_LIMIT = 160 * 1024;         // dynamic LDS of one workgroup: w
 constexpr int LDS_OPT_IN = 64 * 1024;         // ... and beyond this a kernel has to ask (hipFuncAttributeMaxDynamicSharedMemorySize)
 constexpr int GENERIC_GRAD_LDS = 156 * 1024;  // the generic gradient kernel takes as many waves per block (up to 4) as fit this
 constexpr int64_t WIDE_FWD_GROUP_CAP = 4096, GENERIC_FWD_BLOCK_CAP = 8192, H64_FWD_BLOCK_CAP = 2048;  // then grid-stride
+constexpr int H64_HEAD_STAGE = 16 * 16;  // floats per wave (mode 4)
 constexpr int64_t GENERIC_GRAD_BLOCK_CAP = MAX_GRAD_BLOCKS / 2;  // per net: one statistic slot per block
 
 inline int fwd_smem_bytes(const PLayout &L, int wpb) {
@@ -51,7 +52,8 @@ inline bool w2_defer_fits(const PLayout &L) { return Workspace::defer_w2_fits(L)
 // slab_reduce_kernel / wide_small_reduce_kernel leave one sum-of-squares partial per 64 parameters where the workspace has slots for them
 inline bool sq_partials_fit(const PLayout &L) { return ceil_div(L.P, 64) <= WIDE_SQ_SLOTS; }
 
-// ---- forward (mode 0: act, 1: values, 2: bootstrap, 3: evaluate_actions; 0 and 3 run both nets).  It reads no switch.
+// ---- forward (mode 0: act, 1: values, 2: bootstrap, 3: evaluate_actions, 4: the head itself -- tma_policy_head; 0, 3 and 4 run both nets).
+// It reads no switch.
 enum class FwdFamily { Refused, H64, WideF32, WideBF16, Generic };
 struct FwdPlan {
     FwdFamily family;
@@ -64,12 +66,13 @@ struct FwdPlan {
 inline FwdPlan plan_fwd(const PLayout &L, int64_t n, int mode) {
     FwdPlan p{FwdFamily::Refused, L.cont != 0, L.H / 64, 0, 256, 0, TMA_DISPATCH_NONE};
     const int64_t tiles = ceil_div(n, 16), groups = ceil_div(n, 32);
-    const int nets = (mode == 0 || mode == 3) ? 2 : 1;
+    const int nets = (mode == 0 || mode == 3 || mode == 4) ? 2 : 1;
     if (L.img_pi >= 0) {  // both nets' weight images in LDS
         p.family = FwdFamily::H64, p.id = TMA_DISPATCH_FWD_H64;
         const int wpb = tiles >= 512 ? 4 : (tiles >= 64 ? 2 : 1);  // waves per block
         p.grid = ceil_div(tiles, wpb) < H64_FWD_BLOCK_CAP ? ceil_div(tiles, wpb) : H64_FWD_BLOCK_CAP;
         p.block = 64 * wpb, p.lds = nets * FWD_IMG * 4;
+        if (mode == 4) p.lds += wpb * H64_HEAD_STAGE * 4;  // a wave's [16][A] head tile on its way to a coalesced store
     } else if (L.bf16 || (wide_width(L) && fwd_wide_smem_bytes(L) <= LDS_LIMIT)) {  // column-parallel: row groups of 32, one block per group and net
         p.family = L.bf16 ? FwdFamily::WideBF16 : FwdFamily::WideF32;
         p.id = (L.bf16 ? (p.cont ? TMA_DISPATCH_FWD_BF16_NTW2_BOX : TMA_DISPATCH_FWD_BF16_NTW2_DISCRETE)

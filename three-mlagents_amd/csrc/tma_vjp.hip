@@ -15,6 +15,11 @@
 // Summation order of one gradient element: rows in order inside a segment, segments in order inside a chunk, chunks in order.  It depends on
 // (shape, n, chunk length) and on nothing else, so equal inputs give equal bits.
 // Both kernels are bounded loops over their own rows: no spin waits, no exchange between workgroups.
+//
+// tma_policy_head_backward (ABI 218) is the same two launches for the head itself (tma_policy_head: logits / mean, and values):
+//   grad[e] = sum_i sum_j g_head[i][j] dhead_ij/dp_e + sum_i g_values[i] dV_i/dp_e.
+// Phase (a) takes dz3 of a policy row straight from g_head's row (vjp_tile_body<.., HEAD>); phase (b) is the code above, unchanged, and its
+// log_std job sums a plane of zeros.
 #include "tma_ppo_types.h"
 
 #include <cstdlib>
@@ -52,7 +57,9 @@ __device__ __forceinline__ void store_tile(const float *t, int ld, int cols, flo
 }
 
 // ---- (a) one wave per tile: forward, head cotangent, input gradients -> planes
-template <bool CONT, bool IS_PI>
+// HEAD (tma_policy_head_backward, ABI 218): the head cotangent is the caller's -- `g_logp` carries g_head f32[n][A] (or null), `actions` and
+// `g_entropy` are not read, the head's forward is not needed, and the Box head's log_std plane is zeros (the head does not depend on log_std)
+template <bool CONT, bool IS_PI, bool HEAD = false>
 __device__ __forceinline__ void vjp_tile_body(const float *__restrict__ params, const PLayout &L, const float *__restrict__ obs,
                                               const void *__restrict__ actions, int64_t row_base, int rows, const float *__restrict__ g_values,
                                               const float *__restrict__ g_logp, const float *__restrict__ g_entropy, const VjpPlanes &ws, float *smem) {
@@ -73,9 +80,9 @@ __device__ __forceinline__ void vjp_tile_body(const float *__restrict__ params, 
             const bool valid = row0 + lane < rows;
             const int64_t grow = row_base + row0 + lane;
             row_off[lane] = valid ? grow : -1;
-            meta[lane * 4 + 0] = (valid && g_logp != nullptr) ? g_logp[grow] : 0.0f;
-            meta[lane * 4 + 1] = (valid && g_entropy != nullptr) ? g_entropy[grow] : 0.0f;
-            meta[lane * 4 + 2] = (!CONT && IS_PI && valid) ? __int_as_float(static_cast<const int32_t *>(actions)[grow]) : 0.0f;
+            meta[lane * 4 + 0] = (!HEAD && valid && g_logp != nullptr) ? g_logp[grow] : 0.0f;
+            meta[lane * 4 + 1] = (!HEAD && valid && g_entropy != nullptr) ? g_entropy[grow] : 0.0f;
+            meta[lane * 4 + 2] = (!HEAD && !CONT && IS_PI && valid) ? __int_as_float(static_cast<const int32_t *>(actions)[grow]) : 0.0f;
             meta[lane * 4 + 3] = (valid && g_values != nullptr) ? g_values[grow] : 0.0f;
         }
         load_obs_tile(obs, row_off, D, X, ldx, lane);
@@ -89,6 +96,19 @@ __device__ __forceinline__ void vjp_tile_body(const float *__restrict__ params, 
                 const int row = g * 4 + r;
                 dz3[row * ld3 + r16] = r16 == 0 ? meta[row * 4 + 3] : 0.0f;  // dV/dz3 = 1
                 dz3[row * ld3 + 16 + r16] = 0.0f;
+            }
+        } else if constexpr (HEAD) {
+            const float *g_head = g_logp;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int row = g * 4 + r;
+                const int64_t off = row_off[row];
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const int col = 16 * j + r16;
+                    dz3[row * ld3 + col] = (g_head != nullptr && off >= 0 && col < A) ? g_head[off * A + col] : 0.0f;
+                    if constexpr (CONT) ws.dls[(int64_t)(row0 + row) * VJP_LD3 + col] = 0.0f;
+                }
             }
         } else if constexpr (!CONT) {
             f32x4 acc[1];
@@ -147,14 +167,14 @@ __device__ __forceinline__ void vjp_tile_body(const float *__restrict__ params, 
 }
 
 // grid (tile blocks, 2): blockIdx.y = 0 the policy net, 1 the value net
-template <bool CONT>
+template <bool CONT, bool HEAD = false>
 __global__ __launch_bounds__(256) void vjp_tile_kernel(const float *__restrict__ params, PLayout L, const float *__restrict__ obs,
                                                        const void *__restrict__ actions, int64_t row_base, int rows,
                                                        const float *__restrict__ g_values, const float *__restrict__ g_logp,
                                                        const float *__restrict__ g_entropy, VjpPlanes ws) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (blockIdx.y == 0) vjp_tile_body<CONT, true>(params, L, obs, actions, row_base, rows, g_values, g_logp, g_entropy, ws, smem);
-    else vjp_tile_body<CONT, false>(params, L, obs, actions, row_base, rows, g_values, g_logp, g_entropy, ws, smem);
+    if (blockIdx.y == 0) vjp_tile_body<CONT, true, HEAD>(params, L, obs, actions, row_base, rows, g_values, g_logp, g_entropy, ws, smem);
+    else vjp_tile_body<CONT, false, HEAD>(params, L, obs, actions, row_base, rows, g_values, g_logp, g_entropy, ws, smem);
 }
 
 // ---- (b) output-stationary weight-gradient GEMMs.  Jobs of one net, in block order:
@@ -294,15 +314,13 @@ int64_t tma_policy_vjp_workspace_bytes(const tma_policy_dims *d, int64_t n) {
     return (n16 < chunk ? n16 : chunk) * vjp_row_floats(L) * 4;
 }
 
-int tma_policy_evaluate_actions_backward(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
-                                         const float *g_values, const float *g_logp, const float *g_entropy, float *grad_out, void *workspace,
-                                         int64_t workspace_bytes, void *stream) {
-    const char *who = "tma_policy_evaluate_actions_backward";
-    int rc = vjp_check(d, who);  // (every refusal comes back before the first HIP call)
-    if (rc) return rc;
-    if (!params || !obs || !actions || !grad_out) return fail(TMA_ERR_INVALID, "%s: null buffer", who);
-    if (n < 1) return fail(TMA_ERR_INVALID, "%s: n must be >= 1", who);
-    if (!g_values && !g_logp && !g_entropy) return fail(TMA_ERR_INVALID, "%s: g_values, g_logp and g_entropy are all null", who);
+}  // extern "C"
+
+// both entry points behind their own null checks.  head: g_logp carries g_head f32[n][act_dim], actions / g_entropy are null
+static int vjp_run(const char *who, bool head, const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
+                   const float *g_values, const float *g_logp, const float *g_entropy, float *grad_out, void *workspace, int64_t workspace_bytes,
+                   void *stream) {
+    int rc = TMA_OK;
     const int64_t need = tma_policy_vjp_workspace_bytes(d, n);
     if (!workspace || workspace_bytes < need)
         return fail(TMA_ERR_INVALID, "%s: workspace of %lld bytes, tma_policy_vjp_workspace_bytes reports %lld", who, (long long)(workspace ? workspace_bytes : 0),
@@ -347,7 +365,8 @@ int tma_policy_evaluate_actions_backward(const float *params, const tma_policy_d
             TMA_LAUNCH_CHECK();
             return TMA_OK;
         };
-        rc = L.cont ? launch_a(vjp_tile_kernel<true>) : launch_a(vjp_tile_kernel<false>);
+        if (head) rc = L.cont ? launch_a(vjp_tile_kernel<true, true>) : launch_a(vjp_tile_kernel<false, true>);
+        else rc = L.cont ? launch_a(vjp_tile_kernel<true>) : launch_a(vjp_tile_kernel<false>);
         if (rc) return rc;
         const float *obs_chunk = obs + base * L.D;
         if (wide) vjp_reduce_kernel<4, 8><<<dim3((unsigned)n_blocks), dim3(512), 0, s>>>(L, ws, obs_chunk, rows, grad_out, base > 0 ? 1 : 0);
@@ -355,6 +374,31 @@ int tma_policy_evaluate_actions_backward(const float *params, const tma_policy_d
         TMA_LAUNCH_CHECK();
     }
     return TMA_OK;
+}
+
+extern "C" {
+
+int tma_policy_evaluate_actions_backward(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
+                                         const float *g_values, const float *g_logp, const float *g_entropy, float *grad_out, void *workspace,
+                                         int64_t workspace_bytes, void *stream) {
+    const char *who = "tma_policy_evaluate_actions_backward";
+    const int rc = vjp_check(d, who);  // (every refusal comes back before the first HIP call)
+    if (rc) return rc;
+    if (!params || !obs || !actions || !grad_out) return fail(TMA_ERR_INVALID, "%s: null buffer", who);
+    if (n < 1) return fail(TMA_ERR_INVALID, "%s: n must be >= 1", who);
+    if (!g_values && !g_logp && !g_entropy) return fail(TMA_ERR_INVALID, "%s: g_values, g_logp and g_entropy are all null", who);
+    return vjp_run(who, false, params, d, obs, actions, n, g_values, g_logp, g_entropy, grad_out, workspace, workspace_bytes, stream);
+}
+
+int tma_policy_head_backward(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, const float *g_head, const float *g_values,
+                             float *grad_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    const char *who = "tma_policy_head_backward";
+    const int rc = vjp_check(d, who);  // (every refusal comes back before the first HIP call)
+    if (rc) return rc;
+    if (!params || !obs || !grad_out) return fail(TMA_ERR_INVALID, "%s: null buffer", who);
+    if (n < 1) return fail(TMA_ERR_INVALID, "%s: n must be >= 1", who);
+    if (!g_head && !g_values) return fail(TMA_ERR_INVALID, "%s: g_head and g_values are both null", who);
+    return vjp_run(who, true, params, d, obs, nullptr, n, g_values, g_head, nullptr, grad_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

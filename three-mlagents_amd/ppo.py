@@ -101,6 +101,25 @@ class _EvaluateActions(torch.autograd.Function):
         return ctx.policy.evaluate_actions_backward(ctx.obs, ctx.actions, g_values, g_logp, g_entropy), None, None, None
 
 
+class _Head(torch.autograd.Function):
+    """head as a node of a torch autograd graph, written like _EvaluateActions: the forward is the forward-only call, the backward ONE
+    tma_policy_head_backward launch sequence with whichever of the two cotangents autograd supplies."""
+
+    @staticmethod
+    def forward(ctx, leaf, policy, obs):
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None -> NULL, not as a zero array
+        ctx.save_for_backward(leaf)
+        ctx.policy, ctx.obs = policy, obs
+        return policy._head(obs)
+
+    @staticmethod
+    def backward(ctx, g_head, g_values):
+        (leaf,) = ctx.saved_tensors
+        if g_head is None and g_values is None:
+            return torch.zeros_like(leaf), None, None
+        return ctx.policy.head_backward(ctx.obs, g_head, g_values), None, None
+
+
 class HipActorCriticPolicy:
     """Parameters of SB3's ActorCriticPolicy(MlpPolicy) in one flat HBM buffer + the forward kernels."""
 
@@ -277,6 +296,69 @@ class HipActorCriticPolicy:
                                                           _lib.ptr(cots[0]), _lib.ptr(cots[1]), _lib.ptr(cots[2]), _lib.ptr(grad),
                                                           _lib.ptr(self._vjp_ws), self._vjp_ws.numel(), _lib.stream_ptr(self.device)))
         return grad
+
+    def head(self, obs: torch.Tensor):
+        """(head, values), device tensors [n, act_dim] and [n]: the policy net's head before any distribution arithmetic -- the raw logits of a
+        Discrete policy (action_net's output, not normalised), the mean of a Box policy -- and the values (tma_policy_head: the kernels `act`
+        runs, so `values` carries act's bits and a Box head those of act(deterministic=True)'s actions).
+
+        After `parameters()` -- and while its leaf requires grad and torch.is_grad_enabled() -- both outputs are nodes of a torch autograd graph
+        (one tma_policy_head_backward call), as evaluate_actions' are.  Gradients with respect to `obs` are not built: an `obs` that requires
+        grad is a ValueError."""
+        self._sync_if_stepped()
+        differentiable = self._leaf is not None and self._leaf.requires_grad and torch.is_grad_enabled()
+        if differentiable and isinstance(obs, torch.Tensor) and obs.requires_grad:
+            raise ValueError("head: gradients with respect to the observations are not built (obs.requires_grad is set)")
+        obs = self._rows(obs.detach())
+        if differentiable:
+            return _Head.apply(self._leaf, self, obs)
+        return self._head(obs)
+
+    def _head(self, obs: torch.Tensor):
+        n = obs.shape[0]
+        head = torch.empty((n, self.act_dim), dtype=torch.float32, device=self.device)
+        values = torch.empty((n,), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().tma_policy_head(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), n, _lib.ptr(head), _lib.ptr(values),
+                                              _lib.stream_ptr(self.device)))
+        return head, values
+
+    def head_backward(self, obs: torch.Tensor, g_head=None, g_values=None) -> torch.Tensor:
+        """Vector-Jacobian product of `head` with respect to the trainable parameters (tma_policy_head_backward): the flat gradient [n_trainable]
+        of  sum_ij g_head[i, j] head[i, j] + sum_i g_values[i] V_i.  A cotangent may be None (zeros), not both.  The log_std segment of a Box
+        policy comes back as zeros.  Deterministic: equal inputs give equal bits."""
+        self._sync_if_stepped()
+        obs = self._rows(obs.detach())
+        n = obs.shape[0]
+        cots = []
+        for name, c, shape in (("g_head", g_head, (n, self.act_dim)), ("g_values", g_values, (n,))):
+            if c is not None:
+                if tuple(c.shape) != shape:
+                    raise ValueError(f"{name} must have shape {list(shape)}, got {list(c.shape)}")
+                c = c.detach().to(self.device, torch.float32).contiguous()
+            cots.append(c)
+        L = _lib.lib()
+        need = int(L.tma_policy_vjp_workspace_bytes(C.byref(self.dims), n))
+        if need <= 0:
+            _lib.check(_lib.TMA_ERR_INVALID)
+        if self._vjp_ws is None or self._vjp_ws.numel() < need:  # (shared with evaluate_actions_backward)
+            self._vjp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        grad = torch.empty(self.n_trainable, dtype=torch.float32, device=self.device)
+        _lib.check(L.tma_policy_head_backward(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), n, _lib.ptr(cots[0]), _lib.ptr(cots[1]),
+                                              _lib.ptr(grad), _lib.ptr(self._vjp_ws), self._vjp_ws.numel(), _lib.stream_ptr(self.device)))
+        return grad
+
+    def get_distribution(self, obs: torch.Tensor):
+        """SB3's ActorCriticPolicy.get_distribution(obs): the action distribution of every row as a distributions.CategoricalDistribution /
+        DiagGaussianDistribution built on `head` -- `.distribution` is the torch.distributions object a loss on the whole distribution takes
+        (kl_divergence between two policies, distillation).  Box: std = exp(log_std), log_std a view of the parameter leaf when `parameters()`
+        made one (its gradient reaches leaf.grad through torch), else of the flat buffer."""
+        from .distributions import CategoricalDistribution, DiagGaussianDistribution
+
+        head, _ = self.head(obs)
+        if not self.continuous:
+            return CategoricalDistribution(head)
+        src = self._leaf if self._leaf is not None else self.params
+        return DiagGaussianDistribution(head, src[self.offsets[12]:self.offsets[12] + self.act_dim])
 
     def predict_values(self, obs: torch.Tensor) -> torch.Tensor:
         self._sync_if_stepped()
