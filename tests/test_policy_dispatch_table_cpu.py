@@ -86,7 +86,7 @@ def check_planned_cases(switch_entry=None):
         if ident.startswith("GRAD_BF16_"):
             assert entry.endswith("_bf16") and block in (256, 512) and (grid, block) == t.bf_expected_geometry(ident, cont, B), (case, grid, block)
         n += 1
-    rows = {"grad_nodefer": 3, "grad_nw4_bf16": 3, "grad_mt2_bf16": 1}
+    rows = {"grad_nodefer": 3, "grad_nw4_bf16": 3, "grad_mt2_bf16": 1, "grad_nw8_bf16x3": 2}
     assert sorted(rows) == sorted(t.SWITCH_ENTRIES)
     assert n == (rows[switch_entry] if switch_entry else len(t.CASES) - sum(rows.values()))
     assert not torch.cuda.is_initialized()
@@ -116,6 +116,10 @@ def test_plan_query_gives_the_bf16_four_wave_cases_their_ids_in_a_child_process(
 
 def test_plan_query_gives_the_bf16_32_row_group_case_its_id_in_a_child_process():
     _planned_in_child("grad_mt2_bf16")
+
+
+def test_plan_query_gives_the_split_eight_wave_cases_their_ids_in_a_child_process():
+    _planned_in_child("grad_nw8_bf16x3")
 
 
 def test_every_bf16_gradient_leaf_has_a_case_at_every_width_and_head_it_takes():

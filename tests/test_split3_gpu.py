@@ -1,7 +1,9 @@
 """mfma_dtype = "bf16x3" (round 5, opt-in): the f32 update of the reference's default 256 x 256 policy (backend/mlagents/training.py:363-365) on
 the bf16 MFMA with every operand as three bf16 terms (csrc/tma_split3.h).  Held to the bound the exact-f32 kernels are held to against autograd
 (2e-5 of the largest gradient entry: tests/test_ppo_gpu.py), and compared with the exact-f32 kernel on the same inputs; the weight planes the
-optimizer maintains (scatter into three planes per Adam step) must equal a rebuild from the master weights; training must still learn."""
+optimizer maintains (scatter into three planes per Adam step) must equal a rebuild from the master weights; training must still learn; a
+prepared epoch equals self-contained minibatch calls bit for bit.  The kernel's edges (ragged row groups from 4096 samples on, observation
+classes, head widths, the eight-wave instantiations) against a float64 emulation of the split: the bf16x3 rows of tests/test_policy_dispatch_gpu.py."""
 import ctypes as C
 
 import numpy as np
@@ -67,6 +69,51 @@ def test_split3_small_minibatches_stay_on_the_exact_kernel():
     g, _, _ = _hip_grad(pol, bufs, T, N, perm, 10, B, HP)
     g32, _, _ = _hip_grad(pol32, bufs, T, N, perm, 10, B, HP)
     assert torch.equal(g, g32)
+
+
+def test_split3_prepared_epoch_equals_self_contained_minibatches():
+    """One epoch of 3 * 4096 + 1000 rows at batch_size 4096 on a split policy: tma_ppo_epoch_prepare + prepared minibatches against
+    self-contained tma_ppo_minibatch_grad calls over the same on-device permutation -- gradients and statistic slots bit for bit; the three
+    full minibatches run the split kernel, the 1000-row tail the exact-f32 half-group kernel (below the 4096-sample switch)."""
+    from test_policy_dispatch_gpu import _last_dispatch, _name, expected_value
+    from three_mlagents_amd import _lib
+
+    D, A, H, T, N, batch = 6, 5, 256, 8, 1661, 4096
+    total = T * N
+    assert total == 3 * 4096 + 1000
+    pol, sd = _policy(D, H, A, "bf16x3")
+    pol32, _ = _policy(D, H, A, "f32")
+    obs, actions, old_lp, adv, ret = _rollout(pol32, sd, D, A, False, T, N)
+    dev = torch.device("cuda", 0)
+    d = {k: v.to(dev).contiguous() for k, v in dict(obs=obs, actions=actions, old_lp=old_lp, adv=adv, ret=ret).items()}
+    rv = _lib.Rollout(_lib.ptr(d["obs"]), _lib.ptr(d["actions"]), _lib.ptr(d["old_lp"]), _lib.ptr(d["adv"]), _lib.ptr(d["ret"]), T, N)
+    hpar = _lib.PPOHParams(0.2, 0.01, 0.5, 1)
+    L = _lib.lib()
+    ws = torch.zeros(int(L.tma_ppo_workspace_bytes(C.byref(pol.dims))), dtype=torch.uint8, device=dev)
+
+    def run(prepared):
+        out = []
+        if prepared:
+            ep = _lib.Minibatch(None, 77, 3, 0, total, 0)
+            _lib.check(L.tma_ppo_epoch_prepare(C.byref(rv), C.byref(ep), batch, C.byref(pol.dims), _lib.ptr(ws), _lib.stream_ptr()))
+        for start in range(0, total, batch):
+            mb = _lib.Minibatch(None, 77, 3, start, min(batch, total - start), batch if prepared else 0)
+            grad = torch.zeros(pol.n_trainable, device=dev)
+            _lib.check(L.tma_ppo_minibatch_grad(_lib.ptr(pol.params), C.byref(pol.dims), C.byref(rv), C.byref(mb), C.byref(hpar), _lib.ptr(grad),
+                                                _lib.ptr(ws), _lib.stream_ptr()))
+            st = (C.c_double * 8)()
+            _lib.check(L.tma_ppo_pop_stats(_lib.ptr(ws), st, _lib.stream_ptr()))
+            out.append((grad.cpu(), list(st), _last_dispatch()[1]))
+        return out
+
+    a, b = run(False), run(True)
+    assert len(a) == len(b) == 4
+    want = ["GRAD_BF16X3"] * 3 + ["GRAD_F32_KT1_HALF_W8_DEFER"]
+    for k, ((g0, s0, id0), (g1, s1, id1)) in enumerate(zip(a, b)):
+        assert id0 == id1 == expected_value(want[k]), (k, _name(id0), _name(id1))
+        assert torch.equal(g0.view(torch.int32), g1.view(torch.int32)), k
+        assert s0 == s1 and s0[5] == min(batch, total - k * batch), (k, s0, s1)
+        assert float(g0.abs().max()) > 0.0
 
 
 def test_split3_planes_follow_the_optimizer_and_training_learns():
