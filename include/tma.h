@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 218
+#define TMA_VERSION 219
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -642,10 +642,25 @@ int tma_vecnorm_get_original(tma_vecnorm *h, float *obs_out, float *rewards_out,
  * window) with one tma_vecnorm_step behind every tma_env_step, BEFORE the bootstrap that reads that step's terminal_obs and rewards: SB3 adds
  * gamma * V(normalised terminal observation) to the normalised reward.  The buffers end up holding normalised observations and rewards.
  * b->obs slot t_begin must hold NORMALISED observations (tma_vecnorm_reset, or the previous call's last slot).  training = 0 freezes the
- * statistics (evaluation).  The fused chunk kernels are not used: every shape runs launch by launch. */
+ * statistics (evaluation).
+ * ABI 219: where tma_rollout_norm_plan answers with a fused value, and the env handle is reset, the VecNormalize step runs INSIDE the 8-env-tile
+ * f32 fused chunk kernel of tma_rollout_collect -- one launch per chunk (bounded by tma_env_steps_until_refill and terminal_obs_slots) plus one
+ * batched tma_policy_values and one tma_policy_bootstrap launch over the chunk's normalised rows -- with the running statistics in LDS for the
+ * whole chunk.  It leaves, bit for bit, what the per-step composition leaves: buffers, statistics, returns, the raw copies.  Every other shape
+ * runs launch by launch as before; TMA_NO_NORM_FUSED=1 (read once) keeps every shape there. */
 int tma_rollout_collect_norm(tma_env *env, tma_vecnorm *vn, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b, int t_begin,
                              int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, uint32_t env_offset, double gamma, int compute_last_values,
                              int deterministic, int training, void *stream);
+/* Which path tma_rollout_collect_norm takes for (task, dims, N envs, training) (ABI 219; a host-only query, no HIP call).  Fused where
+ * tma_rollout_collect would run its 8-env-tile f32 chunk kernel for the 256-wide policy -- hidden 256, f32 operands, obs_dim / act_dim the
+ * task's; Discrete tasks, or Crawler / Ant with Box actions -- and, with training != 0, N <= 8: the vector is then one tile and a step's
+ * moments one workgroup's work; with training == 0 rows are independent and N may reach the kernel's own cap (2048 Discrete, 4096 Box).
+ * Everything else is PER_STEP.  Bad dims, N < 1 or an unknown task: -TMA_ERR_INVALID / -TMA_ERR_UNKNOWN_TASK. */
+enum { TMA_ROLLOUT_NORM_PER_STEP = 0, TMA_ROLLOUT_NORM_FUSED_DISC_F32 = 1, TMA_ROLLOUT_NORM_FUSED_CONT_F32 = 2 };
+int tma_rollout_norm_plan(int task, const tma_policy_dims *d, int64_t N, int training);
+/* Test aid (ABI 219): the plan value the calling thread's last tma_rollout_collect_norm actually launched (PER_STEP also where a switch or an
+ * env handle that is not reset kept it off the fused kernels). */
+int tma_debug_last_rollout_norm_path(void);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ ACT_I32, ACT_I64, ACT_F32 = 0, 1, 2
 EP_STRIDE = 1 << 20
 EV_SCRATCH_DOUBLES = 1536  # include/tma.h TMA_EV_SCRATCH_DOUBLES
 VECNORM_ONE_LAUNCH_MAX = 256  # include/tma.h TMA_VECNORM_ONE_LAUNCH_MAX
+ROLLOUT_NORM_PER_STEP, ROLLOUT_NORM_FUSED_DISC_F32, ROLLOUT_NORM_FUSED_CONT_F32 = 0, 1, 2  # include/tma.h TMA_ROLLOUT_NORM_*: tma_rollout_norm_plan
 
 _vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_double
 
@@ -161,6 +162,8 @@ SIGNATURES = {
     "tma_vecnorm_get_returns": (_i32, [_vp, _vp, _vp]),
     "tma_vecnorm_get_original": (_i32, [_vp, _vp, _vp, _vp]),
     "tma_rollout_collect_norm": (_i32, [_vp, _vp, _vp, _pd, C.POINTER(RolloutBuffers), _i32, _i32, _i32, _u32, _u32, _u32, _f64, _i32, _i32, _i32, _vp]),
+    "tma_rollout_norm_plan": (_i32, [_i32, _pd, _i64, _i32]),
+    "tma_debug_last_rollout_norm_path": (_i32, []),
 }
 
 # tma_allreduce_fn (include/tma.h): int (*)(void *ctx, float *buffer, int64_t count)

@@ -7,6 +7,7 @@
 // /root/reference/backend/mlagents/training.py:166-170 -> SB3 collect_rollouts (SURVEY.md §3.1 hot loop A, App. C.6).
 #include "tma_internal.h"
 #include "tma_h64_tile.h"
+#include "tma_vecnorm.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -1645,6 +1646,9 @@ __global__ __launch_bounds__(512, 2) void rollout_chunk_wide_cont_pi_kernel(EnvV
     }
 }
 
+// floats of LDS of the 8-env form of rollout_chunk_wide_f32_kernel: X, h1, h2 (16 rows), W3 rows, logits
+__host__ __device__ constexpr int wide_f32_lds_floats(int ldx) { return 8 * ldx + 8 * 260 + 16 * 260 + 8 * 260 + 64; }
+
 // ------------------------------------------------------------------------------------------
 // Fused rollout chunk for the reference's OWN default policy and dtype -- MLP(256, 256), f32 (backend/mlagents/training.py:363-365) -- on
 // the Discrete tasks with observations of up to 32 floats: ONE launch advances every env by n_steps vector steps.
@@ -1661,11 +1665,18 @@ __global__ __launch_bounds__(512, 2) void rollout_chunk_wide_cont_pi_kernel(EnvV
 // and log-probabilities are bit-identical to the per-step composition, which pays two launches, the observation's HBM round trip and
 // the whole weight matrix from L2 per vector step (28 us per step at 8 envs, 13 us at 4096).
 // ------------------------------------------------------------------------------------------
-template <class T, int MROWS>
+//
+// NORM (8-env tiles only): a VecNormalize step in the step loop (tma_rollout_collect_norm).  After wave 0 has stored the tile's raw next
+// observations, rewards, flags and terminal observations, and behind a barrier, all four waves run vn_chunk_step (tma_vecnorm.h: the code of
+// vn_step_one_kernel) on those rows: moments, merge into the running statistics held in LDS, then observations normalised in buffer slot
+// t + 1 and in the LDS tile X that the next step's layer 1 reads, rewards and the truncated rows' terminal observations normalised in place.
+// The Monitor sum `er` stays raw.  Training: ONE tile is the whole vector (N <= 8); frozen statistics: any number of tiles.
+template <class T, int MROWS, bool NORM = false>
 __global__ __launch_bounds__(256, 1) void rollout_chunk_wide_f32_kernel(EnvView v, const float *__restrict__ params, PLayout L, ChunkPtrs b,
                                                                         float *__restrict__ term_obs, int t0, int n_steps, uint32_t rng_seed,
-                                                                        uint32_t rng_step0, int det) {
+                                                                        uint32_t rng_step0, int det, std::conditional_t<NORM, VnChunk, VnNone> vn) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
+    static_assert(!NORM || MROWS == 8, "the normalised form exists on the 8-env tiles");
     // MROWS = 8 (round 6): tiles of EIGHT envs -- the reference's own 8-env runs, and every run of up to 2048 envs (256 blocks).  A 16 x 16 x 4
     // tile pads 8 envs to 16 rows: half the matrix pipe's work is zeros.  v_mfma_f32_4x4x1_16b_f32 with the A operand of one block broadcast to
     // all sixteen (CBSZ = 4, ABID = e) is 4 envs x 64 columns x 1 k in 8 cycles: a wave's 64 columns of both hidden layers are two such
@@ -1754,6 +1765,9 @@ __global__ __launch_bounds__(256, 1) void rollout_chunk_wide_f32_kernel(EnvView 
         const int row = e / ldx, c = e - row * ldx;
         X[e] = (row0 + row < N && c < D) ? b.obs[((int64_t)t0 * N + row0 + row) * D + c] : 0.0f;
     }
+    [[maybe_unused]] int vn_p = 0;  // NORM: which of the two LDS statistics buffers is current
+    if constexpr (NORM)  // the running statistics and the step's scratch: doubles behind the float images
+        vn_chunk_begin(vn, VnChunkLds(reinterpret_cast<double *>(smem_f + wide_f32_lds_floats(ldx)), D));
     __syncthreads();
     double sret = 0.0, slen = 0.0, scnt = 0.0;
 #ifdef TMA_ROLL_TICKS
@@ -1947,9 +1961,20 @@ __global__ __launch_bounds__(256, 1) void rollout_chunk_wide_f32_kernel(EnvView 
             }
             TMA_RTICK(5);
         }
+        if constexpr (NORM) {
+            __syncthreads();  // the tile's raw rows of this step are stored
+            VnArgs a = vn.a;
+            a.obs = b.obs + (int64_t)(t + 1) * N * D, a.rewards = b.rewards + (int64_t)t * N, a.term_obs = term_obs + (int64_t)k * N * D;
+            a.terminated = b.terminated + (int64_t)t * N, a.truncated = b.truncated + (int64_t)t * N;
+            if (k != n_steps - 1) a.raw_obs = nullptr, a.raw_rew = nullptr;  // the raw copies are those of the last step
+            const int64_t left = N - row0;
+            vn_chunk_step(a, VnChunkLds(reinterpret_cast<double *>(smem_f + wide_f32_lds_floats(ldx)), D), vn.stats_out != nullptr, vn_p, row0,
+                          left < M ? left : M, X, ldx);
+        }
         __syncthreads();
         TMA_RTICK(6);
     }
+    if constexpr (NORM) vn_chunk_end(vn, VnChunkLds(reinterpret_cast<double *>(smem_f + wide_f32_lds_floats(ldx)), D), vn_p);
     if (owner) {
         T::pack(v.st, N, i, s);
         v.ep_ret[i] = er;
@@ -1999,10 +2024,11 @@ struct WideContF32Lds {
     // [SW][M], truncated / done flags, per-joint terms of the multi-lane env step
     static constexpr int floats() { return M * LDX + 2 * M * LD + AP * LD + 2 * M * 32 + T::SW * M + 64 + M * T::NJ * 5; }
 };
-template <class T>
+// NORM: rollout_chunk_wide_f32_kernel's VecNormalize step, in the same place of the step loop.
+template <class T, bool NORM = false>
 __global__ __launch_bounds__(256, 1) void rollout_chunk_wide_cont_f32_kernel(EnvView v, const float *__restrict__ params, PLayout L, ChunkPtrs b,
                                                                              float *__restrict__ term_obs, int t0, int n_steps, uint32_t rng_seed,
-                                                                             uint32_t rng_step0, int det) {
+                                                                             uint32_t rng_step0, int det, std::conditional_t<NORM, VnChunk, VnNone> vn) {
     extern __shared__ __attribute__((aligned(16))) float smem_cf[];
     using W = WideContF32Lds<T>;
     constexpr int M = W::M, H = W::H, ld = W::LD, ldx = W::LDX, D = T::OBS, AD = T::ADIM, KQ1 = (D + 3) >> 2, KS2 = H / 4;
@@ -2050,6 +2076,9 @@ __global__ __launch_bounds__(256, 1) void rollout_chunk_wide_cont_f32_kernel(Env
         X[e] = (row0 + row < N && c < D) ? b.obs[((int64_t)t0 * N + row0 + row) * D + c] : 0.0f;
     }
     if (threadIdx.x < 64) trf[threadIdx.x] = 0;  // (trf and dnf)
+    [[maybe_unused]] int vn_p = 0;  // NORM: which of the two LDS statistics buffers is current
+    if constexpr (NORM)  // the running statistics and the step's scratch: doubles behind the float images
+        vn_chunk_begin(vn, VnChunkLds(reinterpret_cast<double *>(smem_cf + W::floats()), D));
     __syncthreads();
     const float *ls = params + L.log_std;
     float lsd_v[2], sd_v[2];  // log_std and exp(log_std) of this lane's two action columns: constant over the launch
@@ -2205,9 +2234,19 @@ __global__ __launch_bounds__(256, 1) void rollout_chunk_wide_cont_f32_kernel(Env
             if (grp_ok) T::template obs_lanes<8>(s, sub, ObsDualF{b.obs + ((int64_t)(t + 1) * N + i) * D, X + my_row * ldx});
             TMA_RTICK(5);
         }
+        if constexpr (NORM) {
+            __syncthreads();  // the tile's raw rows of this step are stored
+            VnArgs a = vn.a;
+            a.obs = b.obs + (int64_t)(t + 1) * N * D, a.rewards = b.rewards + (int64_t)t * N, a.term_obs = term_obs + (int64_t)k * N * D;
+            a.terminated = b.terminated + (int64_t)t * N, a.truncated = b.truncated + (int64_t)t * N;
+            if (k != n_steps - 1) a.raw_obs = nullptr, a.raw_rew = nullptr;  // the raw copies are those of the last step
+            const int64_t left = N - row0;
+            vn_chunk_step(a, VnChunkLds(reinterpret_cast<double *>(smem_cf + W::floats()), D), vn.stats_out != nullptr, vn_p, row0, left < M ? left : M, X, ldx);
+        }
         __syncthreads();
         TMA_RTICK(6);
     }
+    if constexpr (NORM) vn_chunk_end(vn, VnChunkLds(reinterpret_cast<double *>(smem_cf + W::floats()), D), vn_p);
     if (owner) {
         T::pack(v.st, N, i, sl[my_row]);
         v.ep_ret[i] = er;
@@ -2231,12 +2270,21 @@ __global__ __launch_bounds__(256, 1) void rollout_chunk_wide_cont_f32_kernel(Env
 
 template <class T>
 static int launch_chunk_wide_cont_f32(tma_env *env, const float *params, const PLayout &L, const ChunkPtrs &b, float *term_obs, int t0, int n,
-                                      uint32_t rng_seed, uint32_t rng_step0, int det, hipStream_t s) {
+                                      uint32_t rng_seed, uint32_t rng_step0, int det, hipStream_t s, const VnChunk *vn = nullptr) {
     if constexpr (T::FUSED_ROLLOUT && T::NACT == 0 && T::ADIM <= 32 && !T::USES_MT && T::OBS <= 192) {
+        if (vn) {  // a VecNormalize step in the step loop: its float64 statistics and scratch behind the float images
+            static_assert(WideContF32Lds<T>::floats() % 2 == 0, "the doubles behind the float images are 8-byte aligned");
+            auto k = rollout_chunk_wide_cont_f32_kernel<T, true>;
+            const int smem = WideContF32Lds<T>::floats() * 4 + vn_chunk_lds_doubles(T::OBS) * 8;
+            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+            k<<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, *vn);
+            TMA_LAUNCH_CHECK();
+            return TMA_OK;
+        }
         auto k = rollout_chunk_wide_cont_f32_kernel<T>;
         const int smem = WideContF32Lds<T>::floats() * 4;
         TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        k<<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det);
+        k<<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, VnNone{});
         TMA_LAUNCH_CHECK();
         return TMA_OK;
     } else {
@@ -2246,7 +2294,7 @@ static int launch_chunk_wide_cont_f32(tma_env *env, const float *params, const P
 
 template <class T>
 static int launch_chunk_wide_f32(tma_env *env, const float *params, const PLayout &L, const ChunkPtrs &b, float *term_obs, int t0, int n, uint32_t rng_seed,
-                                 uint32_t rng_step0, int det, hipStream_t s) {
+                                 uint32_t rng_step0, int det, hipStream_t s, const VnChunk *vn = nullptr) {
     // (round 6: BrickBreak -- 45 observations, one of the reference's PPO-default tasks -- on the 8-env tiles, whose layer-1 weights are one register per k)
     if constexpr ((T::FUSED_ROLLOUT && T::OBS <= 32 && T::NACT > 0) || T::ID == TMA_TASK_BRICKBREAK) {
         // tiles of eight envs while they give every env its own block round (up to 2048 envs); TMA_WIDE_F32_ROWS=16 / 8 forces a form (A/B, tests)
@@ -2254,16 +2302,25 @@ static int launch_chunk_wide_f32(tma_env *env, const float *params, const PLayou
         const bool m8 = force ? force == 8 : env->v.N <= 2048;
         if (m8) {
             constexpr int ldx = ((T::OBS + 3) & ~3) + 4;
-            const int smem = (8 * ldx + 8 * 260 + 16 * 260 + 8 * 260 + 64) * 4;  // X, h1, h2 (16 rows), W3 rows, logits
-            rollout_chunk_wide_f32_kernel<T, 8><<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det);
+            const int smem = wide_f32_lds_floats(ldx) * 4;  // X, h1, h2 (16 rows), W3 rows, logits
+            if (vn) {  // a VecNormalize step in the step loop: its float64 statistics and scratch behind the float images
+                static_assert(wide_f32_lds_floats(ldx) % 2 == 0, "the doubles behind the float images are 8-byte aligned");
+                const int smem_n = smem + vn_chunk_lds_doubles(T::OBS) * 8;
+                static_assert(wide_f32_lds_floats(ldx) * 4 + vn_chunk_lds_doubles(T::OBS) * 8 <= 64 * 1024, "no opt-in for the LDS");
+                rollout_chunk_wide_f32_kernel<T, 8, true><<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem_n, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, *vn);
+                TMA_LAUNCH_CHECK();
+                return TMA_OK;
+            }
+            rollout_chunk_wide_f32_kernel<T, 8><<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, VnNone{});
             TMA_LAUNCH_CHECK();
             return TMA_OK;
         }
+        if (vn) return fail(TMA_ERR_INVALID, "fused f32 wide rollout: the normalised form runs on 8-env tiles only");
         if constexpr (T::OBS <= 32) {
             auto k = rollout_chunk_wide_f32_kernel<T, 16>;
             constexpr int ldx = ((T::OBS + 3) & ~3) + 2;
             const int smem = 16 * (ldx + 2 * 258) * 4;
-            k<<<dim3((unsigned)ceil_div(env->v.N, 16)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det);
+            k<<<dim3((unsigned)ceil_div(env->v.N, 16)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, VnNone{});
         } else {
             return fail(TMA_ERR_INVALID, "fused f32 wide rollout: this task runs on 8-env tiles only (up to 2048 envs)");
         }
@@ -2333,6 +2390,24 @@ static int launch_chunk_wide(tma_env *env, const float *params, const PLayout &L
 
 // waves per 16-env tile of the calling thread's last 64-wide fused chunk launch (tma_debug_last_rollout_waves)
 static thread_local int g_roll_waves = 0;
+// the path the calling thread's last tma_rollout_collect_norm took (tma_debug_last_rollout_norm_path)
+static thread_local int g_norm_path = TMA_ROLLOUT_NORM_PER_STEP;
+
+// WHICH path tma_rollout_collect_norm takes for a shape: a pure host function (no HIP call, no global, no environment read), in the manner of
+// tma_policy_plan.h.  Fused exactly where tma_rollout_collect would run rollout_chunk_wide_f32_kernel on its 8-env tiles, or
+// rollout_chunk_wide_cont_f32_kernel, for this (task, dims) -- and, while the statistics move, the vector is ONE tile: the moments of a step
+// are then one workgroup's work.  Frozen statistics: rows are independent, any number of tiles up to the kernel's own cap.
+constexpr int64_t NORM_FUSED_TRAIN_MAX = 8, NORM_FUSED_DISC_MAX = 2048, NORM_FUSED_CONT_MAX = 4096;
+inline int plan_rollout_norm(int task, const PLayout &L, const tma_policy_dims &d, int64_t N, bool training) {
+    if (L.bf16 || L.img_pi >= 0 || L.H != 256 || d.obs_dim != tma_task_obs_dim(task)) return TMA_ROLLOUT_NORM_PER_STEP;
+    const bool box_task = task == TMA_TASK_CRAWLER || task == TMA_TASK_ANT;
+    const bool task_fused = dispatch_task(task, [](auto t) { return decltype(t)::FUSED_ROLLOUT ? 1 : 0; }) == 1;
+    const bool disc = !d.continuous && !box_task && d.act_dim == tma_task_num_actions(task) && ((task_fused && d.obs_dim <= 32) || task == TMA_TASK_BRICKBREAK);
+    const bool cont = d.continuous && box_task && d.act_dim == tma_task_act_dim(task);
+    if (disc && N <= (training ? NORM_FUSED_TRAIN_MAX : NORM_FUSED_DISC_MAX)) return TMA_ROLLOUT_NORM_FUSED_DISC_F32;
+    if (cont && N <= (training ? NORM_FUSED_TRAIN_MAX : NORM_FUSED_CONT_MAX)) return TMA_ROLLOUT_NORM_FUSED_CONT_F32;
+    return TMA_ROLLOUT_NORM_PER_STEP;
+}
 
 // a task whose env step needs more registers than a wave of an eight-wave workgroup has (256) stays on the four-wave kernel: T::ROLL8 = false
 template <class T, class = void>
@@ -2380,6 +2455,134 @@ static int launch_chunk(tma_env *env, const float *params, const PLayout &L, con
     if (smem > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     k<<<dim3((unsigned)ceil_div(tiles, wpb)), dim3(64 * wpb), smem, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
     TMA_LAUNCH_CHECK();
+    return TMA_OK;
+}
+
+// the kernel argument of a normalised chunk: the handle's flags, constants and state as vn_step sets them for its one-launch kernel
+static VnChunk vn_chunk_args(const tma_vecnorm *h, int training) {
+    VnChunk c{};
+    VnArgs &a = c.a;
+    a.upd_obs = (training && h->norm_obs) ? 1 : 0;
+    a.upd_ret = training ? 1 : 0;
+    a.returns = h->returns, a.raw_obs = h->raw_obs, a.raw_rew = h->raw_rew;
+    a.N = h->N, a.D = h->D;
+    a.G = 1, a.rows_blk = h->N, a.rows_apply = h->N, a.seg = vn_pow2ceil(h->N);
+    a.norm_obs = h->norm_obs, a.norm_reward = h->norm_reward;
+    a.clip_obs = h->clip_obs, a.clip_reward = h->clip_reward, a.gamma = h->gamma, a.eps = h->epsilon;
+    c.stats_in = h->stats[h->cur];
+    c.stats_out = (a.upd_obs || a.upd_ret) ? h->stats[h->cur ^ 1] : nullptr;
+    return c;
+}
+
+// Box-action tasks (Crawler / Ant shapes): policy-only fused chunk + ONE batched value launch + ONE batched bootstrap launch per chunk of up to
+// terminal_obs_slots steps.  f32: rollout_chunk_wide_cont_f32_kernel, else the bf16 kernel.  vn != nullptr (f32 only): the normalised form of the
+// chunk kernel on that handle's statistics (tma_rollout_collect_norm); the value and bootstrap launches then read normalised rows.
+static int collect_chunks_cont(tma_env *env, tma_vecnorm *vn, int training, bool fused_cont_f32, const float *params, const tma_policy_dims *d,
+                               const tma_rollout_buffers *b, const PLayout &L, int t_begin, int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, double gamma,
+                               int compute_last_values, int det, void *stream) {
+    const int64_t N = b->N;
+    TMA_HIP(hipSetDevice(env->device));
+    ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
+    const int D = d->obs_dim;
+    // The chunk kernel holds the registers of N / 16 (or N / 32) CUs and nothing of the others; the value pass of chunk c depends only on the
+    // observations chunk c left behind.  So it runs on a SIDE stream behind an event on chunk c, beside the chunk kernel of chunk c + 1 on the
+    // CUs that one leaves idle; the terminal-observation slots are split in two halves used alternately, so that chunk c + 1 does not overwrite
+    // what the bootstrap of chunk c still reads.  The call returns with `stream` waiting for the side stream.  (TMA_CONT_SERIAL=1: one stream.)
+    static const bool serial = getenv("TMA_CONT_SERIAL") != nullptr;
+    const int slots = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
+    const bool overlap = !serial && slots >= 2;
+    const int K = overlap ? slots / 2 : slots;
+    hipStream_t mainS = (hipStream_t)stream, sideS = mainS;
+    if (overlap) {
+        if (!env->side) {
+            TMA_HIP(hipStreamCreateWithFlags(&env->side, hipStreamNonBlocking));
+            TMA_HIP(hipEventCreateWithFlags(&env->ev_chunk, hipEventDisableTiming));
+            TMA_HIP(hipEventCreateWithFlags(&env->ev_side[0], hipEventDisableTiming));
+            TMA_HIP(hipEventCreateWithFlags(&env->ev_side[1], hipEventDisableTiming));
+        }
+        sideS = env->side;
+    }
+    int t = t_begin, half = 0;
+    bool used[2] = {false, false};  // ev_side[h] has been recorded behind a bootstrap that reads half h
+    while (t < t_end) {
+        int left = 0;
+        int rc = tma_env_steps_until_refill(env, &left);
+        if (rc) return rc;
+        int n = left < (t_end - t) ? left : (t_end - t);
+        if (n > K) n = K;  // one terminal-observation slot per step of the chunk
+        float *tobs = b->terminal_obs + (overlap ? (int64_t)half * K * N * D : 0);
+        if (overlap && used[half])  // the half about to be rewritten was read by the bootstrap launched two chunks ago
+            TMA_HIP(hipStreamWaitEvent(mainS, env->ev_side[half], 0));
+        const VnChunk vc = vn ? vn_chunk_args(vn, training) : VnChunk{};
+        rc = dispatch_task(env->task, [&](auto task) {
+            using TT = decltype(task);
+            if (fused_cont_f32) return launch_chunk_wide_cont_f32<TT>(env, params, L, cp, tobs, t, n, rng_seed, rng_step0, det, mainS, vn ? &vc : nullptr);
+            return launch_chunk_wide_cont_pi<TT>(env, params, L, cp, tobs, t, n, rng_seed, rng_step0, det, mainS);
+        });
+        if (rc) return rc;
+        if (vn && vc.stats_out) vn->cur ^= 1;  // the chunk left its statistics in the handle's other buffer
+        if (overlap) {
+            TMA_HIP(hipEventRecord(env->ev_chunk, mainS));
+            TMA_HIP(hipStreamWaitEvent(sideS, env->ev_chunk, 0));
+        }
+        rc = tma_policy_values(params, d, b->obs + (int64_t)t * N * D, (int64_t)n * N, b->values + (int64_t)t * N, sideS);
+        if (rc) return rc;
+        rc = tma_policy_bootstrap(params, d, tobs, b->truncated + (int64_t)t * N, (int64_t)n * N, gamma, b->rewards + (int64_t)t * N, sideS);
+        if (rc) return rc;
+        if (overlap) {
+            TMA_HIP(hipEventRecord(env->ev_side[half], sideS));
+            used[half] = true;
+            half ^= 1;
+        }
+        rc = tma_env_internal_after_steps(env, n, stream);
+        if (rc) return rc;
+        t += n;
+    }
+    for (int h = 0; h < 2; h++)
+        if (overlap && used[h]) TMA_HIP(hipStreamWaitEvent(mainS, env->ev_side[h], 0));
+    if (compute_last_values && t_end == T) {
+        if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
+        return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
+    }
+    return TMA_OK;
+}
+
+// The reference's default MLP(256, 256) in f32 on the Discrete tasks: policy-only fused chunk + ONE batched value launch + ONE batched bootstrap
+// launch per chunk of up to terminal_obs_slots steps.  vn != nullptr: the normalised form of the chunk kernel, as in collect_chunks_cont.
+static int collect_chunks_wide_f32(tma_env *env, tma_vecnorm *vn, int training, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b,
+                                   const PLayout &L, int t_begin, int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, double gamma, int compute_last_values,
+                                   int det, void *stream) {
+    const int64_t N = b->N;
+    TMA_HIP(hipSetDevice(env->device));
+    ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
+    const int K = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
+    const int D = d->obs_dim;
+    int t = t_begin;
+    while (t < t_end) {
+        int left = 0;
+        int rc = tma_env_steps_until_refill(env, &left);
+        if (rc) return rc;
+        int n = left < (t_end - t) ? left : (t_end - t);
+        if (n > K) n = K;  // one terminal-observation slot per step of the chunk
+        const VnChunk vc = vn ? vn_chunk_args(vn, training) : VnChunk{};
+        rc = dispatch_task(env->task, [&](auto task) {
+            using TT = decltype(task);
+            return launch_chunk_wide_f32<TT>(env, params, L, cp, b->terminal_obs, t, n, rng_seed, rng_step0, det, (hipStream_t)stream, vn ? &vc : nullptr);
+        });
+        if (rc) return rc;
+        if (vn && vc.stats_out) vn->cur ^= 1;  // the chunk left its statistics in the handle's other buffer
+        rc = tma_policy_values(params, d, b->obs + (int64_t)t * N * D, (int64_t)n * N, b->values + (int64_t)t * N, stream);
+        if (rc) return rc;
+        rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)t * N, (int64_t)n * N, gamma, b->rewards + (int64_t)t * N, stream);
+        if (rc) return rc;
+        rc = tma_env_internal_after_steps(env, n, stream);
+        if (rc) return rc;
+        t += n;
+    }
+    if (compute_last_values && t_end == T) {
+        if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
+        return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
+    }
     return TMA_OK;
 }
 
@@ -2434,70 +2637,8 @@ extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_
     // Box-action tasks (Crawler / Ant shapes), round 4: policy-only fused chunk + ONE batched value launch + ONE batched bootstrap launch per
     // chunk of up to terminal_obs_slots steps (TMA_CONT_TWO_NET=1: the round-2 chunk with both nets in the step loop)
     static const bool cont_two_net = getenv("TMA_CONT_TWO_NET") != nullptr;
-    if ((fused_wide && fused_cont && !cont_two_net) || fused_cont_f32) {
-        TMA_HIP(hipSetDevice(env->device));
-        ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
-        const int D = d->obs_dim;
-        // The chunk kernel holds the registers of N / 16 (or N / 32) CUs and nothing of the others; the value pass of chunk c depends only on the
-        // observations chunk c left behind.  So it runs on a SIDE stream behind an event on chunk c, beside the chunk kernel of chunk c + 1 on the
-        // CUs that one leaves idle; the terminal-observation slots are split in two halves used alternately, so that chunk c + 1 does not overwrite
-        // what the bootstrap of chunk c still reads.  The call returns with `stream` waiting for the side stream.  (TMA_CONT_SERIAL=1: one stream.)
-        static const bool serial = getenv("TMA_CONT_SERIAL") != nullptr;
-        const int slots = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
-        const bool overlap = !serial && slots >= 2;
-        const int K = overlap ? slots / 2 : slots;
-        hipStream_t mainS = (hipStream_t)stream, sideS = mainS;
-        if (overlap) {
-            if (!env->side) {
-                TMA_HIP(hipStreamCreateWithFlags(&env->side, hipStreamNonBlocking));
-                TMA_HIP(hipEventCreateWithFlags(&env->ev_chunk, hipEventDisableTiming));
-                TMA_HIP(hipEventCreateWithFlags(&env->ev_side[0], hipEventDisableTiming));
-                TMA_HIP(hipEventCreateWithFlags(&env->ev_side[1], hipEventDisableTiming));
-            }
-            sideS = env->side;
-        }
-        int t = t_begin, half = 0;
-        bool used[2] = {false, false};  // ev_side[h] has been recorded behind a bootstrap that reads half h
-        while (t < t_end) {
-            int left = 0;
-            int rc = tma_env_steps_until_refill(env, &left);
-            if (rc) return rc;
-            int n = left < (t_end - t) ? left : (t_end - t);
-            if (n > K) n = K;  // one terminal-observation slot per step of the chunk
-            float *tobs = b->terminal_obs + (overlap ? (int64_t)half * K * N * D : 0);
-            if (overlap && used[half])  // the half about to be rewritten was read by the bootstrap launched two chunks ago
-                TMA_HIP(hipStreamWaitEvent(mainS, env->ev_side[half], 0));
-            rc = dispatch_task(env->task, [&](auto task) {
-                using TT = decltype(task);
-                if (fused_cont_f32) return launch_chunk_wide_cont_f32<TT>(env, params, L, cp, tobs, t, n, rng_seed, rng_step0, det, mainS);
-                return launch_chunk_wide_cont_pi<TT>(env, params, L, cp, tobs, t, n, rng_seed, rng_step0, det, mainS);
-            });
-            if (rc) return rc;
-            if (overlap) {
-                TMA_HIP(hipEventRecord(env->ev_chunk, mainS));
-                TMA_HIP(hipStreamWaitEvent(sideS, env->ev_chunk, 0));
-            }
-            rc = tma_policy_values(params, d, b->obs + (int64_t)t * N * D, (int64_t)n * N, b->values + (int64_t)t * N, sideS);
-            if (rc) return rc;
-            rc = tma_policy_bootstrap(params, d, tobs, b->truncated + (int64_t)t * N, (int64_t)n * N, gamma, b->rewards + (int64_t)t * N, sideS);
-            if (rc) return rc;
-            if (overlap) {
-                TMA_HIP(hipEventRecord(env->ev_side[half], sideS));
-                used[half] = true;
-                half ^= 1;
-            }
-            rc = tma_env_internal_after_steps(env, n, stream);
-            if (rc) return rc;
-            t += n;
-        }
-        for (int h = 0; h < 2; h++)
-            if (overlap && used[h]) TMA_HIP(hipStreamWaitEvent(mainS, env->ev_side[h], 0));
-        if (compute_last_values && t_end == T) {
-            if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-            return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
-        }
-        return TMA_OK;
-    }
+    if ((fused_wide && fused_cont && !cont_two_net) || fused_cont_f32)
+        return collect_chunks_cont(env, nullptr, 0, fused_cont_f32, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
     if (fused_wide) {
         TMA_HIP(hipSetDevice(env->device));
         ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
@@ -2528,37 +2669,8 @@ extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_
     const bool fused_bb = env->task == TMA_TASK_BRICKBREAK && !d->continuous && d->act_dim == tma_task_num_actions(env->task) && env->v.N <= 2048 && rows_forced != 16;
     const bool fused_wide_f32 = !no_wide_fused && !L.bf16 && L.img_pi < 0 && L.H == 256 && env->is_reset && (fused_disc || fused_bb) &&
                                 d->obs_dim == tma_task_obs_dim(env->task);
-    if (fused_wide_f32) {
-        TMA_HIP(hipSetDevice(env->device));
-        ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
-        const int K = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
-        const int D = d->obs_dim;
-        int t = t_begin;
-        while (t < t_end) {
-            int left = 0;
-            int rc = tma_env_steps_until_refill(env, &left);
-            if (rc) return rc;
-            int n = left < (t_end - t) ? left : (t_end - t);
-            if (n > K) n = K;  // one terminal-observation slot per step of the chunk
-            rc = dispatch_task(env->task, [&](auto task) {
-                using TT = decltype(task);
-                return launch_chunk_wide_f32<TT>(env, params, L, cp, b->terminal_obs, t, n, rng_seed, rng_step0, det, (hipStream_t)stream);
-            });
-            if (rc) return rc;
-            rc = tma_policy_values(params, d, b->obs + (int64_t)t * N * D, (int64_t)n * N, b->values + (int64_t)t * N, stream);
-            if (rc) return rc;
-            rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)t * N, (int64_t)n * N, gamma, b->rewards + (int64_t)t * N, stream);
-            if (rc) return rc;
-            rc = tma_env_internal_after_steps(env, n, stream);
-            if (rc) return rc;
-            t += n;
-        }
-        if (compute_last_values && t_end == T) {
-            if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-            return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
-        }
-        return TMA_OK;
-    }
+    if (fused_wide_f32)
+        return collect_chunks_wide_f32(env, nullptr, 0, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
     if (fused) {
         TMA_HIP(hipSetDevice(env->device));
         ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
@@ -2639,6 +2751,105 @@ extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_
 }
 
 extern "C" int tma_debug_last_rollout_waves(void) { return tma::g_roll_waves; }
+
+extern "C" int tma_rollout_norm_plan(int task, const tma_policy_dims *d, int64_t N, int training) {
+    using namespace tma;
+    const int rc = tma_check_policy_dims(d);
+    if (rc) return -rc;
+    if (task < TMA_TASK_BASIC || task > TMA_TASK_ANT) return -fail(TMA_ERR_UNKNOWN_TASK, "tma_rollout_norm_plan: unknown task id %d", task);
+    if (N < 1) return -fail(TMA_ERR_INVALID, "tma_rollout_norm_plan: N = %lld envs", (long long)N);
+    return plan_rollout_norm(task, make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype), *d, N, training != 0);
+}
+
+extern "C" int tma_debug_last_rollout_norm_path(void) { return tma::g_norm_path; }
+
+// tma_rollout_collect with a VecNormalize step behind every env step.  Where plan_rollout_norm fuses, the step runs inside the chunk kernel
+// (one launch per chunk + the batched value and bootstrap launches, over normalised rows); everywhere else it is tma_rollout_collect's per-step
+// composition (its last two branches) with vn_step behind tma_env_step.  Both leave the same bits (tests/test_vecnorm_fused_gpu.py).
+extern "C" int tma_rollout_collect_norm(tma_env *env, tma_vecnorm *vn, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b,
+                                        int t_begin, int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, uint32_t env_offset, double gamma,
+                                        int compute_last_values, int deterministic, int training, void *stream) {
+    using namespace tma;
+    const int det = deterministic ? 1 : 0;
+    if (!env || !vn || !params || !d || !b) return fail(TMA_ERR_INVALID, "tma_rollout_collect_norm: null argument");
+    if (!b->obs || !b->actions || !b->rewards || !b->values || !b->log_probs || !b->terminated || !b->truncated || !b->terminal_obs)
+        return fail(TMA_ERR_INVALID, "tma_rollout_collect_norm: rollout buffers has a null plane");
+    if (t_begin < 0 || t_end > T || t_begin > t_end) return fail(TMA_ERR_INVALID, "bad step range [%d, %d) for T=%d", t_begin, t_end, T);
+    const int64_t N = b->N;
+    if (N != vn->N) return fail(TMA_ERR_INVALID, "rollout buffers are for %lld envs, the normalisation handle has %lld", (long long)N, (long long)vn->N);
+    if (d->obs_dim != vn->D) return fail(TMA_ERR_INVALID, "the policy takes %d observations, the normalisation handle has %d", d->obs_dim, vn->D);
+    if (N != env->v.N) return fail(TMA_ERR_INVALID, "rollout buffers are for %lld envs, the env handle has %lld", (long long)N, (long long)env->v.N);
+    if (compute_last_values && t_end == T && !b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
+    // the fused chunks: where the plan says so, on a reset env handle (TMA_NO_NORM_FUSED / TMA_NO_WIDE_FUSED: A/B switches and test hooks, and
+    // the switches that take tma_rollout_collect off these two kernels take this driver off them as well)
+    static const bool no_fused = getenv("TMA_NO_NORM_FUSED") != nullptr || getenv("TMA_NO_WIDE_FUSED") != nullptr;
+    static const bool no_cont_f32 = getenv("TMA_NO_CONT_F32_FUSED") != nullptr;
+    static const bool rows16 = getenv("TMA_WIDE_F32_ROWS") != nullptr && atoi(getenv("TMA_WIDE_F32_ROWS")) == 16;
+    g_norm_path = TMA_ROLLOUT_NORM_PER_STEP;
+    if (!no_fused && env->is_reset && tma_check_policy_dims(d) == TMA_OK) {
+        const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype);
+        int plan = plan_rollout_norm(env->task, L, *d, N, training != 0);
+        if ((plan == TMA_ROLLOUT_NORM_FUSED_DISC_F32 && rows16) || (plan == TMA_ROLLOUT_NORM_FUSED_CONT_F32 && no_cont_f32)) plan = TMA_ROLLOUT_NORM_PER_STEP;
+        if (plan != TMA_ROLLOUT_NORM_PER_STEP) {
+            const int rc = vn_ensure(vn);
+            if (rc) return rc;
+            g_norm_path = plan;
+            if (plan == TMA_ROLLOUT_NORM_FUSED_CONT_F32)  // (the side-stream overlap of the value / bootstrap launches included: they touch nothing of the handle)
+                return collect_chunks_cont(env, vn, training, true, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
+            return collect_chunks_wide_f32(env, vn, training, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
+        }
+    }
+    const int D = d->obs_dim, A = d->continuous ? d->act_dim : 1;
+    const size_t act_elem = d->continuous ? sizeof(float) : sizeof(int32_t);
+    const int K = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
+    if (K == 1 && !det) {
+        for (int t = t_begin; t < t_end; t++) {
+            const float *obs_t = b->obs + (int64_t)t * N * D;
+            float *obs_next = b->obs + (int64_t)(t + 1) * N * D;
+            void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
+            // policy forward of step t; the timeout bootstrap of step t-1 (terminal_obs and rewards already normalised) rides in the same launch
+            int rc = tma_policy_act_bootstrap(params, d, obs_t, N, rng_seed, rng_step0 + (uint32_t)t, env_offset, act_t, b->values + (int64_t)t * N,
+                                              b->log_probs + (int64_t)t * N, t > 0 ? b->terminal_obs : nullptr,
+                                              t > 0 ? b->truncated + (int64_t)(t - 1) * N : nullptr, gamma,
+                                              t > 0 ? b->rewards + (int64_t)(t - 1) * N : nullptr, stream);
+            if (rc) return rc;
+            rc = tma_env_step(env, act_t, d->continuous ? TMA_ACT_F32 : TMA_ACT_I32, 0, 0, 1, obs_next, b->rewards + (int64_t)t * N,
+                              b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, b->terminal_obs, nullptr, nullptr, stream);
+            if (rc) return rc;
+            rc = vn_step(vn, obs_next, b->rewards + (int64_t)t * N, b->terminal_obs, b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N,
+                         training, stream);
+            if (rc) return rc;
+            if (t == T - 1) {  // last step of the rollout: nothing follows to carry its bootstrap
+                rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)t * N, N, gamma, b->rewards + (int64_t)t * N, stream);
+                if (rc) return rc;
+            }
+        }
+    } else {
+        int w0 = t_begin;
+        for (int t = t_begin; t < t_end; t++) {
+            const float *obs_t = b->obs + (int64_t)t * N * D;
+            float *obs_next = b->obs + (int64_t)(t + 1) * N * D;
+            float *tobs = b->terminal_obs + (int64_t)(t - w0) * N * D;
+            void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
+            int rc = tma_policy_act(params, d, obs_t, N, rng_seed, rng_step0 + (uint32_t)t, env_offset, det, act_t, b->values + (int64_t)t * N,
+                                    b->log_probs + (int64_t)t * N, stream);
+            if (rc) return rc;
+            rc = tma_env_step(env, act_t, d->continuous ? TMA_ACT_F32 : TMA_ACT_I32, 0, 0, 1, obs_next, b->rewards + (int64_t)t * N,
+                              b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, tobs, nullptr, nullptr, stream);
+            if (rc) return rc;
+            rc = vn_step(vn, obs_next, b->rewards + (int64_t)t * N, tobs, b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, training, stream);
+            if (rc) return rc;
+            if (t - w0 + 1 == K || t == t_end - 1) {  // the window's bootstraps: one launch over its rows, every one normalised by its own step
+                rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)w0 * N, (int64_t)(t - w0 + 1) * N, gamma,
+                                          b->rewards + (int64_t)w0 * N, stream);
+                if (rc) return rc;
+                w0 = t + 1;
+            }
+        }
+    }
+    if (compute_last_values && t_end == T) return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
+    return TMA_OK;
+}
 
 #ifdef TMA_ROLL_TICKS
 // diagnostic build only: read (reset != 0: clear) the per-phase cycle sums of the f32 wide rollout kernel

@@ -1,6 +1,7 @@
 // tma_vecnorm.hip -- SB3's VecNormalize on the device (include/tma.h, ABI 217): running float64 mean / variance of the observations and of the
-// per-env discounted returns, normalisation and clipping of observations, rewards and terminal observations, and the rollout driver that puts
-// one such step behind every env step (tma_rollout_collect_norm).
+// per-env discounted returns, normalisation and clipping of observations, rewards and terminal observations.  The device code of a step lives in
+// tma_vecnorm.h, which the normalised fused rollout chunks of tma_rollout.hip compile as well; the rollout driver that puts one such step behind
+// every env step (tma_rollout_collect_norm) is in tma_rollout.hip, beside the chunk kernels it launches.
 //
 // State (per handle, HBM, float64): two statistics buffers of 2 D + 4 doubles {mean[D], var[D], obs count, return mean, return var, return
 // count} used alternately -- a step reads the current one and writes the other, so no workgroup of a two-launch step can read a value another
@@ -10,218 +11,19 @@
 // vn_moments_kernel (G <= 64 workgroups, each the moments of its own rows) + vn_apply_kernel (every workgroup folds the G partials in index order,
 // merges them into the running statistics and normalises its own rows; workgroup 0 stores the new statistics).  Frozen statistics: vn_apply_kernel alone.
 //
-// Sums.  Column d of a workgroup's rows is summed by a segment of R = min(64, pow2ceil(rows)) lanes of one wave: lane l adds rows l, l + R, ...
-// in order, then a __shfl_down tree of width R; two passes (mean, then squared distances from it).  The returns have one row per thread: wave
-// tree, four wave partials through LDS, added in wave order.  Workgroup partials (rows, mean, M2) are combined by Chan's formula in index order.
-// Nothing depends on anything but (N, D): no atomics, the same bits on every run.
-// (The column READS of the moments pass have stride D across the lanes of a segment -- uncoalesced at R = 64; the rows were just written by the
+// Sums: tma_vecnorm.h.  (The column READS of the moments pass have stride D across the lanes of a segment -- uncoalesced at R = 64; the rows were just written by the
 // env step and sit in L2.  Staging a block of rows through LDS with row-contiguous loads is the follow-up if the moments pass ever shows up in a
 // profile; the STORES of the normalising pass are whole rows by consecutive threads.)
 //
 // Arithmetic.  -ffp-contract=off -fno-fast-math (csrc/Makefile): the merge and the normalisation are the literal IEEE float64 operation
 // sequences of include/tma.h -- subtract, sqrt, divide; no reciprocal square root.
-#include "tma_internal.h"
+#include "tma_vecnorm.h"
 
 #include <cmath>
 #include <new>
 #include <vector>
 
-struct tma_vecnorm {
-    int D = 0, device = -1;
-    int64_t N = 0;
-    int norm_obs = 1, norm_reward = 1;
-    double clip_obs = 10.0, clip_reward = 10.0, gamma = 0.99, epsilon = 1e-8;
-    // device memory, allocated on first use
-    bool allocated = false;
-    double *stats[2] = {nullptr, nullptr};  // [2 D + 4] each
-    int cur = 0;
-    double *returns = nullptr;   // [N]
-    double *partials = nullptr;  // [G][2 D + 2]: column means, column M2s, return mean, return M2 of workgroup g's rows
-    float *raw_obs = nullptr, *raw_rew = nullptr;
-    int G = 1;                   // workgroups of vn_moments_kernel
-    int64_t rows_blk = 0;        // rows of each (the last one: what is left)
-};
-
 namespace tma {
-
-constexpr int VN_THREADS = 256, VN_MAX_PARTIALS = 64, VN_MAX_APPLY_BLOCKS = 1024;
-
-struct VnArgs {
-    float *obs, *rewards, *term_obs;
-    const uint8_t *terminated, *truncated;
-    const double *st_in;
-    double *st_out;  // nullptr: frozen statistics
-    double *returns, *partials;
-    float *raw_obs, *raw_rew;
-    int64_t N, rows_blk, rows_apply;
-    int D, G, seg;
-    int upd_obs, upd_ret, norm_obs, norm_reward;
-    double clip_obs, clip_reward, gamma, eps;
-};
-
-// sum over a segment of R consecutive lanes (R a power of two <= 64), left in every lane of the segment
-__device__ __forceinline__ double seg_sum(double v, int R) {
-    for (int o = R >> 1; o > 0; o >>= 1) v += __shfl_down(v, o, R);
-    return __shfl(v, 0, R);
-}
-
-// sum over the workgroup's 256 threads: wave tree, four partials through LDS, added in wave order; left in every thread
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();  // (red may still be read from the previous sum)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// column means and M2s (sums of squared distances from the mean) of rows [row0, row0 + rows)
-__device__ void block_obs_moments(const VnArgs &a, int64_t row0, int64_t rows, double *out_mean, double *out_m2) {
-    const int R = a.seg, S = VN_THREADS / R, seg = threadIdx.x / R, lr = threadIdx.x % R, D = a.D;
-    const float *x = a.obs + row0 * D;
-    for (int d0 = 0; d0 < D; d0 += S) {
-        const int d = d0 + seg;
-        const bool ok = d < D;
-        double s = 0.0;
-        if (ok)
-            for (int64_t r = lr; r < rows; r += R) s += (double)x[r * D + d];
-        s = seg_sum(s, R);
-        const double m = s / (double)rows;
-        double q = 0.0;
-        if (ok)
-            for (int64_t r = lr; r < rows; r += R) {
-                const double c = (double)x[r * D + d] - m;
-                q += c * c;
-            }
-        q = seg_sum(q, R);
-        if (ok && lr == 0) {
-            out_mean[d] = m;
-            out_m2[d] = q;
-        }
-    }
-}
-
-// returns = returns * gamma + rewards over rows [row0, row0 + rows), stored; their mean and M2 into out2
-__device__ void block_ret_moments(const VnArgs &a, int64_t row0, int64_t rows, double *out2, double *red) {
-    double s = 0.0;
-    for (int64_t r = threadIdx.x; r < rows; r += VN_THREADS) {
-        const double v = a.returns[row0 + r] * a.gamma + (double)a.rewards[row0 + r];
-        a.returns[row0 + r] = v;
-        s += v;
-    }
-    const double m = block_sum(s, red) / (double)rows;
-    double q = 0.0;
-    for (int64_t r = threadIdx.x; r < rows; r += VN_THREADS) {  // (each thread re-reads what it stored itself)
-        const double c = a.returns[row0 + r] - m;
-        q += c * c;
-    }
-    q = block_sum(q, red);
-    if (threadIdx.x == 0) {
-        out2[0] = m;
-        out2[1] = q;
-    }
-}
-
-__device__ __forceinline__ int64_t partial_rows(const VnArgs &a, int g) {
-    const int64_t left = a.N - (int64_t)g * a.rows_blk;
-    return left < a.rows_blk ? left : a.rows_blk;
-}
-
-// Chan's combination of the G partials of one quantity in index order: batch mean and population variance over the N rows
-__device__ __forceinline__ void fold_partials(const VnArgs &a, const double *part, int stride, int off_mean, int off_m2, double &bm, double &bv) {
-    double n = (double)partial_rows(a, 0), mean = part[off_mean], m2 = part[off_m2];
-    for (int g = 1; g < a.G; g++) {
-        const double nb = (double)partial_rows(a, g), mb = part[(int64_t)g * stride + off_mean], qb = part[(int64_t)g * stride + off_m2];
-        const double delta = mb - mean, tot = n + nb;
-        mean = mean + delta * nb / tot;
-        m2 = m2 + qb + delta * delta * n * nb / tot;
-        n = tot;
-    }
-    bm = mean;
-    bv = m2 / (double)a.N;
-}
-
-// RunningMeanStd.update_from_moments: the operation sequence of include/tma.h
-__device__ __forceinline__ void rms_merge(double mean, double var, double count, double bm, double bv, double n, double &new_mean, double &new_var) {
-    const double delta = bm - mean;
-    const double tot = count + n;
-    new_mean = mean + delta * n / tot;
-    const double m_a = var * count;
-    const double m_b = bv * n;
-    const double M2 = m_a + m_b + delta * delta * count * n / tot;
-    new_var = M2 / tot;
-}
-
-// New statistics from the partials (or the current ones where nothing updates): column mean and sqrt(var + eps) into LDS, the return's
-// sqrt(var + eps) into s_ret[0]; `store`: this workgroup also writes the statistics buffer of the next step.
-__device__ void fold_and_merge(const VnArgs &a, const double *part, double *s_mean, double *s_sd, double *s_ret, bool store) {
-    const int D = a.D, stride = 2 * D + 2;
-    const double *in = a.st_in;
-    const double n = (double)a.N;
-    for (int d = threadIdx.x; d < D; d += VN_THREADS) {
-        double nm = in[d], nv = in[D + d];
-        if (a.upd_obs) {
-            double bm, bv;
-            fold_partials(a, part, stride, d, D + d, bm, bv);
-            rms_merge(in[d], in[D + d], in[2 * D], bm, bv, n, nm, nv);
-        }
-        s_mean[d] = nm;
-        s_sd[d] = sqrt(nv + a.eps);
-        if (store && a.st_out) {
-            a.st_out[d] = nm;
-            a.st_out[D + d] = nv;
-        }
-    }
-    if (threadIdx.x == 0) {
-        double rm = in[2 * D + 1], rv = in[2 * D + 2];
-        if (a.upd_ret) {
-            double bm, bv;
-            fold_partials(a, part, stride, 2 * D, 2 * D + 1, bm, bv);
-            rms_merge(in[2 * D + 1], in[2 * D + 2], in[2 * D + 3], bm, bv, n, rm, rv);
-        }
-        s_ret[0] = sqrt(rv + a.eps);
-        if (store && a.st_out) {
-            a.st_out[2 * D] = a.upd_obs ? in[2 * D] + n : in[2 * D];
-            a.st_out[2 * D + 1] = rm;
-            a.st_out[2 * D + 2] = rv;
-            a.st_out[2 * D + 3] = a.upd_ret ? in[2 * D + 3] + n : in[2 * D + 3];
-        }
-    }
-}
-
-__device__ __forceinline__ float norm_value(float x, double mean, double sd, double clip) {
-    const double y = ((double)x - mean) / sd;
-    return (float)fmin(fmax(y, -clip), clip);
-}
-
-// steps 2, 4, 5, 6 on rows [row0, row0 + rows): whole rows of D floats are read and stored by consecutive threads
-__device__ void apply_rows(const VnArgs &a, int64_t row0, int64_t rows, const double *s_mean, const double *s_sd, double ret_sd) {
-    const int D = a.D;
-    const int64_t base = row0 * D, count = rows * D;
-    for (int64_t e = threadIdx.x; e < count; e += VN_THREADS) {
-        const int d = (int)(e % D);
-        const float x = a.obs[base + e];
-        if (a.raw_obs) a.raw_obs[base + e] = x;
-        if (a.norm_obs) a.obs[base + e] = norm_value(x, s_mean[d], s_sd[d], a.clip_obs);
-    }
-    if (a.term_obs && a.norm_obs && a.terminated) {
-        for (int64_t e = threadIdx.x; e < count; e += VN_THREADS) {
-            const int64_t row = row0 + e / D;
-            if (a.terminated[row] | a.truncated[row]) {
-                const int d = (int)(e % D);
-                a.term_obs[base + e] = norm_value(a.term_obs[base + e], s_mean[d], s_sd[d], a.clip_obs);
-            }
-        }
-    }
-    if (a.rewards) {
-        for (int64_t r = threadIdx.x; r < rows; r += VN_THREADS) {
-            const int64_t i = row0 + r;
-            const float x = a.rewards[i];
-            if (a.raw_rew) a.raw_rew[i] = x;
-            if (a.norm_reward) a.rewards[i] = (float)fmin(fmax((double)x / ret_sd, -a.clip_reward), a.clip_reward);
-            if (a.terminated[i] | a.truncated[i]) a.returns[i] = 0.0;
-        }
-    }
-}
 
 // LDS: s_mean[D], s_sd[D], part[2 D + 2] (one-launch kernel), s_ret[2], red[4]
 __global__ __launch_bounds__(VN_THREADS) void vn_step_one_kernel(VnArgs a) {
@@ -280,13 +82,7 @@ __global__ __launch_bounds__(VN_THREADS) void vn_map_kernel(const float *__restr
     }
 }
 
-static int pow2ceil(int64_t n) {
-    int p = 1;
-    while (p < n && p < 64) p <<= 1;
-    return p;
-}
-
-static int vn_ensure(tma_vecnorm *h) {
+int vn_ensure(tma_vecnorm *h) {
     if (h->device >= 0) TMA_HIP(hipSetDevice(h->device));
     if (h->allocated) return TMA_OK;
     const int D = h->D;
@@ -319,8 +115,8 @@ static int vn_ensure(tma_vecnorm *h) {
 }
 
 // one VecNormalize step (rewards == nullptr: the reset form, observations only) on validated arguments
-static int vn_step(tma_vecnorm *h, float *obs, float *rewards, float *terminal_obs, const uint8_t *terminated, const uint8_t *truncated, int training,
-                   void *stream) {
+int vn_step(tma_vecnorm *h, float *obs, float *rewards, float *terminal_obs, const uint8_t *terminated, const uint8_t *truncated, int training,
+            void *stream) {
     int rc = vn_ensure(h);
     if (rc) return rc;
     const int D = h->D;
@@ -338,12 +134,12 @@ static int vn_step(tma_vecnorm *h, float *obs, float *rewards, float *terminal_o
     a.clip_obs = h->clip_obs, a.clip_reward = h->clip_reward, a.gamma = h->gamma, a.eps = h->epsilon;
     hipStream_t s = (hipStream_t)stream;
     if (updates && N <= TMA_VECNORM_ONE_LAUNCH_MAX) {
-        a.G = 1, a.rows_blk = N, a.rows_apply = N, a.seg = pow2ceil(N);
+        a.G = 1, a.rows_blk = N, a.rows_apply = N, a.seg = vn_pow2ceil(N);
         const size_t lds = sizeof(double) * (4 * (size_t)D + 8);
         vn_step_one_kernel<<<dim3(1), dim3(VN_THREADS), lds, s>>>(a);
         TMA_LAUNCH_CHECK();
     } else {
-        a.G = h->G, a.rows_blk = h->rows_blk, a.seg = pow2ceil(h->rows_blk);
+        a.G = h->G, a.rows_blk = h->rows_blk, a.seg = vn_pow2ceil(h->rows_blk);
         if (updates) {
             vn_moments_kernel<<<dim3(a.G), dim3(VN_THREADS), 0, s>>>(a);
             TMA_LAUNCH_CHECK();
@@ -506,71 +302,5 @@ extern "C" int tma_vecnorm_get_original(tma_vecnorm *h, float *obs_out, float *r
     if (rc) return rc;
     if (obs_out) TMA_HIP(hipMemcpyAsync(obs_out, h->raw_obs, sizeof(float) * (size_t)h->N * h->D, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (rewards_out) TMA_HIP(hipMemcpyAsync(rewards_out, h->raw_rew, sizeof(float) * (size_t)h->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return TMA_OK;
-}
-
-// tma_rollout_collect's per-step composition (csrc/tma_rollout.hip, its last two branches) with a VecNormalize step behind every env step
-extern "C" int tma_rollout_collect_norm(tma_env *env, tma_vecnorm *vn, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b,
-                                        int t_begin, int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, uint32_t env_offset, double gamma,
-                                        int compute_last_values, int deterministic, int training, void *stream) {
-    const int det = deterministic ? 1 : 0;
-    if (!env || !vn || !params || !d || !b) return fail(TMA_ERR_INVALID, "tma_rollout_collect_norm: null argument");
-    if (!b->obs || !b->actions || !b->rewards || !b->values || !b->log_probs || !b->terminated || !b->truncated || !b->terminal_obs)
-        return fail(TMA_ERR_INVALID, "tma_rollout_collect_norm: rollout buffers has a null plane");
-    if (t_begin < 0 || t_end > T || t_begin > t_end) return fail(TMA_ERR_INVALID, "bad step range [%d, %d) for T=%d", t_begin, t_end, T);
-    const int64_t N = b->N;
-    if (N != vn->N) return fail(TMA_ERR_INVALID, "rollout buffers are for %lld envs, the normalisation handle has %lld", (long long)N, (long long)vn->N);
-    if (d->obs_dim != vn->D) return fail(TMA_ERR_INVALID, "the policy takes %d observations, the normalisation handle has %d", d->obs_dim, vn->D);
-    if (N != env->v.N) return fail(TMA_ERR_INVALID, "rollout buffers are for %lld envs, the env handle has %lld", (long long)N, (long long)env->v.N);
-    if (compute_last_values && t_end == T && !b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-    const int D = d->obs_dim, A = d->continuous ? d->act_dim : 1;
-    const size_t act_elem = d->continuous ? sizeof(float) : sizeof(int32_t);
-    const int K = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
-    if (K == 1 && !det) {
-        for (int t = t_begin; t < t_end; t++) {
-            const float *obs_t = b->obs + (int64_t)t * N * D;
-            float *obs_next = b->obs + (int64_t)(t + 1) * N * D;
-            void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
-            // policy forward of step t; the timeout bootstrap of step t-1 (terminal_obs and rewards already normalised) rides in the same launch
-            int rc = tma_policy_act_bootstrap(params, d, obs_t, N, rng_seed, rng_step0 + (uint32_t)t, env_offset, act_t, b->values + (int64_t)t * N,
-                                              b->log_probs + (int64_t)t * N, t > 0 ? b->terminal_obs : nullptr,
-                                              t > 0 ? b->truncated + (int64_t)(t - 1) * N : nullptr, gamma,
-                                              t > 0 ? b->rewards + (int64_t)(t - 1) * N : nullptr, stream);
-            if (rc) return rc;
-            rc = tma_env_step(env, act_t, d->continuous ? TMA_ACT_F32 : TMA_ACT_I32, 0, 0, 1, obs_next, b->rewards + (int64_t)t * N,
-                              b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, b->terminal_obs, nullptr, nullptr, stream);
-            if (rc) return rc;
-            rc = vn_step(vn, obs_next, b->rewards + (int64_t)t * N, b->terminal_obs, b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N,
-                         training, stream);
-            if (rc) return rc;
-            if (t == T - 1) {  // last step of the rollout: nothing follows to carry its bootstrap
-                rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)t * N, N, gamma, b->rewards + (int64_t)t * N, stream);
-                if (rc) return rc;
-            }
-        }
-    } else {
-        int w0 = t_begin;
-        for (int t = t_begin; t < t_end; t++) {
-            const float *obs_t = b->obs + (int64_t)t * N * D;
-            float *obs_next = b->obs + (int64_t)(t + 1) * N * D;
-            float *tobs = b->terminal_obs + (int64_t)(t - w0) * N * D;
-            void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
-            int rc = tma_policy_act(params, d, obs_t, N, rng_seed, rng_step0 + (uint32_t)t, env_offset, det, act_t, b->values + (int64_t)t * N,
-                                    b->log_probs + (int64_t)t * N, stream);
-            if (rc) return rc;
-            rc = tma_env_step(env, act_t, d->continuous ? TMA_ACT_F32 : TMA_ACT_I32, 0, 0, 1, obs_next, b->rewards + (int64_t)t * N,
-                              b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, tobs, nullptr, nullptr, stream);
-            if (rc) return rc;
-            rc = vn_step(vn, obs_next, b->rewards + (int64_t)t * N, tobs, b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, training, stream);
-            if (rc) return rc;
-            if (t - w0 + 1 == K || t == t_end - 1) {  // the window's bootstraps: one launch over its rows, every one normalised by its own step
-                rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)w0 * N, (int64_t)(t - w0 + 1) * N, gamma,
-                                          b->rewards + (int64_t)w0 * N, stream);
-                if (rc) return rc;
-                w0 = t + 1;
-            }
-        }
-    }
-    if (compute_last_values && t_end == T) return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
     return TMA_OK;
 }

@@ -34,3 +34,5 @@ run "TMA_H64_RUNTIME_A=1" "tests/test_ppo_gpu.py tests/test_policy_dispatch_gpu.
 run "TMA_ROLL4=1" "tests/test_ppo_gpu.py tests/test_rollout_oracle_gpu.py tests/test_env_gpu.py tests/test_bench_gpu.py"   # the headline rollout on four waves per tile (round 6) instead of eight
 # round 9
 run "TMA_NO_PREP_FOLD=1" "tests/test_ppo_gpu.py tests/test_h64_head_width_gpu.py tests/test_policy_dispatch_gpu.py tests/test_bench_gpu.py"   # H = 64 fast path: one prepare launch per epoch (tests/test_prep_fold_gpu.py sets the switch itself)
+# VecNormalize: the per-step composition under the wrapper at every shape (tests/test_vecnorm_fused_gpu.py sets the switch itself, per arm)
+run "TMA_NO_NORM_FUSED=1" "tests/test_vecnorm_gpu.py"
