@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 219
+#define TMA_VERSION 220
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -149,7 +149,7 @@ int tma_explained_variance(const float *values, const float *returns, int64_t n,
  *      training.py:377-390) and model.learn() drives at training.py:166-170.  Third-party semantics: SURVEY.md App. C. ---- */
 typedef struct {
     int obs_dim;    /* D */
-    int hidden;     /* H: two tanh layers of width H for both the policy and the value net (multiple of 64) */
+    int hidden;     /* H: two hidden layers of width H (tanh, or `activation` below) for both the policy and the value net (multiple of 64) */
     int act_dim;    /* Discrete(n): n (2..16); Box: action dimension (1..32) */
     int continuous; /* 0: Categorical head; 1: DiagGaussian head with a state-independent log_std */
     int mfma_dtype; /* 0: f32 MFMA everywhere (parity mode, every hidden width); 1: bf16 MFMA operands with f32 master
@@ -162,7 +162,14 @@ typedef struct {
     int device;     /* HIP device the parameter / rollout / workspace buffers live on: every tma_policy_* / tma_ppo_* call makes it
                        the calling thread's current device first (callers may be worker threads: backend/main.py:152
                        asyncio.to_thread).  -1: keep whatever device is current on the calling thread. */
+    int activation; /* ABI 220: the hidden layers' non-linearity (SB3 policy_kwargs activation_fn).  TMA_ACT_TANH (0): every kernel family;
+                       TMA_ACT_RELU (1): h = z > 0 ? z : 0, derivative h > 0 ? 1 : 0 (torch's rule: 0 at z == 0), on the generic
+                       one-wave-per-tile kernels only (forward, minibatch gradient, phase (a) of the VJP) -- the tuned families, the
+                       persistent epoch kernels and the fused rollout chunks stay tanh-only and a ReLU policy never reaches them.
+                       mfma_dtype must be 0 with it.  Parameter count, offsets and workspace sizes do not depend on it. */
 } tma_policy_dims;
+#define TMA_ACT_TANH 0
+#define TMA_ACT_RELU 1
 
 /* parameter buffer = n_total floats: [0, n_trainable) trainable, [in][out] layout, order
  * pi.W1 pi.b1 pi.W2 pi.b2 pi.W3(action_net) pi.b3 vf.W1 vf.b1 vf.W2 vf.b2 vf.W3(value_net) vf.b3 [log_std];

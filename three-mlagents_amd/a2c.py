@@ -216,12 +216,13 @@ class A2C(PPO):
                                              self.learning_rate, RMSPROP_ALPHA, self.rms_prop_eps)
 
     @classmethod
-    def _from_data(cls, data: dict, num, hidden: int, mfma: str):
+    def _from_data(cls, data: dict, num, hidden: int, mfma: str, extra_policy_kwargs: dict | None = None):
         return cls(data.get("policy_class", "MlpPolicy") if isinstance(data.get("policy_class"), str) else "MlpPolicy", None,
                    learning_rate=num("learning_rate", 7e-4), n_steps=num("n_steps", 5), gamma=num("gamma", 0.99), gae_lambda=num("gae_lambda", 1.0),
                    ent_coef=num("ent_coef", 0.0), vf_coef=num("vf_coef", 0.5), max_grad_norm=num("max_grad_norm", 0.5),
                    rms_prop_eps=num("rms_prop_eps", 1e-5), use_rms_prop=num("use_rms_prop", True), normalize_advantage=num("normalize_advantage", False),
-                   policy_kwargs={"net_arch": [hidden, hidden], "mfma_dtype": mfma}, seed=num("seed", 0), _init_setup_model=False)
+                   policy_kwargs={"net_arch": [hidden, hidden], "mfma_dtype": mfma, **(extra_policy_kwargs or {})}, seed=num("seed", 0),
+                   _init_setup_model=False)
 
     def _restore_extra(self, tma_extra: dict) -> None:
         self._rollout_counter = int(tma_extra.get("rollout_counter", 0))

@@ -585,7 +585,7 @@ using namespace tma;
 
 bool tma_epoch_h64p_eligible(const PLayout &L, int64_t batch_size, int64_t total) {
     const bool off = getenv("TMA_NO_PERSIST") != nullptr;  // (read per call: tests switch paths inside one process)
-    if (off || L.img_pi < 0 || batch_size != 256 || total < 2 * batch_size) return false;
+    if (off || L.act != ACT_TANH || L.img_pi < 0 || batch_size != 256 || total < 2 * batch_size) return false;
     const int64_t n_mb = (total + batch_size - 1) / batch_size;
     return n_mb <= 65535 && HP_TABLE + n_mb * 8 <= Workspace::slab_bytes(L);
 }

@@ -48,7 +48,24 @@ struct PLayout {
                          // evaluation and every derived f32 image are those of the exact-f32 mode
     int sp_pi, sp_vf;    // float offsets of the three-plane fragment-major weight images of the two nets (3 x BfNet.size bf16 each); -1 otherwise
     int total;
+    int act;             // tma_policy_dims.activation (0: tanh, 1: ReLU).  No offset above depends on it: a ReLU layout keeps (and the optimizer kernels
+                         // maintain) every derived image, but only the generic kernels -- the ones templated on it -- ever run (tma_policy_plan.h)
 };
+constexpr int ACT_TANH = 0, ACT_RELU = 1;
+// the hidden non-linearity of the generic kernels and its derivative from the STORED activation h (tanh: 1 - h^2; ReLU: h > 0, torch's rule, 0 at z == 0)
+template <int ACT>
+__device__ __forceinline__ float act_fwd(float z) {
+    if constexpr (ACT == ACT_RELU) return z > 0.0f ? z : 0.0f;
+    else return tma_tanh(z);
+}
+template <int ACT>
+__device__ __forceinline__ float act_bwd(float dh, float h) {
+    if constexpr (ACT == ACT_RELU) return h > 0.0f ? dh : 0.0f;
+    else {
+        const float d1 = 1.0f - h * h;
+        return dh * d1;
+    }
+}
 
 // ---- bf16 weight images of ONE net (offsets in bf16 elements from the image base).  Every image is "fragment-major": the
 // eight bf16 one lane feeds to v_mfma_f32_16x16x32_bf16 as its B operand for (output tile, k-step) are contiguous, and the
@@ -88,9 +105,9 @@ constexpr int IMG_B3 = IMG_B2 + 64;         // [16]
 constexpr int IMG_FLOATS = IMG_B3 + 16 + 16;  // padded to a multiple of 4 floats (11440)
 constexpr int IMG_FWD_FLOATS = IMG_W3B;       // forward-only kernels stage [0, IMG_W3B) + the biases
 
-__host__ __device__ inline PLayout make_layout(int D, int H, int A, int cont, int bf16 = 0) {
+__host__ __device__ inline PLayout make_layout(int D, int H, int A, int cont, int bf16 = 0, int act = 0) {
     PLayout L;
-    L.D = D, L.H = H, L.A = A, L.cont = cont;
+    L.D = D, L.H = H, L.A = A, L.cont = cont, L.act = act;
     int o = 0;
     L.pW1t = o, o += D * H;
     L.pb1 = o, o += H;
@@ -279,8 +296,9 @@ __device__ __forceinline__ f32x4 frag_f32(const float *img, int idx, int lane) {
     return *reinterpret_cast<gvec_ptr>(base + (uint32_t)lane * 16u);
 }
 
-// out[16][N] = tanh(in[16][K] . Wt[K][N] + b)   (N % 64 == 0; in/out are wave-private LDS tiles)
-__device__ __forceinline__ void dense_tanh(const float *in, int ldi, int K, const float *__restrict__ Wt, const float *__restrict__ b, int N,
+// out[16][N] = act(in[16][K] . Wt[K][N] + b)   (N % 64 == 0; in/out are wave-private LDS tiles)
+template <int ACT>
+__device__ __forceinline__ void dense_act(const float *in, int ldi, int K, const float *__restrict__ Wt, const float *__restrict__ b, int N,
                                            float *out, int ldo, int lane) {
     const int r16 = lane & 15, g = lane >> 4;
     const int KS = (K + 3) >> 2;
@@ -305,7 +323,7 @@ __device__ __forceinline__ void dense_tanh(const float *in, int ldi, int K, cons
 #pragma unroll
         for (int j = 0; j < 4; j++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) out[(g * 4 + r) * ldo + n0 + 16 * j + r16] = tma_tanh(acc[j][r]);
+            for (int r = 0; r < 4; r++) out[(g * 4 + r) * ldo + n0 + 16 * j + r16] = act_fwd<ACT>(acc[j][r]);
     }
 }
 
@@ -332,7 +350,8 @@ __device__ __forceinline__ void dense_head(const float *in, int ldi, int K, cons
     }
 }
 
-// dzout[16][K] = (dzin[16][N] . W[N][K]) * (1 - hprev^2)      (K % 64 == 0)
+// dzout[16][K] = (dzin[16][N] . W[N][K]) * act'(hprev)      (K % 64 == 0; tanh: 1 - hprev^2)
+template <int ACT>
 __device__ __forceinline__ void dense_bwd_input(const float *dzin, int ldz, int N, const float *__restrict__ W, int K, const float *hprev,
                                                 int ldh, float *dzout, int ldo, int lane) {
     const int r16 = lane & 15, g = lane >> 4;
@@ -358,8 +377,7 @@ __device__ __forceinline__ void dense_bwd_input(const float *dzin, int ldz, int 
             for (int r = 0; r < 4; r++) {
                 const int row = g * 4 + r, col = k0 + 16 * j + r16;
                 const float h = hprev[row * ldh + col];
-                const float d1 = 1.0f - h * h;
-                dzout[row * ldo + col] = acc[j][r] * d1;
+                dzout[row * ldo + col] = act_bwd<ACT>(acc[j][r], h);
             }
     }
 }

@@ -137,7 +137,7 @@ __device__ __forceinline__ void store_head_tile(const f32x4 (&acc)[NJ], int A, f
     for (int e = lane; e < valid * A; e += 64) dst[e] = stage[e];
 }
 
-template <bool CONT, int MODE>
+template <bool CONT, int MODE, int ACT>
 __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict__ params, PLayout L, const float *__restrict__ obs, int64_t n,
                                                          uint32_t rng_seed, uint32_t rng_step, uint32_t env_offset, int deterministic,
                                                          void *__restrict__ actions_out, float *__restrict__ values_out,
@@ -163,8 +163,8 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict
         if (lane < 16) row_off[lane] = (row0 + lane < n) ? row0 + lane : -1;
         load_obs_tile(obs, row_off, D, X, ldx, lane);
         const Net V = vf_net(params, L);
-        dense_tanh(X, ldx, D, V.W1t, V.b1, H, h1, ld, lane);
-        dense_tanh(h1, ld, H, V.W2t, V.b2, H, h2, ld, lane);
+        dense_act<ACT>(X, ldx, D, V.W1t, V.b1, H, h1, ld, lane);
+        dense_act<ACT>(h1, ld, H, V.W2t, V.b2, H, h2, ld, lane);
         f32x4 vacc[1];
         dense_head<1>(h2, ld, H, V.W3t, V.b3, 1, vacc, lane);
         if constexpr (MODE == 1) {
@@ -201,8 +201,8 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(const float *__restrict
                 if (EVAL && logp_out == nullptr && entropy_out == nullptr) continue;
             }
             const Net P = pi_net(params, L);
-            dense_tanh(X, ldx, D, P.W1t, P.b1, H, h1, ld, lane);
-            dense_tanh(h1, ld, H, P.W2t, P.b2, H, h2, ld, lane);
+            dense_act<ACT>(X, ldx, D, P.W1t, P.b1, H, h1, ld, lane);
+            dense_act<ACT>(h1, ld, H, P.W2t, P.b2, H, h2, ld, lane);
             if constexpr (HEAD) {  // (h1 is free once layer 2 has read it: the head tile's scratch)
                 f32x4 acc[CONT ? 2 : 1];
                 dense_head<CONT ? 2 : 1>(h2, ld, H, P.W3t, P.b3, A, acc, lane);
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(64) void adv_epoch_sums_kernel(double *partials, in
 // ------------------------------------------------------------------------------------------
 // Even blocks carry the POLICY net, odd blocks the VALUE net (they share nothing).  The input-gradient tiles overwrite the
 // activations they derive from (dz2 over h2, dz1 over h1), so a wave needs X + 2 activation tiles of LDS and four waves fit.
-template <bool CONT, bool IS_PI>
+template <bool CONT, bool IS_PI, int ACT>
 __device__ __forceinline__ void grad_generic_body(const float *__restrict__ params, const PLayout &L, const Rollout &rb, const Minibatch &mb,
                                                   const HParams &hp, const float *__restrict__ ws_adv, float *__restrict__ grad,
                                                   double *__restrict__ stat_slot, float *smem, int n_blocks_net, int block_net) {
@@ -410,8 +410,8 @@ __device__ __forceinline__ void grad_generic_body(const float *__restrict__ para
             row_off[lane] = off;
         }
         load_obs_tile(rb.obs, row_off, D, X, ldx, lane);
-        dense_tanh(X, ldx, D, Q.W1t, Q.b1, H, h1, ld, lane);
-        dense_tanh(h1, ld, H, Q.W2t, Q.b2, H, h2, ld, lane);
+        dense_act<ACT>(X, ldx, D, Q.W1t, Q.b1, H, h1, ld, lane);
+        dense_act<ACT>(h1, ld, H, Q.W2t, Q.b2, H, h2, ld, lane);
         if constexpr (!IS_PI) {
             f32x4 vacc[1];
             dense_head<1>(h2, ld, H, Q.W3t, Q.b3, 1, vacc, lane);
@@ -516,9 +516,9 @@ __device__ __forceinline__ void grad_generic_body(const float *__restrict__ para
             }
         }
         dense_bwd_weight(h2, ld, H, dz3, ld3, NOUT, gW3, gb3, lane);
-        dense_bwd_input(dz3, ld3, NOUT, Q.W3, H, h2, ld, dzA, ld, lane);
+        dense_bwd_input<ACT>(dz3, ld3, NOUT, Q.W3, H, h2, ld, dzA, ld, lane);
         dense_bwd_weight(h1, ld, H, dzA, ld, H, gW2, gb2, lane);
-        dense_bwd_input(dzA, ld, H, Q.W2, H, h1, ld, dzB, ld, lane);
+        dense_bwd_input<ACT>(dzA, ld, H, Q.W2, H, h1, ld, dzB, ld, lane);
         dense_bwd_weight(X, ldx, D, dzB, ld, H, gW1, gb1, lane);
     }
     double st[5] = {st_a, st_ent, st_kl, st_clip, st_n};
@@ -538,14 +538,14 @@ __device__ __forceinline__ void grad_generic_body(const float *__restrict__ para
     }
 }
 
-template <bool CONT>
+template <bool CONT, int ACT>
 __global__ __launch_bounds__(256) void ppo_grad_kernel(const float *__restrict__ params, PLayout L, Rollout rb, Minibatch mb, HParams hp,
                                                        const float *__restrict__ ws_adv, float *__restrict__ grad, double *__restrict__ stat_slots) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int pair = blockIdx.x >> 1, n_pairs = gridDim.x >> 1;
     double *slot = stat_slots + (int64_t)pair * 8;
-    if ((blockIdx.x & 1) == 0) grad_generic_body<CONT, true>(params, L, rb, mb, hp, ws_adv, grad, slot, smem, n_pairs, pair);
-    else grad_generic_body<CONT, false>(params, L, rb, mb, hp, ws_adv, grad, slot, smem, n_pairs, pair);
+    if ((blockIdx.x & 1) == 0) grad_generic_body<CONT, true, ACT>(params, L, rb, mb, hp, ws_adv, grad, slot, smem, n_pairs, pair);
+    else grad_generic_body<CONT, false, ACT>(params, L, rb, mb, hp, ws_adv, grad, slot, smem, n_pairs, pair);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1815,7 +1815,7 @@ __global__ __launch_bounds__(1024) void opt_small_kernel(float *__restrict__ par
     }
 }
 
-static inline PLayout layout_of(const tma_policy_dims *d) { return make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype); }
+static inline PLayout layout_of(const tma_policy_dims *d) { return make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation); }
 
 // everything derived from the trainable region: [out][in] copies, H == 64 LDS images, bf16 fragment images
 static int launch_sync(float *params, const PLayout &L, hipStream_t s) {
@@ -1866,6 +1866,10 @@ static int check_dims(const tma_policy_dims *d) {
     if (d->mfma_dtype == 2 && (d->hidden != 256 || d->continuous || d->obs_dim > 32))
         return fail(TMA_ERR_INVALID, "mfma_dtype 2 (three-term bf16 split of the f32 update) covers Discrete heads, hidden 256 and up to 32 observations (got hidden %d, obs %d%s)",
                     d->hidden, d->obs_dim, d->continuous ? ", Box actions" : "");
+    if (d->activation != TMA_ACT_TANH && d->activation != TMA_ACT_RELU)
+        return fail(TMA_ERR_INVALID, "activation must be 0 (tanh) or 1 (ReLU), got %d", d->activation);
+    if (d->activation != TMA_ACT_TANH && d->mfma_dtype != 0)
+        return fail(TMA_ERR_INVALID, "activation %d (ReLU) needs mfma_dtype 0 (f32): the bf16 and bf16 x 3 kernels have no ReLU form (got mfma_dtype %d)", d->activation, d->mfma_dtype);
     if (d->mfma_dtype == 1) {
         if (d->hidden != 128 && d->hidden != 192 && d->hidden != 256)
             return fail(TMA_ERR_INVALID, "the bf16 MFMA path covers hidden widths 128 / 192 / 256 (got %d)", d->hidden);
@@ -2389,7 +2393,8 @@ static int launch_fwd(const float *params, const tma_policy_dims *d, const float
         });
     case FwdFamily::Generic: break;
     }
-    return p.cont ? launch(policy_fwd_kernel<true, MODE>, p.lds > LDS_OPT_IN) : launch(policy_fwd_kernel<false, MODE>, p.lds > LDS_OPT_IN);
+    if (L.act == ACT_RELU) return p.cont ? launch(policy_fwd_kernel<true, MODE, ACT_RELU>, p.lds > LDS_OPT_IN) : launch(policy_fwd_kernel<false, MODE, ACT_RELU>, p.lds > LDS_OPT_IN);
+    return p.cont ? launch(policy_fwd_kernel<true, MODE, ACT_TANH>, p.lds > LDS_OPT_IN) : launch(policy_fwd_kernel<false, MODE, ACT_TANH>, p.lds > LDS_OPT_IN);
 }
 
 // The dispatchers' environment switches, each read where the parent dispatchers read it: DispatchSwitches says which once per process and which on
@@ -2742,7 +2747,8 @@ static int minibatch_grad_impl(const float *params, const tma_policy_dims *d, co
             TMA_LAUNCH_CHECK();
             return TMA_OK;
         };
-        lrc = p.cont ? launch(ppo_grad_kernel<true>) : launch(ppo_grad_kernel<false>);
+        if (L.act == ACT_RELU) lrc = p.cont ? launch(ppo_grad_kernel<true, ACT_RELU>) : launch(ppo_grad_kernel<false, ACT_RELU>);
+        else lrc = p.cont ? launch(ppo_grad_kernel<true, ACT_TANH>) : launch(ppo_grad_kernel<false, ACT_TANH>);
     } break;
     }
     if (lrc || p.reduce != GradReduce::Slab) return lrc;
@@ -2848,7 +2854,7 @@ static thread_local int g_prep_folded = 0, g_prep_standalone = 0;
 static bool h64_fold_eligible(const PLayout &L, int64_t total, int64_t batch_size) {
     const bool no_fold = getenv("TMA_NO_ADAM_FOLD") != nullptr;  // test / measurement switch: one optimizer launch per minibatch (read per call)
     const int64_t tail = total % batch_size;
-    return L.img_pi >= 0 && total <= OFFS_CAP && batch_size >= 256 && (tail == 0 || tail >= 256) && total > batch_size && !no_fold;
+    return L.act == ACT_TANH && L.img_pi >= 0 && total <= OFFS_CAP && batch_size >= 256 && (tail == 0 || tail >= 256) && total > batch_size && !no_fold;
 }
 
 // `n_epochs` epochs of the H = 64 fast path (h64_fold_eligible).
@@ -3032,7 +3038,7 @@ int tma_ppo_train_epoch_dp(float *params, const tma_policy_dims *d, const tma_ro
     // grad_sumsq64 launch -- was built first and measured 1.2 us per minibatch SLOWER than the launch it removed: DESIGN.md section 10.)
     const int64_t tail = total % batch_size;
     static const bool no_dp_fold = getenv("TMA_DP_NO_FOLD") != nullptr || getenv("TMA_NO_ADAM_FOLD") != nullptr;  // A/B switch: the round-4 chain
-    if (L.img_pi >= 0 && L.P <= 64 * 256 && prepared_batch == batch_size && batch_size >= 256 && (tail == 0 || tail >= 256) && total > batch_size && !no_dp_fold) {
+    if (L.act == ACT_TANH && L.img_pi >= 0 && L.P <= 64 * 256 && prepared_batch == batch_size && batch_size >= 256 && (tail == 0 || tail >= 256) && total > batch_size && !no_dp_fold) {
         hipStream_t s = job.s;
         FoldChain chain(job, opt);
         double *sqp = job.ws.sq_partials();

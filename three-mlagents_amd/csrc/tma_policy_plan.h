@@ -45,8 +45,12 @@ inline int grad_wide_smem_bytes(const PLayout &L, int nw = 4) {
     return (32 * (ldx + 2 * ld + 34 + 4) + 2 * 32 + 64 + nw * 2 * 2 * 256 + 2 * L.H + 32 + 2 * 32 + 32 * 32) * 4;  // (last terms: row_off_next, the Box heads' action tile)
 }
 inline bool wide_width(const PLayout &L) { return L.H == 128 || L.H == 192 || L.H == 256; }
+// Only the generic one-wave-per-tile kernels (policy_fwd_kernel, ppo_grad_kernel) are templated on the activation: every tuned family below -- the
+// H = 64 LDS-image kernels, the column-parallel ones, and what hangs on them (persistent epochs, the prologue optimizer fold, half groups, two
+// passes, small7, the split) -- is tanh code, so each of their conditions asks this first
+inline bool tanh_layout(const PLayout &L) { return L.act == ACT_TANH; }
 // shapes the f32 column-parallel gradient kernel can take (from how many samples on it does: plan_grad, plan_opt)
-inline bool grad_wide_f32_shape(const PLayout &L) { return !L.bf16 && wide_width(L) && grad_wide_smem_bytes(L) <= LDS_LIMIT; }
+inline bool grad_wide_f32_shape(const PLayout &L) { return tanh_layout(L) && !L.bf16 && wide_width(L) && grad_wide_smem_bytes(L) <= LDS_LIMIT; }
 // the dW2 deferral buffer overlays the upper slabs of the workspace's slab area (Workspace::defer_w2): it must fit there
 inline bool w2_defer_fits(const PLayout &L) { return Workspace::defer_w2_fits(L); }
 // slab_reduce_kernel / wide_small_reduce_kernel leave one sum-of-squares partial per 64 parameters where the workspace has slots for them
@@ -67,20 +71,20 @@ inline FwdPlan plan_fwd(const PLayout &L, int64_t n, int mode) {
     FwdPlan p{FwdFamily::Refused, L.cont != 0, L.H / 64, 0, 256, 0, TMA_DISPATCH_NONE};
     const int64_t tiles = ceil_div(n, 16), groups = ceil_div(n, 32);
     const int nets = (mode == 0 || mode == 3 || mode == 4) ? 2 : 1;
-    if (L.img_pi >= 0) {  // both nets' weight images in LDS
+    if (tanh_layout(L) && L.img_pi >= 0) {  // both nets' weight images in LDS
         p.family = FwdFamily::H64, p.id = TMA_DISPATCH_FWD_H64;
         const int wpb = tiles >= 512 ? 4 : (tiles >= 64 ? 2 : 1);  // waves per block
         p.grid = ceil_div(tiles, wpb) < H64_FWD_BLOCK_CAP ? ceil_div(tiles, wpb) : H64_FWD_BLOCK_CAP;
         p.block = 64 * wpb, p.lds = nets * FWD_IMG * 4;
         if (mode == 4) p.lds += wpb * H64_HEAD_STAGE * 4;  // a wave's [16][A] head tile on its way to a coalesced store
-    } else if (L.bf16 || (wide_width(L) && fwd_wide_smem_bytes(L) <= LDS_LIMIT)) {  // column-parallel: row groups of 32, one block per group and net
+    } else if (tanh_layout(L) && (L.bf16 || (wide_width(L) && fwd_wide_smem_bytes(L) <= LDS_LIMIT))) {  // column-parallel: row groups of 32, one block per group and net
         p.family = L.bf16 ? FwdFamily::WideBF16 : FwdFamily::WideF32;
         p.id = (L.bf16 ? (p.cont ? TMA_DISPATCH_FWD_BF16_NTW2_BOX : TMA_DISPATCH_FWD_BF16_NTW2_DISCRETE)
                        : (p.cont ? TMA_DISPATCH_FWD_F32_NTW2_BOX : TMA_DISPATCH_FWD_F32_NTW2_DISCRETE)) + (p.ntw - 2) |
                (groups > WIDE_FWD_GROUP_CAP ? TMA_DISPATCH_GRID_CAPPED : 0);
         p.grid = nets * (groups < WIDE_FWD_GROUP_CAP ? groups : WIDE_FWD_GROUP_CAP);
         p.lds = L.bf16 ? fwd_wide_bf_smem_bytes(L.D, L.H) : fwd_wide_smem_bytes(L);
-    } else {  // one wave per 16-row tile
+    } else {  // one wave per 16-row tile: every width of a non-tanh layout, too
         int wpb = tiles >= 1024 ? 4 : 1;  // small batches: one wave per block so every CU gets work
         while (wpb > 1 && fwd_smem_bytes(L, wpb) > LDS_OPT_IN) wpb >>= 1;
         p.lds = fwd_smem_bytes(L, wpb);
@@ -170,7 +174,7 @@ inline GradPlan plan_grad(const PLayout &L, bool cont, int64_t count, bool prepa
     GradPlan p{};
     p.cont = cont, p.normalize = normalize_advantage && count > 1, p.ntw = L.H / 64;
     const int64_t tiles = ceil_div(count, 16);
-    const bool h64 = L.img_pi >= 0 && tiles >= 16;  // >= 256 samples: persistent LDS-image kernel; smaller batches: generic kernel
+    const bool h64 = tanh_layout(L) && L.img_pi >= 0 && tiles >= 16;  // >= 256 samples: persistent LDS-image kernel; smaller batches: generic kernel
     const bool wide_f32 = grad_wide_f32_shape(L) && (tiles >= 8 || sw.force_wide);
     // offsets cache: written by the advantage pass, read by every gradient kernel (saves the permutation arithmetic per sample);
     // a prepared epoch (tma_ppo_epoch_prepare) left offsets and partials in the workspace
@@ -241,7 +245,7 @@ inline OptPlan plan_opt(const PLayout &L, bool local, int64_t last_count, const 
     const bool sq = sq_partials_fit(L);
     // "did the gradient end in a slab reduction", as this entry point has always asked it: from 256 samples (H = 64) and 128 samples (f32
     // column-parallel) on.  plan_grad reduces from 241 (16 tiles) and 113 (8 tiles) on; in between the global step runs, which is right for any gradient.
-    const bool red_h64 = L.img_pi >= 0 && last_count >= 256;
+    const bool red_h64 = tanh_layout(L) && L.img_pi >= 0 && last_count >= 256;  // (a non-tanh layout: the generic gradient kernel at every count, no reduction)
     const bool red_wide = L.bf16 || (grad_wide_f32_shape(L) && last_count >= 128 && !sw.force_wide_now);
     OptPlan p{OptKernels::Adam, false, ceil_div(L.P, 256), 256, TMA_DISPATCH_OPT_ADAM};
     if (local && (red_h64 || red_wide) && sq && last_count >= 1) {

@@ -8,7 +8,7 @@
 namespace tma {
 
 // floats per packed sample record {obs padded to a multiple of 4 | log_prob, advantage, action bits, return}; 0: shape without them
-static inline int rec_floats(const PLayout &L) { return (L.img_pi >= 0 && L.D <= 8) ? ((L.D + 3) & ~3) + 4 : 0; }
+static inline int rec_floats(const PLayout &L) { return (L.act == ACT_TANH && L.img_pi >= 0 && L.D <= 8) ? ((L.D + 3) & ~3) + 4 : 0; }
 
 // What the bf16 column-parallel gradient launches for a shape (plan_grad_bf in tma_policy_plan.h decides, tma_launch_grad_wide_bf launches):
 // ppo_grad_wide_bf_kernel<cont, H / 64, mt, kt1c, ks1c, PASS, waves>

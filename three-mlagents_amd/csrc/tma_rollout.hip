@@ -2399,7 +2399,7 @@ static thread_local int g_norm_path = TMA_ROLLOUT_NORM_PER_STEP;
 // are then one workgroup's work.  Frozen statistics: rows are independent, any number of tiles up to the kernel's own cap.
 constexpr int64_t NORM_FUSED_TRAIN_MAX = 8, NORM_FUSED_DISC_MAX = 2048, NORM_FUSED_CONT_MAX = 4096;
 inline int plan_rollout_norm(int task, const PLayout &L, const tma_policy_dims &d, int64_t N, bool training) {
-    if (L.bf16 || L.img_pi >= 0 || L.H != 256 || d.obs_dim != tma_task_obs_dim(task)) return TMA_ROLLOUT_NORM_PER_STEP;
+    if (L.act != ACT_TANH || L.bf16 || L.img_pi >= 0 || L.H != 256 || d.obs_dim != tma_task_obs_dim(task)) return TMA_ROLLOUT_NORM_PER_STEP;
     const bool box_task = task == TMA_TASK_CRAWLER || task == TMA_TASK_ANT;
     const bool task_fused = dispatch_task(task, [](auto t) { return decltype(t)::FUSED_ROLLOUT ? 1 : 0; }) == 1;
     const bool disc = !d.continuous && !box_task && d.act_dim == tma_task_num_actions(task) && ((task_fused && d.obs_dim <= 32) || task == TMA_TASK_BRICKBREAK);
@@ -2618,8 +2618,9 @@ extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_
     if (t_begin < 0 || t_end > T || t_begin > t_end) return fail(TMA_ERR_INVALID, "bad step range [%d, %d) for T=%d", t_begin, t_end, T);
     const int64_t N = b->N;
     if (N != env->v.N) return fail(TMA_ERR_INVALID, "rollout buffers are for %lld envs, the env handle has %lld", (long long)N, (long long)env->v.N);
-    const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype);
-    const bool fused = L.img_pi >= 0 && env->is_reset &&
+    const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
+    // (every fused chunk kernel below is tanh code: a policy with another activation runs the per-step composition at the end)
+    const bool fused = L.act == ACT_TANH && L.img_pi >= 0 && env->is_reset &&
                        (env->task == TMA_TASK_GRIDWORLD || env->task == TMA_TASK_PUSH || env->task == TMA_TASK_BALL3D || env->task == TMA_TASK_WALLJUMP ||
                         env->task == TMA_TASK_BICYCLE || env->task == TMA_TASK_GLIDER) &&
                        d->obs_dim == tma_task_obs_dim(env->task) && d->act_dim == tma_task_num_actions(env->task);
@@ -2629,10 +2630,10 @@ extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_
     const bool fused_disc = task_fused && !d->continuous && env->task != TMA_TASK_CRAWLER && env->task != TMA_TASK_ANT && d->act_dim == tma_task_num_actions(env->task) && d->obs_dim <= 32;
     // ... and on the Crawler shape (Box actions, 172 observations): layer-1 fragments streamed per step, env state in LDS
     const bool fused_cont = d->continuous && (env->task == TMA_TASK_CRAWLER || env->task == TMA_TASK_ANT) && d->act_dim == tma_task_act_dim(env->task);
-    const bool fused_wide = !no_wide_fused && L.bf16 && L.H == 256 && env->is_reset && d->obs_dim == tma_task_obs_dim(env->task) && (fused_disc || fused_cont);
+    const bool fused_wide = !no_wide_fused && L.act == ACT_TANH && L.bf16 && L.H == 256 && env->is_reset && d->obs_dim == tma_task_obs_dim(env->task) && (fused_disc || fused_cont);
     // ... and in f32 (the reference's dtype), round 6: tiles of eight envs, up to 4096 envs (two block rounds; beyond that the per-step composition)
     static const bool no_cont_f32 = getenv("TMA_NO_CONT_F32_FUSED") != nullptr;  // A/B switch
-    const bool fused_cont_f32 = !no_wide_fused && !no_cont_f32 && !L.bf16 && L.img_pi < 0 && L.H == 256 && env->is_reset && fused_cont &&
+    const bool fused_cont_f32 = !no_wide_fused && !no_cont_f32 && L.act == ACT_TANH && !L.bf16 && L.img_pi < 0 && L.H == 256 && env->is_reset && fused_cont &&
                                 d->obs_dim == tma_task_obs_dim(env->task) && env->v.N <= 4096;
     // Box-action tasks (Crawler / Ant shapes), round 4: policy-only fused chunk + ONE batched value launch + ONE batched bootstrap launch per
     // chunk of up to terminal_obs_slots steps (TMA_CONT_TWO_NET=1: the round-2 chunk with both nets in the step loop)
@@ -2667,7 +2668,7 @@ extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_
     // batched value launch + ONE batched bootstrap launch per chunk of up to terminal_obs_slots steps
     static const int rows_forced = getenv("TMA_WIDE_F32_ROWS") ? atoi(getenv("TMA_WIDE_F32_ROWS")) : 0;
     const bool fused_bb = env->task == TMA_TASK_BRICKBREAK && !d->continuous && d->act_dim == tma_task_num_actions(env->task) && env->v.N <= 2048 && rows_forced != 16;
-    const bool fused_wide_f32 = !no_wide_fused && !L.bf16 && L.img_pi < 0 && L.H == 256 && env->is_reset && (fused_disc || fused_bb) &&
+    const bool fused_wide_f32 = !no_wide_fused && L.act == ACT_TANH && !L.bf16 && L.img_pi < 0 && L.H == 256 && env->is_reset && (fused_disc || fused_bb) &&
                                 d->obs_dim == tma_task_obs_dim(env->task);
     if (fused_wide_f32)
         return collect_chunks_wide_f32(env, nullptr, 0, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
@@ -2758,7 +2759,7 @@ extern "C" int tma_rollout_norm_plan(int task, const tma_policy_dims *d, int64_t
     if (rc) return -rc;
     if (task < TMA_TASK_BASIC || task > TMA_TASK_ANT) return -fail(TMA_ERR_UNKNOWN_TASK, "tma_rollout_norm_plan: unknown task id %d", task);
     if (N < 1) return -fail(TMA_ERR_INVALID, "tma_rollout_norm_plan: N = %lld envs", (long long)N);
-    return plan_rollout_norm(task, make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype), *d, N, training != 0);
+    return plan_rollout_norm(task, make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation), *d, N, training != 0);
 }
 
 extern "C" int tma_debug_last_rollout_norm_path(void) { return tma::g_norm_path; }
@@ -2787,7 +2788,7 @@ extern "C" int tma_rollout_collect_norm(tma_env *env, tma_vecnorm *vn, const flo
     static const bool rows16 = getenv("TMA_WIDE_F32_ROWS") != nullptr && atoi(getenv("TMA_WIDE_F32_ROWS")) == 16;
     g_norm_path = TMA_ROLLOUT_NORM_PER_STEP;
     if (!no_fused && env->is_reset && tma_check_policy_dims(d) == TMA_OK) {
-        const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype);
+        const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
         int plan = plan_rollout_norm(env->task, L, *d, N, training != 0);
         if ((plan == TMA_ROLLOUT_NORM_FUSED_DISC_F32 && rows16) || (plan == TMA_ROLLOUT_NORM_FUSED_CONT_F32 && no_cont_f32)) plan = TMA_ROLLOUT_NORM_PER_STEP;
         if (plan != TMA_ROLLOUT_NORM_PER_STEP) {

@@ -5,7 +5,7 @@
 // the gradient kernels of tma_policy.hip / tma_h64.hip / tma_bf16.hip, which this file leaves alone.
 //
 // DETERMINISTIC by construction: no float atomics.  The rows are walked in chunks; a chunk takes two launches.
-//   (a) vjp_tile_kernel: one wave per 16-row tile and net -- forward (load_obs_tile, dense_tanh, dense_head), the head cotangent dz3 from the
+//   (a) vjp_tile_kernel: one wave per 16-row tile and net -- forward (load_obs_tile, dense_act, dense_head), the head cotangent dz3 from the
 //       three cotangent arrays, the input gradients dz2, dz1 (dense_bwd_input); h1, h2, dz1, dz2, dz3 (and the Box head's per-row log_std
 //       terms) of the chunk go to the workspace, every row of every tile written (rows behind the batch carry dz = 0).
 //   (b) vjp_reduce_kernel: the weight gradients as output-stationary GEMMs over the chunk's rows -- X^T dz1, h1^T dz2, h2^T dz3 -- and the bias
@@ -59,7 +59,7 @@ __device__ __forceinline__ void store_tile(const float *t, int ld, int cols, flo
 // ---- (a) one wave per tile: forward, head cotangent, input gradients -> planes
 // HEAD (tma_policy_head_backward, ABI 218): the head cotangent is the caller's -- `g_logp` carries g_head f32[n][A] (or null), `actions` and
 // `g_entropy` are not read, the head's forward is not needed, and the Box head's log_std plane is zeros (the head does not depend on log_std)
-template <bool CONT, bool IS_PI, bool HEAD = false>
+template <bool CONT, bool IS_PI, bool HEAD, int ACT>
 __device__ __forceinline__ void vjp_tile_body(const float *__restrict__ params, const PLayout &L, const float *__restrict__ obs,
                                               const void *__restrict__ actions, int64_t row_base, int rows, const float *__restrict__ g_values,
                                               const float *__restrict__ g_logp, const float *__restrict__ g_entropy, const VjpPlanes &ws, float *smem) {
@@ -86,9 +86,9 @@ __device__ __forceinline__ void vjp_tile_body(const float *__restrict__ params, 
             meta[lane * 4 + 3] = (valid && g_values != nullptr) ? g_values[grow] : 0.0f;
         }
         load_obs_tile(obs, row_off, D, X, ldx, lane);
-        dense_tanh(X, ldx, D, Q.W1t, Q.b1, H, h1, ld, lane);
+        dense_act<ACT>(X, ldx, D, Q.W1t, Q.b1, H, h1, ld, lane);
         store_tile(h1, ld, H, ws.h1[net], row0, lane);
-        dense_tanh(h1, ld, H, Q.W2t, Q.b2, H, h2, ld, lane);
+        dense_act<ACT>(h1, ld, H, Q.W2t, Q.b2, H, h2, ld, lane);
         store_tile(h2, ld, H, ws.h2[net], row0, lane);
         if constexpr (!IS_PI) {
 #pragma unroll
@@ -159,22 +159,22 @@ __device__ __forceinline__ void vjp_tile_body(const float *__restrict__ params, 
             }
         }
         store_tile(dz3, ld3, VJP_LD3, ws.dz3[net], row0, lane);
-        dense_bwd_input(dz3, ld3, NOUT, Q.W3, H, h2, ld, dzA, ld, lane);
+        dense_bwd_input<ACT>(dz3, ld3, NOUT, Q.W3, H, h2, ld, dzA, ld, lane);
         store_tile(dzA, ld, H, ws.dz2[net], row0, lane);
-        dense_bwd_input(dzA, ld, H, Q.W2, H, h1, ld, dzB, ld, lane);
+        dense_bwd_input<ACT>(dzA, ld, H, Q.W2, H, h1, ld, dzB, ld, lane);
         store_tile(dzB, ld, H, ws.dz1[net], row0, lane);
     }
 }
 
 // grid (tile blocks, 2): blockIdx.y = 0 the policy net, 1 the value net
-template <bool CONT, bool HEAD = false>
+template <bool CONT, bool HEAD, int ACT>
 __global__ __launch_bounds__(256) void vjp_tile_kernel(const float *__restrict__ params, PLayout L, const float *__restrict__ obs,
                                                        const void *__restrict__ actions, int64_t row_base, int rows,
                                                        const float *__restrict__ g_values, const float *__restrict__ g_logp,
                                                        const float *__restrict__ g_entropy, VjpPlanes ws) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (blockIdx.y == 0) vjp_tile_body<CONT, true, HEAD>(params, L, obs, actions, row_base, rows, g_values, g_logp, g_entropy, ws, smem);
-    else vjp_tile_body<CONT, false, HEAD>(params, L, obs, actions, row_base, rows, g_values, g_logp, g_entropy, ws, smem);
+    if (blockIdx.y == 0) vjp_tile_body<CONT, true, HEAD, ACT>(params, L, obs, actions, row_base, rows, g_values, g_logp, g_entropy, ws, smem);
+    else vjp_tile_body<CONT, false, HEAD, ACT>(params, L, obs, actions, row_base, rows, g_values, g_logp, g_entropy, ws, smem);
 }
 
 // ---- (b) output-stationary weight-gradient GEMMs.  Jobs of one net, in block order:
@@ -309,7 +309,7 @@ int64_t tma_policy_vjp_workspace_bytes(const tma_policy_dims *d, int64_t n) {
         fail(TMA_ERR_INVALID, "tma_policy_vjp_workspace_bytes: n must be >= 1");
         return 0;
     }
-    const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype);
+    const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
     const int64_t chunk = vjp_default_chunk(L), n16 = (n + 15) & ~(int64_t)15;
     return (n16 < chunk ? n16 : chunk) * vjp_row_floats(L) * 4;
 }
@@ -325,7 +325,7 @@ static int vjp_run(const char *who, bool head, const float *params, const tma_po
     if (!workspace || workspace_bytes < need)
         return fail(TMA_ERR_INVALID, "%s: workspace of %lld bytes, tma_policy_vjp_workspace_bytes reports %lld", who, (long long)(workspace ? workspace_bytes : 0),
                     (long long)need);
-    const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype);
+    const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
     int64_t chunk = 0;
     if ((rc = vjp_chunk_rows(L, &chunk))) return rc;
     const int lds1 = vjp_tile_lds_floats(L) * 4;
@@ -365,8 +365,11 @@ static int vjp_run(const char *who, bool head, const float *params, const tma_po
             TMA_LAUNCH_CHECK();
             return TMA_OK;
         };
-        if (head) rc = L.cont ? launch_a(vjp_tile_kernel<true, true>) : launch_a(vjp_tile_kernel<false, true>);
-        else rc = L.cont ? launch_a(vjp_tile_kernel<true>) : launch_a(vjp_tile_kernel<false>);
+        if (L.act == ACT_RELU) {
+            if (head) rc = L.cont ? launch_a(vjp_tile_kernel<true, true, ACT_RELU>) : launch_a(vjp_tile_kernel<false, true, ACT_RELU>);
+            else rc = L.cont ? launch_a(vjp_tile_kernel<true, false, ACT_RELU>) : launch_a(vjp_tile_kernel<false, false, ACT_RELU>);
+        } else if (head) rc = L.cont ? launch_a(vjp_tile_kernel<true, true, ACT_TANH>) : launch_a(vjp_tile_kernel<false, true, ACT_TANH>);
+        else rc = L.cont ? launch_a(vjp_tile_kernel<true, false, ACT_TANH>) : launch_a(vjp_tile_kernel<false, false, ACT_TANH>);
         if (rc) return rc;
         const float *obs_chunk = obs + base * L.D;
         if (wide) vjp_reduce_kernel<4, 8><<<dim3((unsigned)n_blocks), dim3(512), 0, s>>>(L, ws, obs_chunk, rows, grad_out, base > 0 ? 1 : 0);

@@ -82,6 +82,46 @@ def orthogonal_init(obs_dim: int, hidden: int, act_dim: int, continuous: bool, s
     return sd
 
 
+def default_linear_init(obs_dim: int, hidden: int, act_dim: int, continuous: bool, seed: int) -> dict[str, torch.Tensor]:
+    """policy_kwargs ortho_init=False: what torch.nn.Linear leaves when SB3 does not re-initialise -- weights AND biases uniform within
+    +-1/sqrt(fan_in) (kaiming_uniform_ with a = sqrt(5) is that bound) -- drawn from the seeded CPU generator in the order of SB3_KEYS.
+    Deterministic per seed; SB3's distribution, not its draws."""
+    gen = torch.Generator().manual_seed(int(seed))
+    D, H, A = int(obs_dim), int(hidden), int(act_dim)
+    sd = {}
+    for i, (o, fan_in) in enumerate(((H, D), (H, H), (A, H), (H, D), (H, H), (1, H))):
+        bound = 1.0 / math.sqrt(fan_in)
+        sd[SB3_KEYS[2 * i]] = (torch.rand(o, fan_in, generator=gen) * 2.0 - 1.0) * bound
+        sd[SB3_KEYS[2 * i + 1]] = (torch.rand(o, generator=gen) * 2.0 - 1.0) * bound
+    if continuous:
+        sd["log_std"] = torch.zeros(A)
+    return sd
+
+
+def initial_state_dict(obs_dim: int, hidden: int, act_dim: int, continuous: bool, seed: int, log_std_init: float = 0.0,
+                       ortho_init: bool = True) -> dict[str, torch.Tensor]:
+    """The parameters a new policy starts from (CPU): SB3's orthogonal initialisation or torch's default one, log_std filled with log_std_init."""
+    sd = (orthogonal_init if ortho_init else default_linear_init)(obs_dim, hidden, act_dim, continuous, seed)
+    if continuous:
+        sd["log_std"] = torch.full((int(act_dim),), float(log_std_init))
+    return sd
+
+
+MFMA_DTYPES = {"f32": 0, "bf16": 1, "bf16x3": 2}
+
+
+def policy_dims(obs_dim: int, hidden: int, act_dim: int, continuous: bool, mfma_dtype: str = "f32", device_index: int = -1, activation="tanh"):
+    """tma_policy_dims of a policy, or ValueError for what the constructor refuses (no device needed)."""
+    from .sb3_format import ACTIVATIONS, parse_activation
+
+    if mfma_dtype not in MFMA_DTYPES:  # bf16x3 (round 5): the f32 update on the bf16 MFMA, every operand as three bf16 terms (csrc/tma_split3.h)
+        raise ValueError(f"mfma_dtype must be 'f32', 'bf16' or 'bf16x3', got {mfma_dtype!r}")
+    act = parse_activation(activation)
+    if act != "tanh" and mfma_dtype != "f32":
+        raise ValueError(f"activation_fn {act!r} needs mfma_dtype='f32': the bf16 and bf16x3 kernels are tanh-only (got mfma_dtype={mfma_dtype!r})")
+    return _lib.PolicyDims(int(obs_dim), int(hidden), int(act_dim), 1 if continuous else 0, MFMA_DTYPES[mfma_dtype], int(device_index), ACTIVATIONS[act][0])
+
+
 class _EvaluateActions(torch.autograd.Function):
     """evaluate_actions as a node of a torch autograd graph (HipActorCriticPolicy.parameters() opts in): the forward is the forward-only call,
     the backward ONE tma_policy_evaluate_actions_backward launch sequence with whichever cotangents autograd supplies."""
@@ -123,15 +163,20 @@ class _Head(torch.autograd.Function):
 class HipActorCriticPolicy:
     """Parameters of SB3's ActorCriticPolicy(MlpPolicy) in one flat HBM buffer + the forward kernels."""
 
-    def __init__(self, obs_dim: int, act_dim: int, continuous: bool, hidden: int, device, seed: int = 0, mfma_dtype: str = "f32"):
-        if mfma_dtype not in ("f32", "bf16", "bf16x3"):  # bf16x3 (round 5): the f32 update on the bf16 MFMA, every operand as three bf16 terms (csrc/tma_split3.h)
-            raise ValueError(f"mfma_dtype must be 'f32', 'bf16' or 'bf16x3', got {mfma_dtype!r}")
-        self.mfma_dtype = mfma_dtype
+    def __init__(self, obs_dim: int, act_dim: int, continuous: bool, hidden: int, device, seed: int = 0, mfma_dtype: str = "f32",
+                 activation="tanh", log_std_init: float = 0.0, ortho_init: bool = True):
+        from .sb3_format import parse_activation
+
+        # activation: SB3's policy_kwargs activation_fn -- torch.nn.Tanh / torch.nn.ReLU or "tanh" / "relu".  ReLU runs the generic kernel
+        # families only (csrc/tma_policy_plan.h: tanh_layout) and needs mfma_dtype "f32"
+        dims = policy_dims(obs_dim, hidden, act_dim, continuous, mfma_dtype, -1, activation)  # (the refusals, before anything touches the device)
+        self.mfma_dtype, self.activation = mfma_dtype, parse_activation(activation)
+        self.log_std_init, self.ortho_init = float(log_std_init), bool(ortho_init)
         self.obs_dim, self.act_dim, self.continuous, self.hidden = int(obs_dim), int(act_dim), bool(continuous), int(hidden)
         self.device = torch.device(device)
         # dims.device: every tma_policy_* / tma_ppo_* call makes it the calling thread's HIP device (learn() may run in a worker thread)
-        self.dims = _lib.PolicyDims(int(obs_dim), int(hidden), int(act_dim), 1 if continuous else 0, {"f32": 0, "bf16": 1, "bf16x3": 2}[mfma_dtype],
-                                    self.device.index if self.device.index is not None else -1)
+        dims.device = self.device.index if self.device.index is not None else -1
+        self.dims = dims
         nt, ntot = C.c_int64(0), C.c_int64(0)
         _lib.check(_lib.lib().tma_policy_param_count(C.byref(self.dims), C.byref(nt), C.byref(ntot)))
         self.n_trainable, self.n_total = nt.value, ntot.value
@@ -146,7 +191,7 @@ class HipActorCriticPolicy:
 
     # -- init / (de)serialisation in SB3's state_dict naming -------------------------------
     def _orthogonal_init(self, seed: int) -> dict[str, torch.Tensor]:
-        return orthogonal_init(self.obs_dim, self.hidden, self.act_dim, self.continuous, seed)
+        return initial_state_dict(self.obs_dim, self.hidden, self.act_dim, self.continuous, seed, self.log_std_init, self.ortho_init)
 
     def _segments(self):
         D, H, A = self.obs_dim, self.hidden, self.act_dim
@@ -444,8 +489,10 @@ class PPO:
         cont = eng.num_actions == 0
         A = eng.act_dim if cont else eng.num_actions
         # policy_kwargs["mfma_dtype"] = "bf16" (engine extension; BASELINE.json configs[2]): bf16 MFMA operands for 128..256-wide nets
-        self.policy = HipActorCriticPolicy(eng.obs_dim, A, cont, H, self.device, seed=self.seed,
-                                           mfma_dtype=self.policy_kwargs.get("mfma_dtype", "f32"))
+        # policy_kwargs["activation_fn"] (torch.nn.Tanh / torch.nn.ReLU), ["log_std_init"], ["ortho_init"]: SB3's own members of that name
+        pk = self.policy_kwargs
+        self.policy = HipActorCriticPolicy(eng.obs_dim, A, cont, H, self.device, seed=self.seed, mfma_dtype=pk.get("mfma_dtype", "f32"),
+                                           activation=pk.get("activation_fn"), log_std_init=pk.get("log_std_init", 0.0), ortho_init=pk.get("ortho_init", True))
         if not getattr(self, "_keep_env_state", False):  # (load(..., force_reset=False): the env vector goes on where it stands)
             env.seed(self.seed)  # BaseAlgorithm.set_random_seed -> env.seed(seed): env i gets seed + i
         T, N, D, dev = self.n_steps, self.n_envs, eng.obs_dim, self.device
@@ -1187,7 +1234,7 @@ class PPO:
         obs_space = getattr(env, "observation_space", None) or Box(-np.inf, np.inf, (pol.obs_dim,), np.float32)
         act_space = getattr(env, "action_space", None) or (Box(-1.0, 1.0, (pol.act_dim,), np.float32) if pol.continuous else Discrete(pol.act_dim))
         data = {
-            "policy_kwargs": {"net_arch": [pol.hidden, pol.hidden]}, "num_timesteps": self.num_timesteps, "_total_timesteps": getattr(self, "_total_timesteps", 0),
+            "policy_kwargs": sb3_format.policy_kwargs_data(pol.hidden, pol.activation, pol.log_std_init, pol.ortho_init), "num_timesteps": self.num_timesteps, "_total_timesteps": getattr(self, "_total_timesteps", 0),
             "_num_timesteps_at_start": 0, "seed": self.seed, "action_noise": None, "start_time": time.time_ns(), "learning_rate": self.learning_rate,
             "tensorboard_log": self.tensorboard_log, "_last_obs": None, "_last_episode_starts": None, "_last_original_obs": None, "_episode_num": 0,
             "use_sde": False, "sde_sample_freq": -1, "_current_progress_remaining": 0.0, "_stats_window_size": 100, "ep_info_buffer": None,
@@ -1196,7 +1243,7 @@ class PPO:
             "rollout_buffer_class": None, "rollout_buffer_kwargs": {}, "batch_size": self.batch_size, "n_epochs": self.n_epochs, "clip_range": self.clip_range,
             "clip_range_vf": None, "normalize_advantage": self.normalize_advantage, "target_kl": None, "verbose": self.verbose, "_custom_logger": False,
             "tma": {"engine": "three-mlagents_amd", "task_id": getattr(env, "task_id", None), "mfma_dtype": self.policy_kwargs.get("mfma_dtype", "f32"),
-                    "adam_step": self._adam_step, "allreduce_path": self.allreduce_path if hasattr(self, "_native_comm") else "none",
+                    "activation": pol.activation, "adam_step": self._adam_step, "allreduce_path": self.allreduce_path if hasattr(self, "_native_comm") else "none",
                     "world_size": getattr(self, "world_size", 1), "obs_dim": pol.obs_dim, "act_dim": pol.act_dim, "continuous": pol.continuous, "hidden": pol.hidden},
         }
         data.update(sb3_format.data_members(obs_space, act_space))
@@ -1253,14 +1300,15 @@ class PPO:
     ALGORITHM = "ppo"  # data["tma"]["algorithm"] of the zips a class writes and loads (zips from before the key existed are PPO's)
 
     @classmethod
-    def _from_data(cls, data: dict, num, hidden: int, mfma: str) -> "PPO":
+    def _from_data(cls, data: dict, num, hidden: int, mfma: str, extra_policy_kwargs: dict | None = None) -> "PPO":
         """An instance without an env from a zip's `data` (num(key, default): a scalar member, or the default where SB3 pickled an object)."""
         return cls(data.get("policy_class", "MlpPolicy") if isinstance(data.get("policy_class"), str) else "MlpPolicy", None,
                    learning_rate=num("learning_rate", 3e-4), n_steps=num("n_steps", 2048), batch_size=num("batch_size", 64),
                    n_epochs=num("n_epochs", 10), gamma=num("gamma", 0.99), gae_lambda=num("gae_lambda", 0.95), clip_range=num("clip_range", 0.2),
                    normalize_advantage=num("normalize_advantage", True), ent_coef=num("ent_coef", 0.0), vf_coef=num("vf_coef", 0.5),
                    max_grad_norm=num("max_grad_norm", 0.5),
-                   policy_kwargs={"net_arch": [hidden, hidden], "mfma_dtype": mfma}, seed=num("seed", 0), _init_setup_model=False)
+                   policy_kwargs={"net_arch": [hidden, hidden], "mfma_dtype": mfma, **(extra_policy_kwargs or {})}, seed=num("seed", 0),
+                   _init_setup_model=False)
 
     def _restore_extra(self, tma_extra: dict) -> None:
         """Engine-only members of a zip's data["tma"] beyond the Adam step (none for PPO)."""
@@ -1310,7 +1358,10 @@ class PPO:
             v = data.get(key, default)
             return default if isinstance(v, dict) or v is None else v  # SB3 stores schedules as pickled objects
 
-        model = cls._from_data(data, _num, data["hidden"], mfma)
+        from . import sb3_format
+
+        pk_extra = sb3_format.policy_kwargs_from_data(data)  # activation_fn ("tanh" / "relu"; an unknown one is a ValueError), log_std_init, ortho_init
+        model = cls._from_data(data, _num, data["hidden"], mfma, pk_extra)
         model.num_timesteps, model._n_updates = data.get("num_timesteps", 0), data.get("_n_updates", 0)
         model._adam_step = int(tma_extra.get("adam_step", data.get("_adam_step", 0)))
         if env is not None:
@@ -1320,8 +1371,6 @@ class PPO:
             model._restore_extra(tma_extra)
             model.policy.load_state_dict(sd)
             state = opt.get("state") or {}
-            from . import sb3_format
-
             order = sb3_format.parameter_order(model.policy.continuous)
             model._load_optimizer_state(state, order)
         else:
@@ -1329,7 +1378,8 @@ class PPO:
 
             dev = _require_gpu(None if device == "auto" else device)
             model.device = dev
-            model.policy = HipActorCriticPolicy(data["obs_dim"], data["act_dim"], data["continuous"], data["hidden"], dev, seed=0, mfma_dtype=mfma)
+            model.policy = HipActorCriticPolicy(data["obs_dim"], data["act_dim"], data["continuous"], data["hidden"], dev, seed=0, mfma_dtype=mfma,
+                                                activation=pk_extra["activation_fn"], log_std_init=pk_extra["log_std_init"], ortho_init=pk_extra["ortho_init"])
             model.policy.load_state_dict(sd)
         return model
 

@@ -18,6 +18,7 @@ from __future__ import annotations
 import base64
 import contextlib
 import pickle
+import re
 import sys
 import types
 from typing import Any
@@ -93,6 +94,67 @@ def data_members(observation_space, action_space) -> dict[str, Any]:
         "observation_space": serialized(space_pickle(observation_space), f"<class '{om}.{on}'>", _shape=list(observation_space.shape)),
         "action_space": serialized(space_pickle(action_space), f"<class '{am}.{an}'>", _shape=list(action_space.shape)),
     }
+
+
+# ---- policy_kwargs: activation_fn, log_std_init, ortho_init.  SB3's data_to_json keeps, beside the pickled blob of a non-JSON member, a str() of
+# each of its items: a policy built with activation_fn=nn.ReLU leaves "activation_fn": "<class 'torch.nn.modules.activation.ReLU'>" there.
+ACTIVATIONS = {"tanh": (0, "Tanh"), "relu": (1, "ReLU")}  # name -> (tma_policy_dims.activation, torch.nn class name)
+
+
+def parse_activation(fn) -> str:
+    """policy_kwargs["activation_fn"] -> "tanh" / "relu".  Accepted: None (SB3's default, tanh), torch.nn.Tanh, torch.nn.ReLU, "tanh", "relu"."""
+    if fn is None:
+        return "tanh"
+    if isinstance(fn, str) and fn.lower() in ACTIVATIONS:
+        return fn.lower()
+    if isinstance(fn, type):
+        import torch
+
+        for name, (_, cls) in ACTIVATIONS.items():
+            if fn is getattr(torch.nn, cls):
+                return name
+    raise ValueError(f"activation_fn must be torch.nn.Tanh or torch.nn.ReLU (or 'tanh' / 'relu'), got {fn!r}: the kernels have no other activation")
+
+
+def activation_repr(name: str) -> str:
+    """str(torch.nn.<cls>): what SB3's JSON shows for the member."""
+    return f"<class 'torch.nn.modules.activation.{ACTIVATIONS[name][1]}'>"
+
+
+def policy_kwargs_data(hidden: int, activation: str = "tanh", log_std_init: float = 0.0, ortho_init: bool = True) -> dict[str, Any]:
+    """data["policy_kwargs"] of a zip: net_arch, and each of the three other supported kwargs where it is not SB3's default."""
+    pk: dict[str, Any] = {"net_arch": [int(hidden), int(hidden)]}
+    if activation != "tanh":
+        pk["activation_fn"] = activation_repr(activation)
+    if float(log_std_init) != 0.0:
+        pk["log_std_init"] = float(log_std_init)
+    if not ortho_init:
+        pk["ortho_init"] = False
+    return pk
+
+
+def policy_kwargs_from_data(data: dict) -> dict[str, Any]:
+    """{"activation_fn", "log_std_init", "ortho_init"} of a zip's `data`: the activation from data["tma"] (this engine's zips), else from the text
+    of data["policy_kwargs"]["activation_fn"] (this engine's, or the str() SB3 keeps beside its blob), else tanh.  A name that is neither Tanh nor
+    ReLU is a ValueError: such a zip would otherwise run its weights through the wrong non-linearity."""
+    tma = data.get("tma") if isinstance(data.get("tma"), dict) else {}
+    pk = data.get("policy_kwargs") if isinstance(data.get("policy_kwargs"), dict) else {}
+    act = None
+    if tma.get("activation") is not None:
+        act = parse_activation(str(tma["activation"]))
+    elif pk.get("activation_fn") is not None:
+        text = str(pk["activation_fn"])
+        words = re.findall(r"[A-Za-z_]\w*", text)  # the class name is the last identifier of "<class 'torch.nn.modules.activation.ReLU'>" (LeakyReLU is not ReLU)
+        hits = [name for name, (_, cls) in ACTIVATIONS.items() if words and (words[-1] == cls or words[-1].lower() == name)]
+        if len(hits) != 1:
+            raise ValueError(f"policy zip with activation_fn {text!r}: the engine runs torch.nn.Tanh and torch.nn.ReLU policies only")
+        act = hits[0]
+    out: dict[str, Any] = {"activation_fn": act or "tanh", "log_std_init": 0.0, "ortho_init": True}
+    if isinstance(pk.get("log_std_init"), (int, float)):
+        out["log_std_init"] = float(pk["log_std_init"])
+    if isinstance(pk.get("ortho_init"), bool):
+        out["ortho_init"] = pk["ortho_init"]
+    return out
 
 
 # torch registers an ActorCriticPolicy's parameters in this order: the module's own (log_std) first, then the sub-modules in the order
