@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 220
+#define TMA_VERSION 221
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -422,6 +422,20 @@ int tma_ppo_persist_fallbacks(void *workspace, int64_t *count_out, void *stream)
  * HOST memory, the env-major flat indices f = i*T + t of permuted rows [0, total) for (perm_seed, perm_epoch).  Minibatch m of size B is
  * rows [m*B, (m+1)*B).  Lets a caller reproduce or log the schedule; no GPU work. */
 int tma_ppo_permutation(uint32_t perm_seed, uint32_t perm_epoch, int64_t total, int64_t *indices_out_host);
+/* One minibatch of SB3's RolloutBuffer.get as dense device tensors (ABI 221): permuted rows [mb->start, mb->start + mb->count) of a rollout, in
+ * ONE launch.  The gradient entries above gather their rows inside their kernels; this is for a caller who writes the update itself (a torch loss
+ * on tma_policy_evaluate_actions / tma_policy_head and their VJPs) and needs the rows the engine's own epoch would have used.
+ * Row selection is exactly the gradient kernels': mb->indices if given (device memory), else the on-device permutation (perm_seed, perm_epoch)
+ * over T*N -- the env-major flat index f = i*T + t (SB3 swap_and_flatten), read from plane row t*N + i.  mb->prepared_batch and mb->stats_count
+ * are ignored; rb->packed is never read.  `values`: the [T][N] plane of the rollout's value predictions (tma_rollout has none; may be NULL).
+ * `d` supplies D, A and the head kind.  Outputs: obs_out f32[count][D], actions_out i32[count] (Discrete) or f32[count][A] (Box), the four
+ * scalar planes f32[count]; any output pointer may be NULL and that plane is then skipped (old_values_out must be NULL when `values` is).
+ * A pure copy: every output element has the bits of its source element.  No atomics, no workspace; the grid is capped and strides; every
+ * offset is 64-bit.  Refused with TMA_ERR_INVALID before any HIP call: rb / d / mb NULL, bad dims, a source plane that is NULL while its
+ * output is not, count < 1, start < 0, start + count > T*N, T*N >= 2^31. */
+int tma_rollout_gather(const tma_rollout *rb, const float *values /* [T][N], may be NULL */, const tma_policy_dims *d, const tma_minibatch *mb,
+                       float *obs_out /* [count][D] */, void *actions_out /* i32 [count] | f32 [count][A] */, float *old_values_out,
+                       float *old_log_prob_out, float *advantages_out, float *returns_out, void *stream);
 /* Profiling aid for bench.py's roofline object: when enabled, tma_ppo_minibatch_grad brackets its DOMINANT kernel (the persistent
  * forward+backward kernel; for two-pass shapes both passes; not the advantage pass, not the slab reduction) with HIP events recorded on
  * the stream it launches on; tma_debug_last_grad_kernel_us waits for the last bracketed launch and returns its duration. */

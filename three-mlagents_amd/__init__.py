@@ -8,7 +8,7 @@ __version__ = "0.2.0"
 
 from .tasks import ENGINE_TASKS, EngineTask, make_env, resolve  # noqa: E402
 
-__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C"]
+__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C", "RolloutBuffer", "RolloutBufferSamples"]
 
 
 def __getattr__(name):  # the algorithm classes import torch: on first use, not with the task table
@@ -20,4 +20,8 @@ def __getattr__(name):  # the algorithm classes import torch: on first use, not 
         from .a2c import A2C
 
         return A2C
+    if name in ("RolloutBuffer", "RolloutBufferSamples"):
+        from . import rollout_buffer
+
+        return getattr(rollout_buffer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

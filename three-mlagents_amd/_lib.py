@@ -16,6 +16,7 @@ ACT_I32, ACT_I64, ACT_F32 = 0, 1, 2
 EP_STRIDE = 1 << 20
 EV_SCRATCH_DOUBLES = 1536  # include/tma.h TMA_EV_SCRATCH_DOUBLES
 VECNORM_ONE_LAUNCH_MAX = 256  # include/tma.h TMA_VECNORM_ONE_LAUNCH_MAX
+GATHER_BLOCKS = 2048  # csrc/tma_workspace.h GATHER_BLOCKS: tma_rollout_gather's grid cap (workgroups of four waves); the tests size a case past it
 ROLLOUT_NORM_PER_STEP, ROLLOUT_NORM_FUSED_DISC_F32, ROLLOUT_NORM_FUSED_CONT_F32 = 0, 1, 2  # include/tma.h TMA_ROLLOUT_NORM_*: tma_rollout_norm_plan
 
 _vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_double
@@ -111,6 +112,7 @@ SIGNATURES = {
     "tma_ppo_adam_step": (_i32, [_vp, _vp, _vp, _vp, _pd, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp]),
     "tma_ppo_adam_step_local": (_i32, [_vp, _vp, _vp, _vp, _pd, _i64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _i64]),
     "tma_ppo_permutation": (_i32, [_u32, _u32, _i64, _vp]),
+    "tma_rollout_gather": (_i32, [C.POINTER(Rollout), _vp, _pd, C.POINTER(Minibatch), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tma_ppo_persist_fallbacks": (_i32, [_vp, C.POINTER(_i64), _vp]),
     "tma_ppo_train_epoch_local": (_i32, [_vp, _pd, C.POINTER(Rollout), _u32, _u32, _i64, C.POINTER(PPOHParams), _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64,
                                          _f64, _vp, _vp]),

@@ -19,6 +19,7 @@ constexpr int WIDE_SQ_SLOTS = 8192;    // sum-of-squares partials of slab_reduce
 constexpr int64_t DZ1_CAP = 1 << 18;   // samples per minibatch whose dz1 images fit the workspace cache (two-pass layouts only)
 constexpr int W2_DEFER_ROWS = 1024;    // rows per image of the dW2 deferral buffer ([net][h1 | dz2][W2_DEFER_ROWS][H]: half-group minibatches of <= 1024 samples)
 constexpr int ADV_BLOCKS = 128;        // partial blocks per minibatch at the most (1 024 rows each up to 131 072 rows, longer slices beyond)
+constexpr int GATHER_BLOCKS = 2048;    // workgroups of tma_rollout_gather at the most (four waves each: 32 waves a CU), then it strides (uses no workspace)
 
 // (round 6: ... and 97 .. 128 observations with a Box head at H = 256 -- Ant-v5's 105 -- as four layer-1 k-steps)
 static inline bool bf_two_pass(const PLayout &L) {

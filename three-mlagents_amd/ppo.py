@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rollout_buffer import RolloutBuffer, perm_seed as _perm_seed
 from .vec_env import HipVecEnv
 
 SB3_KEYS = [
@@ -526,6 +527,9 @@ class PPO:
         self._rollout_view = _lib.Rollout(_lib.ptr(b["obs"]), _lib.ptr(b["actions"]), _lib.ptr(b["log_probs"]), _lib.ptr(b["advantages"]),
                                           _lib.ptr(b["returns"]), T, N, _lib.ptr(self._packed) if self._packed is not None else None)
         self._hp = _lib.PPOHParams(self.clip_range, self.ent_coef, self.vf_coef, 1 if self.normalize_advantage else 0)
+        # SB3's model.rollout_buffer: views of the planes above and get(batch_size), the engine's own minibatches as device tensors for an update
+        # written in torch (rollout_buffer.py); it launches nothing unless get() is called
+        self.rollout_buffer = RolloutBuffer(self)
         # data parallel: global advantage statistics come from tma_ppo_epoch_prepare's partials -- its limits are checked HERE, before any
         # rank has collected a rollout, not inside train()
         if self.world_size > 1 and self.normalize_advantage and not (T * N <= (1 << 22) and self.batch_size >= 256):
@@ -728,6 +732,7 @@ class PPO:
     def collect_rollouts(self, callback=None, chunk: int | None = None) -> bool:
         """SB3 OnPolicyAlgorithm.collect_rollouts: n_steps vector steps through the native driver, then GAE."""
         L, T, eng = _lib.lib(), self.n_steps, self.env.engine
+        self.rollout_buffer.full = False  # (until this rollout is complete and its advantages exist)
         self.policy._sync_if_stepped()  # (a torch optimizer stepped policy.parameters(): rebuild the derived copies the drivers read)
         vn = self._vecnorm
         if not self._last_obs_valid:
@@ -772,6 +777,7 @@ class PPO:
             # behind the advantages / returns it copies, so that the `packed` pointer of the rollout view is never stale for a direct
             # tma_ppo_minibatch_grad caller between collect_rollouts() and train()
             _lib.check(L.tma_ppo_pack_samples(C.byref(self._rollout_view), C.byref(self.policy.dims), _lib.ptr(self._packed), self._stream()))
+        self.rollout_buffer.full = True
         return True
 
     # -- update ---------------------------------------------------------------------------
@@ -781,7 +787,7 @@ class PPO:
         self.policy._sync_if_stepped()
         total = self.n_steps * self.n_envs
         scale = 1.0 / self.world_size
-        perm_seed = (self.seed * 2654435761 + 12345) & 0xFFFFFFFF
+        perm_seed = _perm_seed(self.seed)
         can_prepare = total <= (1 << 22) and self.batch_size >= 256  # limits of tma_ppo_epoch_prepare (include/tma.h)
         # data parallel: every rank normalises a minibatch's advantages with the mean / std of the GLOBAL minibatch (the rows of all
         # ranks), as one SB3 run over the concatenated batch would -- one all-reduce of 16 B per minibatch, once per epoch
