@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 221
+#define TMA_VERSION 222
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -232,6 +232,25 @@ int tma_policy_head(const float *params, const tma_policy_dims *d, const float *
  * NULL cotangents and a workspace below what the bytes function reports are refused (TMA_ERR_INVALID) before any HIP call. */
 int tma_policy_head_backward(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, const float *g_head, const float *g_values,
                              float *grad_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* The two VJPs above with the gradient with respect to the OBSERVATIONS as a second output (ABI 222): what torch autograd computes behind a torch
+ * module in front of the policy (a learned encoder) or behind a loss differentiated with respect to a frozen policy's input (saliency, FGSM / PGD,
+ * a teacher's dKL/dobs) --
+ *   grad_obs[i][k] = sum_n dz1_pi[i][n] W1_pi[n][k] + sum_n dz1_vf[i][n] W1_vf[n][k],   dz1: row i's cotangent at the first layer's pre-activation.
+ * grad_params f32[n_trainable] and grad_obs f32[n][obs_dim] (dense) may each be NULL, not both.  With grad_obs NULL the call IS the ..._backward
+ * call above: the same launches, the same bits.  With grad_params NULL (a frozen policy) the weight-gradient launch is skipped.  grad_obs is
+ * OVERWRITTEN, exactly n * obs_dim floats (a row whose cotangents are all zero gets zeros), by a third launch per chunk behind the other two:
+ * one wave per 16-row tile on the f32 MFMA, no reduction over rows, one accumulator chain per element in an order that depends on `hidden`
+ * alone -- a row's gradient has the same bits whatever the batch around it, the chunk length, or whether grad_params is asked for.  grad_params
+ * has the bits of the ..._backward call whether or not grad_obs is asked for.  grad_obs needs no alignment beyond a float's.  Workspace, chunking,
+ * TMA_VJP_CHUNK_ROWS and every refusal are those of the ..._backward calls (grad_params itself may be NULL here); also refused (TMA_ERR_INVALID,
+ * before any HIP call): both outputs NULL, grad_obs overlapping obs (byte ranges of n * obs_dim * 4) and grad_obs overlapping the workspace. */
+int tma_policy_evaluate_actions_vjp(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
+                                    const float *g_values, const float *g_logp, const float *g_entropy,
+                                    float *grad_params /* [n_trainable] or NULL */, float *grad_obs /* [n][obs_dim] or NULL */,
+                                    void *workspace, int64_t workspace_bytes, void *stream);
+int tma_policy_head_vjp(const float *params, const tma_policy_dims *d, const float *obs, int64_t n,
+                        const float *g_head, const float *g_values,
+                        float *grad_params, float *grad_obs, void *workspace, int64_t workspace_bytes, void *stream);
 /* ActorCriticPolicy.predict_values */
 int tma_policy_values(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, float *values_out, void *stream);
 /* collect_rollouts timeout bootstrap: rewards[i] += gamma * V(terminal_obs[i]) where truncated[i] */

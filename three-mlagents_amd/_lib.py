@@ -94,6 +94,8 @@ SIGNATURES = {
     "tma_policy_evaluate_actions_backward": (_i32, [_vp, _pd, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "tma_policy_head": (_i32, [_vp, _pd, _vp, _i64, _vp, _vp, _vp]),
     "tma_policy_head_backward": (_i32, [_vp, _pd, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tma_policy_evaluate_actions_vjp": (_i32, [_vp, _pd, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tma_policy_head_vjp": (_i32, [_vp, _pd, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "tma_policy_values": (_i32, [_vp, _pd, _vp, _i64, _vp, _vp]),
     "tma_policy_bootstrap": (_i32, [_vp, _pd, _vp, _vp, _i64, _f64, _vp, _vp]),
     "tma_ppo_workspace_bytes": (_i64, [_pd]),

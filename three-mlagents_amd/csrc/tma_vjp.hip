@@ -15,6 +15,10 @@
 // Summation order of one gradient element: rows in order inside a segment, segments in order inside a chunk, chunks in order.  It depends on
 // (shape, n, chunk length) and on nothing else, so equal inputs give equal bits.
 // Both kernels are bounded loops over their own rows: no spin waits, no exchange between workgroups.
+//   (c) vjp_input_kernel (ABI 222, only where the caller asks for grad_obs): the gradient with respect to the observations of the chunk's rows,
+//       dObs[i][k] = sum_n dz1_pi[i][n] W1t_pi[k][n] + sum_n dz1_vf[i][n] W1t_vf[k][n], from the two dz1 planes phase (a) left behind.  One wave per
+//       16-row tile, no reduction over rows, plain stores: rows [base, base + rows) of grad_obs are overwritten.  Where grad_params is not asked
+//       for (a frozen policy) phase (b) is not launched: (a) then (c) per chunk.
 //
 // tma_policy_head_backward (ABI 218) is the same two launches for the head itself (tma_policy_head: logits / mean, and values):
 //   grad[e] = sum_i sum_j g_head[i][j] dhead_ij/dp_e + sum_i g_values[i] dV_i/dp_e.
@@ -276,6 +280,82 @@ __global__ __launch_bounds__(64 * NW) void vjp_reduce_kernel(PLayout L, VjpPlane
     }
 }
 
+// ---- (c) the observation gradient of a chunk: dObs[16][D] = dz1_pi[16][H] . W1t_pi[D][H]^T + dz1_vf[16][H] . W1t_vf[D][H]^T
+// No [out][in] copy of W1 exists and none is needed: the B operand of output column k and products n is W1t[k][n], so the four n a lane feeds to
+// four consecutive k-steps are 16 contiguous bytes of row k -- and the A operand the same 16 bytes of the dz1 row.  Both come straight from
+// global memory (W1t is at most 172 x 1024 floats per net and L2-resident; a dz1 tile is read once per pass of 64 columns, and the
+// passes of a tile are separate waves), no LDS.
+// The value net's W1t starts at an odd float offset for most heads, hence the 4-byte-aligned vector type (gfx950 loads it as one dwordx4).
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// NT column tiles [k0, k0 + 16 NT) of one row tile.  ONE accumulator chain per output element: the policy net's H products, then the value net's,
+// each net in blocks of 16 n (q), inside a block k-step v = 0..3 takes n = 16 q + 4 g + v from lane group g = 0..3 (the MFMA's own k order) --
+// a fixed order that depends on nothing but H, so equal inputs give equal bits whatever the batch, the chunk length or the row's place in it.
+// Columns k >= D read row D - 1 (an address that exists) and are never stored: an MFMA column depends on its own B column alone.
+template <int NT>
+__device__ __forceinline__ void vjp_input_pass(const float *a_pi, const float *a_vf, const float *__restrict__ w_pi, const float *__restrict__ w_vf, int H,
+                                               int D, int k0, float *__restrict__ out, int rows_left, int lane) {
+    constexpr int QB = NT <= 2 ? 4 : 2;  // blocks of 16 n per batch of loads (H % 64 == 0: H / 16 is a multiple of 4)
+    const int r16 = lane & 15, g = lane >> 4;
+    int woff[NT];
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+        const int k = k0 + 16 * j + r16;
+        woff[j] = (k < D ? k : D - 1) * H + 4 * g;
+    }
+    f32x4 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; j++) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int net = 0; net < 2; net++) {
+        const float *a = (net == 0 ? a_pi : a_vf) + r16 * H + 4 * g;
+        const float *w = net == 0 ? w_pi : w_vf;
+        for (int q0 = 0; q0 < (H >> 4); q0 += QB) {
+            f32x4 av[QB], bv[QB][NT];
+#pragma unroll
+            for (int u = 0; u < QB; u++) {
+                av[u] = *reinterpret_cast<const f32x4 *>(a + 16 * (q0 + u));
+#pragma unroll
+                for (int j = 0; j < NT; j++) bv[u][j] = *reinterpret_cast<const f32x4_a4 *>(w + woff[j] + 16 * (q0 + u));
+            }
+#pragma unroll
+            for (int u = 0; u < QB; u++)
+#pragma unroll
+                for (int v = 0; v < 4; v++)
+#pragma unroll
+                    for (int j = 0; j < NT; j++) acc[j] = mfma16(av[u][v], bv[u][j][v], acc[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+        const int col = k0 + 16 * j + r16;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int row = g * 4 + r;
+            if (row < rows_left && col < D) out[(int64_t)row * D + col] = acc[j][r];  // rows behind the batch are not stored
+        }
+    }
+}
+
+// grid (16-row tiles of the chunk, passes of 64 output columns): one wave each.  The row index into a dz1 plane is chunk-local, the one into
+// grad_obs global (64-bit)
+__global__ __launch_bounds__(64) void vjp_input_kernel(const float *__restrict__ params, PLayout L, VjpPlanes ws, int64_t row_base, int rows,
+                                                       float *__restrict__ grad_obs) {
+    const int lane = threadIdx.x, row0 = (int)blockIdx.x << 4, ct = (int)blockIdx.y << 2;
+    const int D = L.D, H = L.H, n_ct = (D + 15) >> 4;  // column tiles of 16; this wave's are [ct, min(ct + 4, n_ct))
+    if (row0 >= rows || ct >= n_ct) return;
+    const float *a_pi = ws.dz1[0] + (int64_t)row0 * H, *a_vf = ws.dz1[1] + (int64_t)row0 * H;
+    const float *w_pi = params + L.pW1t, *w_vf = params + L.vW1t;
+    float *out = grad_obs + (row_base + row0) * D;
+    const int left = rows - row0;
+    switch (n_ct - ct) {
+    case 1: vjp_input_pass<1>(a_pi, a_vf, w_pi, w_vf, H, D, 16 * ct, out, left, lane); break;
+    case 2: vjp_input_pass<2>(a_pi, a_vf, w_pi, w_vf, H, D, 16 * ct, out, left, lane); break;
+    case 3: vjp_input_pass<3>(a_pi, a_vf, w_pi, w_vf, H, D, 16 * ct, out, left, lane); break;
+    default: vjp_input_pass<4>(a_pi, a_vf, w_pi, w_vf, H, D, 16 * ct, out, left, lane); break;
+    }
+}
+
 static int vjp_chunk_rows(const PLayout &L, int64_t *out) {
     int64_t c = vjp_default_chunk(L);
     if (const char *e = getenv("TMA_VJP_CHUNK_ROWS"); e && *e) {  // test hook, read on every call: shorter chunks (never longer: the workspace is sized for the default)
@@ -316,15 +396,23 @@ int64_t tma_policy_vjp_workspace_bytes(const tma_policy_dims *d, int64_t n) {
 
 }  // extern "C"
 
-// both entry points behind their own null checks.  head: g_logp carries g_head f32[n][act_dim], actions / g_entropy are null
+static bool bytes_overlap(const void *a, int64_t na, const void *b, int64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
+}
+
+// every entry point behind its own null checks.  head: g_logp carries g_head f32[n][act_dim], actions / g_entropy are null.  grad_out
+// (parameters) and grad_obs may each be null, not both: without grad_out phase (b) is not launched, without grad_obs phase (c)
 static int vjp_run(const char *who, bool head, const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
-                   const float *g_values, const float *g_logp, const float *g_entropy, float *grad_out, void *workspace, int64_t workspace_bytes,
-                   void *stream) {
+                   const float *g_values, const float *g_logp, const float *g_entropy, float *grad_out, float *grad_obs, void *workspace,
+                   int64_t workspace_bytes, void *stream) {
     int rc = TMA_OK;
     const int64_t need = tma_policy_vjp_workspace_bytes(d, n);
     if (!workspace || workspace_bytes < need)
         return fail(TMA_ERR_INVALID, "%s: workspace of %lld bytes, tma_policy_vjp_workspace_bytes reports %lld", who, (long long)(workspace ? workspace_bytes : 0),
                     (long long)need);
+    if (grad_obs && bytes_overlap(grad_obs, n * d->obs_dim * 4, workspace, workspace_bytes))
+        return fail(TMA_ERR_INVALID, "%s: grad_obs overlaps the workspace", who);
     const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
     int64_t chunk = 0;
     if ((rc = vjp_chunk_rows(L, &chunk))) return rc;
@@ -371,12 +459,45 @@ static int vjp_run(const char *who, bool head, const float *params, const tma_po
         } else if (head) rc = L.cont ? launch_a(vjp_tile_kernel<true, true, ACT_TANH>) : launch_a(vjp_tile_kernel<false, true, ACT_TANH>);
         else rc = L.cont ? launch_a(vjp_tile_kernel<true, false, ACT_TANH>) : launch_a(vjp_tile_kernel<false, false, ACT_TANH>);
         if (rc) return rc;
-        const float *obs_chunk = obs + base * L.D;
-        if (wide) vjp_reduce_kernel<4, 8><<<dim3((unsigned)n_blocks), dim3(512), 0, s>>>(L, ws, obs_chunk, rows, grad_out, base > 0 ? 1 : 0);
-        else vjp_reduce_kernel<1, 16><<<dim3((unsigned)n_blocks), dim3(1024), 0, s>>>(L, ws, obs_chunk, rows, grad_out, base > 0 ? 1 : 0);
-        TMA_LAUNCH_CHECK();
+        if (grad_out) {
+            const float *obs_chunk = obs + base * L.D;
+            if (wide) vjp_reduce_kernel<4, 8><<<dim3((unsigned)n_blocks), dim3(512), 0, s>>>(L, ws, obs_chunk, rows, grad_out, base > 0 ? 1 : 0);
+            else vjp_reduce_kernel<1, 16><<<dim3((unsigned)n_blocks), dim3(1024), 0, s>>>(L, ws, obs_chunk, rows, grad_out, base > 0 ? 1 : 0);
+            TMA_LAUNCH_CHECK();
+        }
+        if (grad_obs) {
+            vjp_input_kernel<<<dim3((unsigned)tiles, (unsigned)((L.D + 63) / 64)), dim3(64), 0, s>>>(params, L, ws, base, rows, grad_obs);
+            TMA_LAUNCH_CHECK();
+        }
     }
     return TMA_OK;
+}
+
+// the refusals of the four entry points, in one order: dims, null inputs, n, cotangents, outputs, overlap with obs (then vjp_run's: workspace)
+static int vjp_eval(const char *who, const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
+                    const float *g_values, const float *g_logp, const float *g_entropy, float *grad_params, float *grad_obs, bool params_required,
+                    void *workspace, int64_t workspace_bytes, void *stream) {
+    const int rc = vjp_check(d, who);  // (every refusal comes back before the first HIP call)
+    if (rc) return rc;
+    if (!params || !obs || !actions || (params_required && !grad_params)) return fail(TMA_ERR_INVALID, "%s: null buffer", who);
+    if (n < 1) return fail(TMA_ERR_INVALID, "%s: n must be >= 1", who);
+    if (!g_values && !g_logp && !g_entropy) return fail(TMA_ERR_INVALID, "%s: g_values, g_logp and g_entropy are all null", who);
+    if (!grad_params && !grad_obs) return fail(TMA_ERR_INVALID, "%s: grad_params and grad_obs are both null", who);
+    if (grad_obs && bytes_overlap(grad_obs, n * d->obs_dim * 4, obs, n * d->obs_dim * 4)) return fail(TMA_ERR_INVALID, "%s: grad_obs overlaps obs", who);
+    return vjp_run(who, false, params, d, obs, actions, n, g_values, g_logp, g_entropy, grad_params, grad_obs, workspace, workspace_bytes, stream);
+}
+
+static int vjp_head(const char *who, const float *params, const tma_policy_dims *d, const float *obs, int64_t n, const float *g_head,
+                    const float *g_values, float *grad_params, float *grad_obs, bool params_required, void *workspace, int64_t workspace_bytes,
+                    void *stream) {
+    const int rc = vjp_check(d, who);
+    if (rc) return rc;
+    if (!params || !obs || (params_required && !grad_params)) return fail(TMA_ERR_INVALID, "%s: null buffer", who);
+    if (n < 1) return fail(TMA_ERR_INVALID, "%s: n must be >= 1", who);
+    if (!g_head && !g_values) return fail(TMA_ERR_INVALID, "%s: g_head and g_values are both null", who);
+    if (!grad_params && !grad_obs) return fail(TMA_ERR_INVALID, "%s: grad_params and grad_obs are both null", who);
+    if (grad_obs && bytes_overlap(grad_obs, n * d->obs_dim * 4, obs, n * d->obs_dim * 4)) return fail(TMA_ERR_INVALID, "%s: grad_obs overlaps obs", who);
+    return vjp_run(who, true, params, d, obs, nullptr, n, g_values, g_head, nullptr, grad_params, grad_obs, workspace, workspace_bytes, stream);
 }
 
 extern "C" {
@@ -384,24 +505,25 @@ extern "C" {
 int tma_policy_evaluate_actions_backward(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
                                          const float *g_values, const float *g_logp, const float *g_entropy, float *grad_out, void *workspace,
                                          int64_t workspace_bytes, void *stream) {
-    const char *who = "tma_policy_evaluate_actions_backward";
-    const int rc = vjp_check(d, who);  // (every refusal comes back before the first HIP call)
-    if (rc) return rc;
-    if (!params || !obs || !actions || !grad_out) return fail(TMA_ERR_INVALID, "%s: null buffer", who);
-    if (n < 1) return fail(TMA_ERR_INVALID, "%s: n must be >= 1", who);
-    if (!g_values && !g_logp && !g_entropy) return fail(TMA_ERR_INVALID, "%s: g_values, g_logp and g_entropy are all null", who);
-    return vjp_run(who, false, params, d, obs, actions, n, g_values, g_logp, g_entropy, grad_out, workspace, workspace_bytes, stream);
+    return vjp_eval("tma_policy_evaluate_actions_backward", params, d, obs, actions, n, g_values, g_logp, g_entropy, grad_out, nullptr, true, workspace,
+                    workspace_bytes, stream);
+}
+
+int tma_policy_evaluate_actions_vjp(const float *params, const tma_policy_dims *d, const float *obs, const void *actions, int64_t n,
+                                    const float *g_values, const float *g_logp, const float *g_entropy, float *grad_params, float *grad_obs,
+                                    void *workspace, int64_t workspace_bytes, void *stream) {
+    return vjp_eval("tma_policy_evaluate_actions_vjp", params, d, obs, actions, n, g_values, g_logp, g_entropy, grad_params, grad_obs, false, workspace,
+                    workspace_bytes, stream);
 }
 
 int tma_policy_head_backward(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, const float *g_head, const float *g_values,
                              float *grad_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    const char *who = "tma_policy_head_backward";
-    const int rc = vjp_check(d, who);  // (every refusal comes back before the first HIP call)
-    if (rc) return rc;
-    if (!params || !obs || !grad_out) return fail(TMA_ERR_INVALID, "%s: null buffer", who);
-    if (n < 1) return fail(TMA_ERR_INVALID, "%s: n must be >= 1", who);
-    if (!g_head && !g_values) return fail(TMA_ERR_INVALID, "%s: g_head and g_values are both null", who);
-    return vjp_run(who, true, params, d, obs, nullptr, n, g_values, g_head, nullptr, grad_out, workspace, workspace_bytes, stream);
+    return vjp_head("tma_policy_head_backward", params, d, obs, n, g_head, g_values, grad_out, nullptr, true, workspace, workspace_bytes, stream);
+}
+
+int tma_policy_head_vjp(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, const float *g_head, const float *g_values,
+                        float *grad_params, float *grad_obs, void *workspace, int64_t workspace_bytes, void *stream) {
+    return vjp_head("tma_policy_head_vjp", params, d, obs, n, g_head, g_values, grad_params, grad_obs, false, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

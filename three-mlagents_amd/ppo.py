@@ -124,41 +124,51 @@ def policy_dims(obs_dim: int, hidden: int, act_dim: int, continuous: bool, mfma_
 
 
 class _EvaluateActions(torch.autograd.Function):
-    """evaluate_actions as a node of a torch autograd graph (HipActorCriticPolicy.parameters() opts in): the forward is the forward-only call,
-    the backward ONE tma_policy_evaluate_actions_backward launch sequence with whichever cotangents autograd supplies."""
+    """evaluate_actions as a node of a torch autograd graph (HipActorCriticPolicy.parameters() opts the parameters in, enable_obs_grad() and an `obs`
+    that requires grad the observations): the forward is the forward-only call, the backward ONE tma_policy_evaluate_actions_vjp launch sequence with whichever
+    cotangents autograd supplies, for exactly the inputs ctx.needs_input_grad names.  leaf: the parameter leaf, or None (a frozen policy);
+    obs: float32, contiguous, on the policy's device (the caller's dtype / device conversion is torch's, in front of this node)."""
 
     @staticmethod
     def forward(ctx, leaf, policy, obs, actions):
         ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None -> NULL, not as a zero array
-        ctx.save_for_backward(leaf)  # (torch then refuses a backward after an in-place step on the leaf, as it does for its own modules)
-        ctx.policy, ctx.obs, ctx.actions = policy, obs, actions
-        return policy._evaluate_actions(obs, actions)
+        if leaf is not None:
+            ctx.save_for_backward(leaf)  # (torch then refuses a backward after an in-place step on the leaf, as it does for its own modules)
+        ctx.policy, ctx.obs, ctx.actions = policy, obs.detach(), actions
+        return policy._evaluate_actions(ctx.obs, actions)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g_values, g_logp, g_entropy):
-        (leaf,) = ctx.saved_tensors
+        want_p, want_o = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
         if g_values is None and g_logp is None and g_entropy is None:
-            return torch.zeros_like(leaf), None, None, None
-        return ctx.policy.evaluate_actions_backward(ctx.obs, ctx.actions, g_values, g_logp, g_entropy), None, None, None
+            return (torch.zeros_like(ctx.saved_tensors[0]) if want_p else None), None, (torch.zeros_like(ctx.obs) if want_o else None), None
+        g = ctx.policy.evaluate_actions_backward(ctx.obs, ctx.actions, g_values, g_logp, g_entropy, params_grad=want_p, obs_grad=want_o)
+        gp, go = g if (want_p and want_o) else ((g, None) if want_p else (None, g))
+        return gp, None, go, None
 
 
 class _Head(torch.autograd.Function):
     """head as a node of a torch autograd graph, written like _EvaluateActions: the forward is the forward-only call, the backward ONE
-    tma_policy_head_backward launch sequence with whichever of the two cotangents autograd supplies."""
+    tma_policy_head_vjp launch sequence with whichever of the two cotangents autograd supplies."""
 
     @staticmethod
     def forward(ctx, leaf, policy, obs):
         ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None -> NULL, not as a zero array
-        ctx.save_for_backward(leaf)
-        ctx.policy, ctx.obs = policy, obs
-        return policy._head(obs)
+        if leaf is not None:
+            ctx.save_for_backward(leaf)
+        ctx.policy, ctx.obs = policy, obs.detach()
+        return policy._head(ctx.obs)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g_head, g_values):
-        (leaf,) = ctx.saved_tensors
+        want_p, want_o = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
         if g_head is None and g_values is None:
-            return torch.zeros_like(leaf), None, None
-        return ctx.policy.head_backward(ctx.obs, g_head, g_values), None, None
+            return (torch.zeros_like(ctx.saved_tensors[0]) if want_p else None), None, (torch.zeros_like(ctx.obs) if want_o else None)
+        g = ctx.policy.head_backward(ctx.obs, g_head, g_values, params_grad=want_p, obs_grad=want_o)
+        gp, go = g if (want_p and want_o) else ((g, None) if want_p else (None, g))
+        return gp, None, go
 
 
 class HipActorCriticPolicy:
@@ -188,6 +198,7 @@ class HipActorCriticPolicy:
         self._leaf: torch.Tensor | None = None  # parameters(): the autograd leaf over params[:n_trainable]; None = forward-only, as ever
         self._synced_version = 0                # ... and its _version when the derived copies were last rebuilt
         self._vjp_ws: torch.Tensor | None = None
+        self._obs_grad = False                  # enable_obs_grad(): an `obs` that requires grad becomes an edge of the autograd graph
         self.load_state_dict(self._orthogonal_init(seed))
 
     # -- init / (de)serialisation in SB3's state_dict naming -------------------------------
@@ -210,12 +221,55 @@ class HipActorCriticPolicy:
         steps the live weights, and `evaluate_actions` becomes differentiable with respect to it.  The kernel-launching methods rebuild the
         derived weight copies (`sync`) when an in-place step moved the leaf since the last rebuild.  bf16 policies are refused: their forward
         rounds the operands and the f32 backward would not be its derivative."""
-        if self.mfma_dtype == "bf16":
-            raise ValueError("parameters(): the backward of evaluate_actions is not built for mfma_dtype='bf16' (use 'f32' or 'bf16x3')")
+        self._refuse_bf16_backward("parameters()")
         if self._leaf is None:
             self._leaf = self.params[: self.n_trainable].detach().requires_grad_(True)
             self._synced_version = self._leaf._version
         return [self._leaf]
+
+    def _refuse_bf16_backward(self, who: str) -> None:
+        if self.mfma_dtype == "bf16":
+            raise ValueError(f"{who}: the backward of evaluate_actions is not built for mfma_dtype='bf16' (use 'f32' or 'bf16x3')")
+
+    def enable_obs_grad(self, on: bool = True) -> "HipActorCriticPolicy":
+        """Opt in to gradients with respect to the observations (off by default: nothing below changes until this is called).  From then on an
+        `obs` that requires grad makes `evaluate_actions` / `head` / `get_distribution` nodes of its autograd graph and receives its gradient --
+        with or without `parameters()`: a frozen policy needs no leaf and makes none.  bf16 policies are refused for the reason `parameters()`
+        gives.  Returns the policy."""
+        if on:
+            self._refuse_bf16_backward("enable_obs_grad()")
+        self._obs_grad = bool(on)
+        return self
+
+    def _graph_inputs(self, who: str, obs: torch.Tensor):
+        """(differentiable?, leaf or None, obs): whether the call is a node of an autograd graph -- grad mode on and the parameter leaf requiring
+        grad, or `obs` requiring grad after enable_obs_grad() -- and `obs` as float32 contiguous rows on the policy's device, still attached to
+        the caller's graph in the latter case.  Without enable_obs_grad() an `obs` that requires grad is what it always was: a ValueError where
+        the call is differentiable with respect to the parameters, ignored where it is not."""
+        grad_mode = torch.is_grad_enabled()
+        want_leaf = grad_mode and self._leaf is not None and self._leaf.requires_grad
+        want_obs = grad_mode and isinstance(obs, torch.Tensor) and obs.requires_grad
+        if want_obs and not self._obs_grad:
+            if want_leaf:
+                raise ValueError(f"{who}: obs.requires_grad is set, and gradients with respect to the observations are off: "
+                                 "call policy.enable_obs_grad() first")
+            want_obs = False
+        return want_obs or want_leaf, self._leaf, (self._rows(obs) if want_obs else self._rows(obs.detach()))
+
+    @staticmethod
+    def _check_vjp_flags(who: str, params_grad: bool, obs_grad: bool) -> None:
+        if not params_grad and not obs_grad:
+            raise ValueError(f"{who}: params_grad and obs_grad are both False, nothing to compute")
+
+    def _vjp_outputs(self, n: int, params_grad: bool, obs_grad: bool):
+        need = int(_lib.lib().tma_policy_vjp_workspace_bytes(C.byref(self.dims), n))
+        if need <= 0:
+            _lib.check(_lib.TMA_ERR_INVALID)
+        if self._vjp_ws is None or self._vjp_ws.numel() < need:  # allocated lazily, kept: it grows to the chunk bound and stays there
+            self._vjp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        grad = torch.empty(self.n_trainable, dtype=torch.float32, device=self.device) if params_grad else None
+        grad_obs = torch.empty((n, self.obs_dim), dtype=torch.float32, device=self.device) if obs_grad else None
+        return grad, grad_obs
 
     def sync(self) -> None:
         """tma_policy_sync: rebuild everything derived from the trainable prefix ([out][in] copies, LDS / fragment images)."""
@@ -290,15 +344,15 @@ class HipActorCriticPolicy:
 
         After `parameters()` -- and while its leaf requires grad and torch.is_grad_enabled() -- the three outputs (the same kernels, the same
         bits) are nodes of a torch autograd graph: `loss.backward()` leaves the gradient with respect to the flat trainable vector in
-        `parameters()[0].grad` (one tma_policy_evaluate_actions_backward call).  Gradients with respect to `obs` are not built: an `obs` that
-        requires grad is a ValueError."""
+        `parameters()[0].grad`.  After `enable_obs_grad()` an `obs` that requires grad (a torch module in front of the policy, or the input of
+        a frozen policy: no `parameters()` needed, no leaf made) makes them nodes as well and receives its gradient in its own dtype and on its
+        own device; without it such an `obs` is a ValueError where the call is differentiable with respect to the parameters.  One
+        tma_policy_evaluate_actions_vjp call per backward, for exactly the gradients autograd asks for; first order only."""
         self._sync_if_stepped()
-        differentiable = self._leaf is not None and self._leaf.requires_grad and torch.is_grad_enabled()
-        if differentiable and isinstance(obs, torch.Tensor) and obs.requires_grad:
-            raise ValueError("evaluate_actions: gradients with respect to the observations are not built (obs.requires_grad is set)")
-        obs, actions = self._rows_actions(obs, actions)
+        differentiable, leaf, rows = self._graph_inputs("evaluate_actions", obs)
+        obs, actions = self._rows_actions(rows, actions)
         if differentiable:
-            return _EvaluateActions.apply(self._leaf, self, obs, actions)
+            return _EvaluateActions.apply(leaf, self, rows, actions)
         return self._evaluate_actions(obs, actions)
 
     def _rows_actions(self, obs: torch.Tensor, actions: torch.Tensor):
@@ -317,10 +371,13 @@ class HipActorCriticPolicy:
                                                           _lib.ptr(values), _lib.ptr(logp), _lib.ptr(entropy), _lib.stream_ptr(self.device)))
         return values, logp, entropy
 
-    def evaluate_actions_backward(self, obs: torch.Tensor, actions: torch.Tensor, g_values=None, g_logp=None, g_entropy=None) -> torch.Tensor:
-        """Vector-Jacobian product of evaluate_actions with respect to the trainable parameters (tma_policy_evaluate_actions_backward): the flat
-        gradient [n_trainable] of  sum_i g_values[i] V_i + g_logp[i] logp_i + g_entropy[i] H_i.  A cotangent may be None (zeros), not all three.
-        Deterministic: equal inputs give equal bits."""
+    def evaluate_actions_backward(self, obs: torch.Tensor, actions: torch.Tensor, g_values=None, g_logp=None, g_entropy=None, *,
+                                  params_grad: bool = True, obs_grad: bool = False):
+        """Vector-Jacobian product of evaluate_actions (tma_policy_evaluate_actions_vjp) of  sum_i g_values[i] V_i + g_logp[i] logp_i +
+        g_entropy[i] H_i:  with respect to the trainable parameters, the flat gradient [n_trainable] (params_grad, the default);  with respect to
+        the observations, float32 [n, obs_dim] (obs_grad);  the pair (parameters, observations) when both are asked for;  neither is a ValueError.
+        A cotangent may be None (zeros), not all three.  Deterministic: equal inputs give equal bits."""
+        self._check_vjp_flags("evaluate_actions_backward", params_grad, obs_grad)
         self._sync_if_stepped()
         obs, actions = self._rows_actions(obs, actions)
         n = obs.shape[0]
@@ -331,17 +388,11 @@ class HipActorCriticPolicy:
                     raise ValueError(f"{name} must have shape [{n}], got {list(c.shape)}")
                 c = c.detach().to(self.device, torch.float32).contiguous()
             cots.append(c)
-        L = _lib.lib()
-        need = int(L.tma_policy_vjp_workspace_bytes(C.byref(self.dims), n))
-        if need <= 0:
-            _lib.check(_lib.TMA_ERR_INVALID)
-        if self._vjp_ws is None or self._vjp_ws.numel() < need:  # allocated lazily, kept: it grows to the chunk bound and stays there
-            self._vjp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        grad = torch.empty(self.n_trainable, dtype=torch.float32, device=self.device)
-        _lib.check(L.tma_policy_evaluate_actions_backward(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), _lib.ptr(actions), n,
-                                                          _lib.ptr(cots[0]), _lib.ptr(cots[1]), _lib.ptr(cots[2]), _lib.ptr(grad),
-                                                          _lib.ptr(self._vjp_ws), self._vjp_ws.numel(), _lib.stream_ptr(self.device)))
-        return grad
+        grad, grad_obs = self._vjp_outputs(n, params_grad, obs_grad)
+        _lib.check(_lib.lib().tma_policy_evaluate_actions_vjp(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), _lib.ptr(actions), n,
+                                                              _lib.ptr(cots[0]), _lib.ptr(cots[1]), _lib.ptr(cots[2]), _lib.ptr(grad), _lib.ptr(grad_obs),
+                                                              _lib.ptr(self._vjp_ws), self._vjp_ws.numel(), _lib.stream_ptr(self.device)))
+        return (grad, grad_obs) if (params_grad and obs_grad) else (grad if params_grad else grad_obs)
 
     def head(self, obs: torch.Tensor):
         """(head, values), device tensors [n, act_dim] and [n]: the policy net's head before any distribution arithmetic -- the raw logits of a
@@ -349,16 +400,13 @@ class HipActorCriticPolicy:
         runs, so `values` carries act's bits and a Box head those of act(deterministic=True)'s actions).
 
         After `parameters()` -- and while its leaf requires grad and torch.is_grad_enabled() -- both outputs are nodes of a torch autograd graph
-        (one tma_policy_head_backward call), as evaluate_actions' are.  Gradients with respect to `obs` are not built: an `obs` that requires
-        grad is a ValueError."""
+        (one tma_policy_head_vjp call), as evaluate_actions' are -- and so they are, after `enable_obs_grad()`, where `obs` requires grad, which then
+        receives its gradient (no `parameters()` needed for that; without `enable_obs_grad()` the rule is evaluate_actions')."""
         self._sync_if_stepped()
-        differentiable = self._leaf is not None and self._leaf.requires_grad and torch.is_grad_enabled()
-        if differentiable and isinstance(obs, torch.Tensor) and obs.requires_grad:
-            raise ValueError("head: gradients with respect to the observations are not built (obs.requires_grad is set)")
-        obs = self._rows(obs.detach())
+        differentiable, leaf, rows = self._graph_inputs("head", obs)
         if differentiable:
-            return _Head.apply(self._leaf, self, obs)
-        return self._head(obs)
+            return _Head.apply(leaf, self, rows)
+        return self._head(rows)
 
     def _head(self, obs: torch.Tensor):
         n = obs.shape[0]
@@ -368,10 +416,12 @@ class HipActorCriticPolicy:
                                               _lib.stream_ptr(self.device)))
         return head, values
 
-    def head_backward(self, obs: torch.Tensor, g_head=None, g_values=None) -> torch.Tensor:
-        """Vector-Jacobian product of `head` with respect to the trainable parameters (tma_policy_head_backward): the flat gradient [n_trainable]
-        of  sum_ij g_head[i, j] head[i, j] + sum_i g_values[i] V_i.  A cotangent may be None (zeros), not both.  The log_std segment of a Box
-        policy comes back as zeros.  Deterministic: equal inputs give equal bits."""
+    def head_backward(self, obs: torch.Tensor, g_head=None, g_values=None, *, params_grad: bool = True, obs_grad: bool = False):
+        """Vector-Jacobian product of `head` (tma_policy_head_vjp) of  sum_ij g_head[i, j] head[i, j] + sum_i g_values[i] V_i:  the flat gradient
+        [n_trainable] (params_grad, the default; the log_std segment of a Box policy comes back as zeros), the gradient with respect to the
+        observations [n, obs_dim] (obs_grad), or the pair when both are asked for; neither is a ValueError.  A cotangent may be None (zeros),
+        not both.  Deterministic: equal inputs give equal bits."""
+        self._check_vjp_flags("head_backward", params_grad, obs_grad)
         self._sync_if_stepped()
         obs = self._rows(obs.detach())
         n = obs.shape[0]
@@ -382,16 +432,11 @@ class HipActorCriticPolicy:
                     raise ValueError(f"{name} must have shape {list(shape)}, got {list(c.shape)}")
                 c = c.detach().to(self.device, torch.float32).contiguous()
             cots.append(c)
-        L = _lib.lib()
-        need = int(L.tma_policy_vjp_workspace_bytes(C.byref(self.dims), n))
-        if need <= 0:
-            _lib.check(_lib.TMA_ERR_INVALID)
-        if self._vjp_ws is None or self._vjp_ws.numel() < need:  # (shared with evaluate_actions_backward)
-            self._vjp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        grad = torch.empty(self.n_trainable, dtype=torch.float32, device=self.device)
-        _lib.check(L.tma_policy_head_backward(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), n, _lib.ptr(cots[0]), _lib.ptr(cots[1]),
-                                              _lib.ptr(grad), _lib.ptr(self._vjp_ws), self._vjp_ws.numel(), _lib.stream_ptr(self.device)))
-        return grad
+        grad, grad_obs = self._vjp_outputs(n, params_grad, obs_grad)
+        _lib.check(_lib.lib().tma_policy_head_vjp(_lib.ptr(self.params), C.byref(self.dims), _lib.ptr(obs), n, _lib.ptr(cots[0]), _lib.ptr(cots[1]),
+                                                  _lib.ptr(grad), _lib.ptr(grad_obs), _lib.ptr(self._vjp_ws), self._vjp_ws.numel(),
+                                                  _lib.stream_ptr(self.device)))
+        return (grad, grad_obs) if (params_grad and obs_grad) else (grad if params_grad else grad_obs)
 
     def get_distribution(self, obs: torch.Tensor):
         """SB3's ActorCriticPolicy.get_distribution(obs): the action distribution of every row as a distributions.CategoricalDistribution /
