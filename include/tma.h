@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 222
+#define TMA_VERSION 223
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -561,12 +561,9 @@ typedef struct {
                                rewards[t] += gamma * V(terminal_obs[t]) of K consecutive steps in ONE launch over K*N rows
                                instead of one small launch per vector step */
 } tma_rollout_buffers;
-/* One launch advances every env by many vector steps ("fused chunk") for: 64-wide f32 policies on GridWorld / Push / Ball3D / WallJump /
- * Bicycle / Glider; 256-wide policies, bf16 or f32, on the Discrete tasks with up to 32 observations and on the Box-action tasks (Crawler /
- * Ant shapes; f32: up to 4096 envs, round 6).  Every other shape runs policy forward + env step launch by launch -- the same results bit for bit
- * (tests/test_ppo_gpu.py::test_native_rollout_equals_stepwise_composition); TMA_NO_WIDE_FUSED=1 / TMA_NO_CONT_F32_FUSED=1 force that path;
- * the 64-wide fused chunk runs eight waves per 16-env tile where every CU gets at most one tile at a time (fewer than 16 384 envs); TMA_ROLL4=1 runs it on
- * four (round 6's kernel), TMA_ROLL2=1 on two (round 5's) -- the same results bit for bit.
+/* One launch advances every env by many vector steps ("fused chunk") for the shapes of six kernel families; every other shape runs policy
+ * forward + env step launch by launch -- the same results bit for bit (tests/test_ppo_gpu.py::test_native_rollout_equals_stepwise_composition).
+ * Which family runs a shape, its precedence, thresholds and switches: DESIGN.md 4.3 (csrc/tma_rollout_plan.h; tma_debug_plan_rollout answers it).
  * deterministic != 0: actions are the distribution's mode (first maximal logit / Gaussian mean) instead of samples -- what SB3's
  * evaluate_policy(deterministic=True) asks of the policy (backend/mlagents/training.py:177-184,240-247); evaluation.py runs whole evaluation
  * chunks through this entry point and reads the finished episodes from the env's episode log. */
@@ -701,6 +698,17 @@ int tma_rollout_norm_plan(int task, const tma_policy_dims *d, int64_t N, int tra
 /* Test aid (ABI 219): the plan value the calling thread's last tma_rollout_collect_norm actually launched (PER_STEP also where a switch or an
  * env handle that is not reset kept it off the fused kernels). */
 int tma_debug_last_rollout_norm_path(void);
+/* The plan behind tma_rollout_collect / tma_rollout_collect_norm (ABI 223; host-only queries, no HIP call).
+ * tma_debug_plan_rollout: what the driver would run for (task, dims, N envs, reset env handle or not, terminal_obs_slots, norm) under this
+ * process's switches -- out6 = {family, waves per 16-env tile (H64 only, else 0), envs per tile or group (PER_STEP: 0), grid, block, LDS bytes of
+ * the chunk kernel (PER_STEP launches none: 1, 64, 0)}.  norm: NONE for tma_rollout_collect, TRAINING / FROZEN for tma_rollout_collect_norm.
+ * It refuses what the real calls refuse: NULL arguments, bad dims, an unknown task, N < 1.
+ * tma_debug_last_rollout_plan: out3 = {family, waves, rows} of the calling thread's last tma_rollout_collect / tma_rollout_collect_norm. */
+enum { TMA_ROLLOUT_FAMILY_PER_STEP = 0, TMA_ROLLOUT_FAMILY_H64 = 1, TMA_ROLLOUT_FAMILY_BF16_DISC = 2, TMA_ROLLOUT_FAMILY_BF16_BOX_TWO_NET = 3,
+       TMA_ROLLOUT_FAMILY_BF16_BOX_PI = 4, TMA_ROLLOUT_FAMILY_F32_DISC = 5, TMA_ROLLOUT_FAMILY_F32_BOX = 6 };
+enum { TMA_ROLLOUT_PLAN_NORM_NONE = 0, TMA_ROLLOUT_PLAN_NORM_TRAINING = 1, TMA_ROLLOUT_PLAN_NORM_FROZEN = 2 };
+int tma_debug_plan_rollout(int task, const tma_policy_dims *d, int64_t N, int is_reset, int terminal_obs_slots, int norm, int32_t *out6);
+int tma_debug_last_rollout_plan(int32_t *out3);
 
 #ifdef __cplusplus
 }

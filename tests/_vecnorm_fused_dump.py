@@ -18,6 +18,7 @@ The configuration is one JSON object on the command line:
   poison                           1: tma_debug_poison_lds(0) in front of every rollout -- NaNs in every LDS word a kernel does not write itself
   train                            1: behind the dumps PPO.train() and one whole learn() iteration; params_finite.npy
 usage: _vecnorm_fused_dump.py '<json>' out_dir"""
+import ctypes as C
 import json
 import os
 import sys
@@ -82,6 +83,9 @@ for r in range(2):
     np.save(os.path.join(out, f"r{r}_original_obs.npy"), env.get_original_obs())
     np.save(os.path.join(out, f"r{r}_original_reward.npy"), env.get_original_reward())
 np.save(os.path.join(out, "path.npy"), np.array(L.tma_debug_last_rollout_norm_path()))
+last_plan = (C.c_int32 * 3)()
+_lib.check(L.tma_debug_last_rollout_plan(last_plan))
+np.save(os.path.join(out, "plan.npy"), np.array(list(last_plan)))  # family, waves, rows (TMA_ROLLOUT_FAMILY_*)
 np.save(os.path.join(out, "slots.npy"), np.array(m._rb.terminal_obs_slots))
 if cfg.get("train"):
     m.train()

@@ -1,6 +1,7 @@
 """GPU tests of the actor-critic / PPO kernels against the torch-CPU restatement of SB3 2.9.0 (oracle/sb3_ref.py).
 Floating point: tolerances are written next to each check ("parity unpinned" boundary)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -346,6 +347,19 @@ def test_gae_flags_equals_sb3_layout(monkeypatch, T, N, scan):
     assert np.array_equal(adv2.cpu().numpy(), adv_ref) and np.array_equal(ret2.cpu().numpy(), ret_ref)
 
 
+# The rows of test_native_rollout_equals_stepwise_composition that are meant for a fused chunk kernel: in a process without a rollout switch the
+# driver must not have run them step by step (tests/test_rollout_plan_cpu.py: exactly the rows its table gives a fused family)
+FUSED_ROLLOUT_ROWS = [("gridworld", 64, 200, "f32"), ("push", 64, 200, "f32"), ("ball3d", 64, 200, "f32"), ("walljump", 64, 200, "f32"), ("gridworld", 64, 16400, "f32"),
+                      ("ball3d", 256, 200, "bf16"), ("gridworld", 256, 200, "bf16"), ("push", 256, 96, "bf16"), ("basic", 256, 40, "bf16"), ("walljump", 256, 64, "bf16"),
+                      ("ball3d", 256, 200, "f32"), ("basic", 256, 8, "f32"), ("basic", 256, 40, "f32"), ("basic", 256, 5, "f32"), ("gridworld", 256, 200, "f32"),
+                      ("gridworld", 256, 2100, "f32"), ("push", 256, 72, "f32"), ("walljump", 256, 64, "f32"), ("bicycle", 256, 40, "f32"), ("glider", 256, 40, "f32"),
+                      ("crawler", 256, 72, "bf16"), ("crawler", 256, 40, "f32"), ("ant", 256, 72, "bf16"), ("ant", 256, 40, "f32"), ("crawler", 256, 12, "f32"),
+                      ("bicycle", 64, 200, "f32"), ("glider", 64, 200, "f32"), ("bicycle", 256, 72, "bf16"), ("glider", 256, 72, "bf16"),
+                      ("brickbreak", 256, 8, "f32"), ("brickbreak", 256, 44, "f32")]
+ROLLOUT_SWITCHES = ("TMA_NO_WIDE_FUSED", "TMA_NO_CONT_F32_FUSED", "TMA_CONT_TWO_NET", "TMA_CONT_SERIAL", "TMA_WIDE_F32_ROWS", "TMA_WIDE_ROWS", "TMA_CONT_ROWS",
+                    "TMA_ROLL2", "TMA_ROLL4", "TMA_NO_NORM_FUSED")
+
+
 @pytest.mark.parametrize("task,hidden,N,mfma", [("gridworld", 64, 200, "f32"), ("push", 64, 200, "f32"), ("ball3d", 64, 200, "f32"), ("walljump", 64, 200, "f32"),
                                                 ("basic", 64, 200, "f32"), ("gridworld", 128, 200, "f32"), ("gridworld", 64, 16400, "f32"),
                                                 # the 256-wide bf16 fused chunk (register-resident layer-2 weights, 32-env row groups; 200 = a ragged last group)
@@ -374,12 +388,19 @@ def test_native_rollout_equals_stepwise_composition(task, hidden, N, mfma):
     from three_mlagents_amd.ppo import PPO
     from three_mlagents_amd.vec_env import HipVecEnv
 
-    # N = 200: two-wave fused kernel (one tile per block); N = 16400: >= 1024 tiles, the four-tiles-per-block single-wave kernel
+    # N = 200: the eight-wave fused kernel (one tile per block; Glider: the four-wave one); N = 16400: >= 1024 tiles, the four-tiles-per-block single-wave kernel
     T = {"ball3d": 230, "gridworld": 130, "walljump": 170, "basic": 60, "crawler": 40, "ant": 40, "bicycle": 110, "glider": 110, "brickbreak": 70}.get(task, 48)  # long enough to reach the time limit (timeout-bootstrap path)
     env = HipVecEnv(task, N, seed=3, ring_depth=16)
     model = PPO("MlpPolicy", env, n_steps=T, batch_size=256, n_epochs=1, seed=3, policy_kwargs={"net_arch": [hidden, hidden], "mfma_dtype": mfma})
     _lib.check(_lib.lib().tma_debug_poison_lds(0, _lib.stream_ptr()))  # NaNs in every LDS word the rollout kernels do not write themselves
     assert model.collect_rollouts()
+    # the driver ran what its plan names for this shape (csrc/tma_rollout_plan.h; tests/test_rollout_plan_cpu.py holds the plan to a table)
+    ran, plan = (C.c_int32 * 3)(), (C.c_int32 * 6)()
+    _lib.check(_lib.lib().tma_debug_last_rollout_plan(ran))
+    _lib.check(_lib.lib().tma_debug_plan_rollout(env.engine.task, C.byref(model.policy.dims), N, 1, model._rb.terminal_obs_slots, _lib.ROLLOUT_PLAN_NORM_NONE, plan))
+    assert tuple(ran) == tuple(plan[:3]), (tuple(ran), tuple(plan))
+    if (task, hidden, N, mfma) in FUSED_ROLLOUT_ROWS and not any(s in os.environ for s in ROLLOUT_SWITCHES):  # (a switch may send its rows step by step)
+        assert _lib.ROLLOUT_FAMILIES[ran[0]] != "PER_STEP", tuple(ran)
     b = {k: v.clone() for k, v in model.buf.items()}
     assert all(torch.isfinite(b[k]).all() for k in ("values", "log_probs", "rewards", "obs"))
     env2 = HipVecEnv(task, N, seed=3, ring_depth=16)

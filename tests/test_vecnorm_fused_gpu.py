@@ -26,6 +26,7 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PER_STEP, FUSED_DISC, FUSED_CONT = 0, 1, 2
+FAMILY_PER_STEP, FAMILY_F32_DISC, FAMILY_F32_BOX = 0, 5, 6  # include/tma.h TMA_ROLLOUT_FAMILY_*
 KEYS = ("obs", "actions", "log_probs", "values", "rewards", "terminated", "truncated", "last_values", "stats", "vn_returns", "original_obs", "original_reward")
 
 # name -> (configuration, plan value of the plain run).  Seed 3 was checked once with the per-step arm: B truncates (4 rows), E terminates (5).
@@ -93,6 +94,9 @@ def test_fused_chunk_equals_the_per_step_composition(name, dump):
     cfg, plan = CASES[name]
     fused, stepped = dump(name, True), dump(name, False)
     assert int(_load(fused, "path")) == plan and int(_load(stepped, "path")) == PER_STEP
+    # ... and the plan the driver recorded (csrc/tma_rollout_plan.h): one of the two f32 policy-only families on 8-env tiles, against the per-step composition
+    assert tuple(_load(fused, "plan")) == ({FUSED_DISC: FAMILY_F32_DISC, FUSED_CONT: FAMILY_F32_BOX}[plan], 0, 8)
+    assert tuple(_load(stepped, "plan")) == (FAMILY_PER_STEP, 0, 0)
     _assert_same_bits(fused, stepped, name)
     for r in range(2):
         for key in ("obs", "log_probs", "values", "rewards", "last_values", "stats", "vn_returns"):

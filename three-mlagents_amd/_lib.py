@@ -18,8 +18,11 @@ EV_SCRATCH_DOUBLES = 1536  # include/tma.h TMA_EV_SCRATCH_DOUBLES
 VECNORM_ONE_LAUNCH_MAX = 256  # include/tma.h TMA_VECNORM_ONE_LAUNCH_MAX
 GATHER_BLOCKS = 2048  # csrc/tma_workspace.h GATHER_BLOCKS: tma_rollout_gather's grid cap (workgroups of four waves); the tests size a case past it
 ROLLOUT_NORM_PER_STEP, ROLLOUT_NORM_FUSED_DISC_F32, ROLLOUT_NORM_FUSED_CONT_F32 = 0, 1, 2  # include/tma.h TMA_ROLLOUT_NORM_*: tma_rollout_norm_plan
+# include/tma.h TMA_ROLLOUT_FAMILY_* / TMA_ROLLOUT_PLAN_NORM_*: tma_debug_plan_rollout, tma_debug_last_rollout_plan
+ROLLOUT_FAMILIES = ("PER_STEP", "H64", "BF16_DISC", "BF16_BOX_TWO_NET", "BF16_BOX_PI", "F32_DISC", "F32_BOX")
+ROLLOUT_PLAN_NORM_NONE, ROLLOUT_PLAN_NORM_TRAINING, ROLLOUT_PLAN_NORM_FROZEN = 0, 1, 2
 
-_vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_double
+_vp, _i32, _i64, _u32, _f64 =C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_double
 
 
 
@@ -168,6 +171,8 @@ SIGNATURES = {
     "tma_rollout_collect_norm": (_i32, [_vp, _vp, _vp, _pd, C.POINTER(RolloutBuffers), _i32, _i32, _i32, _u32, _u32, _u32, _f64, _i32, _i32, _i32, _vp]),
     "tma_rollout_norm_plan": (_i32, [_i32, _pd, _i64, _i32]),
     "tma_debug_last_rollout_norm_path": (_i32, []),
+    "tma_debug_plan_rollout": (_i32, [_i32, _pd, _i64, _i32, _i32, _i32, C.POINTER(_i32)]),
+    "tma_debug_last_rollout_plan": (_i32, [C.POINTER(_i32)]),
 }
 
 # tma_allreduce_fn (include/tma.h): int (*)(void *ctx, float *buffer, int64_t count)

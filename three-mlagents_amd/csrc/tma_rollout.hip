@@ -2268,23 +2268,58 @@ __global__ __launch_bounds__(256, 1) void rollout_chunk_wide_cont_f32_kernel(Env
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The host driver: tma_rollout_plan.h decides family and geometry, one launcher per family launches the plan, run_chunks is the
+// one chunk loop, collect_per_step the one per-step composition, last_values_tail the one tail.
+// ------------------------------------------------------------------------------------------
+// dynamic LDS the launchers pass: the totals of what each kernel carves for itself
+constexpr int h64_chunk_lds_bytes(int waves) {
+    // both nets' forward images, the observation / terminal-observation tiles, bootstrap scratch; four and eight waves: their exchange buffers
+    const int base = 2 * FWD_IMG + 4 * 16 * CH_LDX + 32 + 32 + 4;
+    return (waves == 8   ? base + 2048 + 1024 + 2048 + 1024 + 1024 + 512 + 512 + 96
+            : waves == 4 ? base + 1024 + 512 + 512 + 512 + 96
+            : waves == 2 ? base
+                         : 2 * FWD_IMG + 4 * 2 * 16 * CH_LDX) * 4;  // one wave per tile, four tiles a workgroup
+}
 template <class T>
-static int launch_chunk_wide_cont_f32(tma_env *env, const float *params, const PLayout &L, const ChunkPtrs &b, float *term_obs, int t0, int n,
-                                      uint32_t rng_seed, uint32_t rng_step0, int det, hipStream_t s, const VnChunk *vn = nullptr) {
-    if constexpr (T::FUSED_ROLLOUT && T::NACT == 0 && T::ADIM <= 32 && !T::USES_MT && T::OBS <= 192) {
-        if (vn) {  // a VecNormalize step in the step loop: its float64 statistics and scratch behind the float images
+constexpr int wide_f32_lds_bytes(int rows) {  // rollout_chunk_wide_f32_kernel: the 8-env form, else X, h1, h2 of 16 rows
+    return rows == 8 ? wide_f32_lds_floats(((T::OBS + 3) & ~3) + 4) * 4 : 16 * (((T::OBS + 3) & ~3) + 2 + 2 * 258) * 4;
+}
+
+#include "tma_rollout_plan.h"
+
+static_assert(h64_chunk_lds_bytes(8) <= LDS_LIMIT, "LDS of a CU");
+
+// what one chunk launch takes besides the plan
+struct ChunkCall {
+    const EnvView &v;
+    const float *params;
+    const PLayout &L;
+    const ChunkPtrs &b;
+    float *term_obs;
+    int t0, n;
+    uint32_t rng_seed, rng_step0;
+    float gamma;
+    int det;
+    hipStream_t s;
+    const VnChunk *vn;  // norm_in_chunk: the kernel argument of the normalised form
+};
+#define TMA_OPT_IN_LDS(k, bytes) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
+
+template <class T>
+static int launch_f32_box(const RolloutPlan &p, const ChunkCall &c) {
+    if constexpr (wide_box_task<T>) {
+        const dim3 grid((unsigned)p.grid), block(p.block);
+        if (c.vn) {
             static_assert(WideContF32Lds<T>::floats() % 2 == 0, "the doubles behind the float images are 8-byte aligned");
             auto k = rollout_chunk_wide_cont_f32_kernel<T, true>;
-            const int smem = WideContF32Lds<T>::floats() * 4 + vn_chunk_lds_doubles(T::OBS) * 8;
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            k<<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, *vn);
-            TMA_LAUNCH_CHECK();
-            return TMA_OK;
+            TMA_OPT_IN_LDS(k, p.lds);
+            k<<<grid, block, p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.term_obs, c.t0, c.n, c.rng_seed, c.rng_step0, c.det, *c.vn);
+        } else {
+            auto k = rollout_chunk_wide_cont_f32_kernel<T>;
+            TMA_OPT_IN_LDS(k, p.lds);
+            k<<<grid, block, p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.term_obs, c.t0, c.n, c.rng_seed, c.rng_step0, c.det, VnNone{});
         }
-        auto k = rollout_chunk_wide_cont_f32_kernel<T>;
-        const int smem = WideContF32Lds<T>::floats() * 4;
-        TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        k<<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, VnNone{});
         TMA_LAUNCH_CHECK();
         return TMA_OK;
     } else {
@@ -2293,34 +2328,21 @@ static int launch_chunk_wide_cont_f32(tma_env *env, const float *params, const P
 }
 
 template <class T>
-static int launch_chunk_wide_f32(tma_env *env, const float *params, const PLayout &L, const ChunkPtrs &b, float *term_obs, int t0, int n, uint32_t rng_seed,
-                                 uint32_t rng_step0, int det, hipStream_t s, const VnChunk *vn = nullptr) {
-    // (round 6: BrickBreak -- 45 observations, one of the reference's PPO-default tasks -- on the 8-env tiles, whose layer-1 weights are one register per k)
-    if constexpr ((T::FUSED_ROLLOUT && T::OBS <= 32 && T::NACT > 0) || T::ID == TMA_TASK_BRICKBREAK) {
-        // tiles of eight envs while they give every env its own block round (up to 2048 envs); TMA_WIDE_F32_ROWS=16 / 8 forces a form (A/B, tests)
-        static const int force = getenv("TMA_WIDE_F32_ROWS") ? atoi(getenv("TMA_WIDE_F32_ROWS")) : 0;
-        const bool m8 = force ? force == 8 : env->v.N <= 2048;
-        if (m8) {
+static int launch_f32_disc(const RolloutPlan &p, const ChunkCall &c) {
+    if constexpr (wide_f32_task<T>) {
+        const dim3 grid((unsigned)p.grid), block(p.block);
+        if (p.rows == 8) {
             constexpr int ldx = ((T::OBS + 3) & ~3) + 4;
-            const int smem = wide_f32_lds_floats(ldx) * 4;  // X, h1, h2 (16 rows), W3 rows, logits
-            if (vn) {  // a VecNormalize step in the step loop: its float64 statistics and scratch behind the float images
-                static_assert(wide_f32_lds_floats(ldx) % 2 == 0, "the doubles behind the float images are 8-byte aligned");
-                const int smem_n = smem + vn_chunk_lds_doubles(T::OBS) * 8;
-                static_assert(wide_f32_lds_floats(ldx) * 4 + vn_chunk_lds_doubles(T::OBS) * 8 <= 64 * 1024, "no opt-in for the LDS");
-                rollout_chunk_wide_f32_kernel<T, 8, true><<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem_n, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, *vn);
-                TMA_LAUNCH_CHECK();
-                return TMA_OK;
-            }
-            rollout_chunk_wide_f32_kernel<T, 8><<<dim3((unsigned)ceil_div(env->v.N, 8)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, VnNone{});
+            static_assert(wide_f32_lds_floats(ldx) % 2 == 0, "the doubles behind the float images are 8-byte aligned");
+            static_assert(wide_f32_lds_floats(ldx) * 4 + vn_chunk_lds_doubles(T::OBS) * 8 <= LDS_OPT_IN, "no opt-in for the LDS");
+            if (c.vn) rollout_chunk_wide_f32_kernel<T, 8, true><<<grid, block, p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.term_obs, c.t0, c.n, c.rng_seed, c.rng_step0, c.det, *c.vn);
+            else rollout_chunk_wide_f32_kernel<T, 8><<<grid, block, p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.term_obs, c.t0, c.n, c.rng_seed, c.rng_step0, c.det, VnNone{});
             TMA_LAUNCH_CHECK();
             return TMA_OK;
         }
-        if (vn) return fail(TMA_ERR_INVALID, "fused f32 wide rollout: the normalised form runs on 8-env tiles only");
+        if (c.vn) return fail(TMA_ERR_INVALID, "fused f32 wide rollout: the normalised form runs on 8-env tiles only");
         if constexpr (T::OBS <= 32) {
-            auto k = rollout_chunk_wide_f32_kernel<T, 16>;
-            constexpr int ldx = ((T::OBS + 3) & ~3) + 2;
-            const int smem = 16 * (ldx + 2 * 258) * 4;
-            k<<<dim3((unsigned)ceil_div(env->v.N, 16)), dim3(256), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det, VnNone{});
+            rollout_chunk_wide_f32_kernel<T, 16><<<grid, block, p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.term_obs, c.t0, c.n, c.rng_seed, c.rng_step0, c.det, VnNone{});
         } else {
             return fail(TMA_ERR_INVALID, "fused f32 wide rollout: this task runs on 8-env tiles only (up to 2048 envs)");
         }
@@ -2332,23 +2354,11 @@ static int launch_chunk_wide_f32(tma_env *env, const float *params, const PLayou
 }
 
 template <class T>
-static int launch_chunk_wide_cont_pi(tma_env *env, const float *params, const PLayout &L, const ChunkPtrs &b, float *term_obs, int t0, int n,
-                                     uint32_t rng_seed, uint32_t rng_step0, int det, hipStream_t s) {
-    if constexpr (T::FUSED_ROLLOUT && T::NACT == 0 && T::ADIM <= 32 && !T::USES_MT && T::OBS <= 192) {
-        // 16 envs per block while that still leaves CUs idle at 32 (up to 4096 envs: <= 256 blocks of 16), else 32 (TMA_CONT_ROWS=16/32 forces one)
-        static const int forced = getenv("TMA_CONT_ROWS") ? atoi(getenv("TMA_CONT_ROWS")) : 0;
-        const bool rows16 = forced ? forced == 16 : env->v.N <= 4096;
-        if (rows16) {
-            auto k = rollout_chunk_wide_cont_pi_kernel<T, 16>;
-            const int smem = WideContPiLds<T, 16>::bytes();
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            k<<<dim3((unsigned)ceil_div(env->v.N, 16)), dim3(512), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det);
-        } else {
-            auto k = rollout_chunk_wide_cont_pi_kernel<T, 32>;
-            const int smem = WideContPiLds<T, 32>::bytes();
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            k<<<dim3((unsigned)ceil_div(env->v.N, 32)), dim3(512), smem, s>>>(env->v, params, L, b, term_obs, t0, n, rng_seed, rng_step0, det);
-        }
+static int launch_bf16_box_pi(const RolloutPlan &p, const ChunkCall &c) {
+    if constexpr (wide_box_task<T>) {
+        auto k = p.rows == 16 ? rollout_chunk_wide_cont_pi_kernel<T, 16> : rollout_chunk_wide_cont_pi_kernel<T, 32>;
+        TMA_OPT_IN_LDS(k, p.lds);
+        k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.term_obs, c.t0, c.n, c.rng_seed, c.rng_step0, c.det);
         TMA_LAUNCH_CHECK();
         return TMA_OK;
     } else {
@@ -2357,30 +2367,11 @@ static int launch_chunk_wide_cont_pi(tma_env *env, const float *params, const PL
 }
 
 template <class T>
-static int launch_chunk_wide(tma_env *env, const float *params, const PLayout &L, const ChunkPtrs &b, int t0, int n, uint32_t rng_seed,
-                             uint32_t rng_step0, float gamma, int det, hipStream_t s) {
-    if constexpr (T::FUSED_ROLLOUT && T::OBS <= 32 && T::NACT > 0) {
-        // 16 envs per block while 32 would leave CUs idle (up to 4096 envs: <= 256 blocks of 16), else 32 (TMA_WIDE_ROWS=16/32 forces one)
-        static const int forced = getenv("TMA_WIDE_ROWS") ? atoi(getenv("TMA_WIDE_ROWS")) : 0;
-        const bool rows16 = forced ? forced == 16 : env->v.N <= 4096;
-        if (rows16) {
-            auto k = rollout_chunk_wide_bf_kernel<T, 16>;
-            const int smem = WideLds<16>::bytes();
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            k<<<dim3((unsigned)ceil_div(env->v.N, 16)), dim3(512), smem, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
-        } else {
-            auto k = rollout_chunk_wide_bf_kernel<T, 32>;
-            const int smem = WideLds<32>::bytes();
-            TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            k<<<dim3((unsigned)ceil_div(env->v.N, 32)), dim3(512), smem, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
-        }
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
-    } else if constexpr (T::FUSED_ROLLOUT && T::NACT == 0 && T::ADIM <= 32 && !T::USES_MT && ((T::OBS + 31) / 32) % 2 == 0) {
-        auto k = rollout_chunk_wide_cont_kernel<T>;
-        const int smem = WideContLds<T>::bytes();
-        TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        k<<<dim3((unsigned)ceil_div(env->v.N, 32)), dim3(512), smem, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
+static int launch_bf16_disc(const RolloutPlan &p, const ChunkCall &c) {
+    if constexpr (wide_disc_task<T>) {
+        auto k = p.rows == 16 ? rollout_chunk_wide_bf_kernel<T, 16> : rollout_chunk_wide_bf_kernel<T, 32>;
+        TMA_OPT_IN_LDS(k, p.lds);
+        k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.t0, c.n, c.rng_seed, c.rng_step0, c.gamma, c.det);
         TMA_LAUNCH_CHECK();
         return TMA_OK;
     } else {
@@ -2388,75 +2379,87 @@ static int launch_chunk_wide(tma_env *env, const float *params, const PLayout &L
     }
 }
 
-// waves per 16-env tile of the calling thread's last 64-wide fused chunk launch (tma_debug_last_rollout_waves)
+template <class T>
+static int launch_bf16_box_two_net(const RolloutPlan &p, const ChunkCall &c) {
+    if constexpr (two_net_task<T>) {
+        auto k = rollout_chunk_wide_cont_kernel<T>;
+        TMA_OPT_IN_LDS(k, p.lds);
+        k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.t0, c.n, c.rng_seed, c.rng_step0, c.gamma, c.det);
+        TMA_LAUNCH_CHECK();
+        return TMA_OK;
+    } else {
+        return fail(TMA_ERR_INVALID, "no fused wide rollout for this task");
+    }
+}
+
+// eight waves: one tile of a net per wave, every activation formed once (round 8); four: each net on two waves (round 6); two: the policy and
+// the value net of a tile on a wave each; one: four tiles a workgroup (from 1024 tiles on; below, one tile per workgroup so all 256 CUs take part)
+template <class T>
+static int launch_h64(const RolloutPlan &p, const ChunkCall &c) {
+    if constexpr (h64_task<T>) {
+        auto k = p.waves == 4 ? rollout_chunk4_h64_kernel<T> : (p.waves == 2 ? rollout_chunk2_h64_kernel<T> : rollout_chunk_h64_kernel<T>);
+        if constexpr (roll8_task<T>::value) {
+            if (p.waves == 8) k = rollout_chunk8_h64_kernel<T>;
+        }
+        if (p.lds > LDS_OPT_IN) TMA_OPT_IN_LDS(k, p.lds);
+        k<<<dim3((unsigned)p.grid), dim3(p.block), p.lds, c.s>>>(c.v, c.params, c.L, c.b, c.t0, c.n, c.rng_seed, c.rng_step0, c.gamma, c.det);
+        TMA_LAUNCH_CHECK();
+        return TMA_OK;
+    } else {
+        return fail(TMA_ERR_INVALID, "no fused 64-wide rollout for this task");
+    }
+}
+
+template <class T>
+static int launch_family(const RolloutPlan &p, const ChunkCall &c) {
+    switch (p.family) {
+    case RolloutFamily::H64: return launch_h64<T>(p, c);
+    case RolloutFamily::Bf16Disc: return launch_bf16_disc<T>(p, c);
+    case RolloutFamily::Bf16BoxTwoNet: return launch_bf16_box_two_net<T>(p, c);
+    case RolloutFamily::Bf16BoxPi: return launch_bf16_box_pi<T>(p, c);
+    case RolloutFamily::F32Disc: return launch_f32_disc<T>(p, c);
+    case RolloutFamily::F32Box: return launch_f32_box<T>(p, c);
+    case RolloutFamily::PerStep: break;
+    }
+    return fail(TMA_ERR_INVALID, "the per-step composition launches no chunk");
+}
+
+// the switches, read once per process: the one getenv site of the rollout driver
+static const RolloutSwitches &read_rollout_switches() {
+    static const RolloutSwitches sw = [] {
+        auto get = [](const char *name) { return getenv(name); };
+        auto set = [&](const char *name) { return get(name) != nullptr; };  // (a flag is on whenever it is set, to any value)
+        auto num = [&](const char *name) { return get(name) ? atoi(get(name)) : 0; };
+        RolloutSwitches w{};
+        w.no_wide_fused = set("TMA_NO_WIDE_FUSED"), w.no_cont_f32 = set("TMA_NO_CONT_F32_FUSED"), w.no_norm_fused = set("TMA_NO_NORM_FUSED");
+        w.cont_two_net = set("TMA_CONT_TWO_NET"), w.cont_serial = set("TMA_CONT_SERIAL"), w.roll2 = set("TMA_ROLL2"), w.roll4 = set("TMA_ROLL4");
+        w.wide_f32_rows = num("TMA_WIDE_F32_ROWS"), w.wide_rows = num("TMA_WIDE_ROWS"), w.cont_rows = num("TMA_CONT_ROWS");
+        return w;
+    }();
+    return sw;
+}
+
+// the calling thread's last plan (tma_debug_last_rollout_plan), the waves of its last H64 plan (tma_debug_last_rollout_waves) and what its last
+// tma_rollout_collect_norm ran (tma_debug_last_rollout_norm_path)
+static thread_local RolloutPlan g_last_plan;
 static thread_local int g_roll_waves = 0;
-// the path the calling thread's last tma_rollout_collect_norm took (tma_debug_last_rollout_norm_path)
 static thread_local int g_norm_path = TMA_ROLLOUT_NORM_PER_STEP;
 
-// WHICH path tma_rollout_collect_norm takes for a shape: a pure host function (no HIP call, no global, no environment read), in the manner of
-// tma_policy_plan.h.  Fused exactly where tma_rollout_collect would run rollout_chunk_wide_f32_kernel on its 8-env tiles, or
-// rollout_chunk_wide_cont_f32_kernel, for this (task, dims) -- and, while the statistics move, the vector is ONE tile: the moments of a step
-// are then one workgroup's work.  Frozen statistics: rows are independent, any number of tiles up to the kernel's own cap.
-constexpr int64_t NORM_FUSED_TRAIN_MAX = 8, NORM_FUSED_DISC_MAX = 2048, NORM_FUSED_CONT_MAX = 4096;
-inline int plan_rollout_norm(int task, const PLayout &L, const tma_policy_dims &d, int64_t N, bool training) {
-    if (L.act != ACT_TANH || L.bf16 || L.img_pi >= 0 || L.H != 256 || d.obs_dim != tma_task_obs_dim(task)) return TMA_ROLLOUT_NORM_PER_STEP;
-    const bool box_task = task == TMA_TASK_CRAWLER || task == TMA_TASK_ANT;
-    const bool task_fused = dispatch_task(task, [](auto t) { return decltype(t)::FUSED_ROLLOUT ? 1 : 0; }) == 1;
-    const bool disc = !d.continuous && !box_task && d.act_dim == tma_task_num_actions(task) && ((task_fused && d.obs_dim <= 32) || task == TMA_TASK_BRICKBREAK);
-    const bool cont = d.continuous && box_task && d.act_dim == tma_task_act_dim(task);
-    if (disc && N <= (training ? NORM_FUSED_TRAIN_MAX : NORM_FUSED_DISC_MAX)) return TMA_ROLLOUT_NORM_FUSED_DISC_F32;
-    if (cont && N <= (training ? NORM_FUSED_TRAIN_MAX : NORM_FUSED_CONT_MAX)) return TMA_ROLLOUT_NORM_FUSED_CONT_F32;
-    return TMA_ROLLOUT_NORM_PER_STEP;
-}
-
-// a task whose env step needs more registers than a wave of an eight-wave workgroup has (256) stays on the four-wave kernel: T::ROLL8 = false
-template <class T, class = void>
-struct roll8_task : std::true_type {};
-template <class T>
-struct roll8_task<T, std::enable_if_t<!T::ROLL8>> : std::false_type {};
-
-template <class T>
-static int launch_chunk(tma_env *env, const float *params, const PLayout &L, const ChunkPtrs &b, int t0, int n, uint32_t rng_seed, uint32_t rng_step0,
-                        float gamma, int det, hipStream_t s) {
-    const int64_t tiles = ceil_div(env->v.N, 16);
-    const int wpb = tiles >= 1024 ? 4 : 1;  // BASELINE shape (256 tiles): one wave per block so all 256 CUs take part
-    const int smem = (2 * FWD_IMG + wpb * 2 * 16 * CH_LDX) * 4;
-    static const bool roll2 = getenv("TMA_ROLL2") != nullptr;  // A/B switch: the two-wave kernel
-    static const bool roll4 = getenv("TMA_ROLL4") != nullptr;  // A/B switch: the four-wave kernel
-    g_roll_waves = wpb != 1 ? 1 : (roll2 ? 2 : (roll4 ? 4 : 8));
-    if constexpr (!roll8_task<T>::value) {
-        if (g_roll_waves == 8) g_roll_waves = 4;
-    } else if (wpb == 1 && !roll2 && !roll4) {  // one tile per CU: one tile of a net per wave, every activation formed once (round 8)
-        const int smem8 = (2 * FWD_IMG + 4 * 16 * CH_LDX + 32 + 32 + 4 + 2048 + 1024 + 2048 + 1024 + 1024 + 512 + 512 + 96) * 4;
-        static_assert((2 * FWD_IMG + 4 * 16 * CH_LDX + 32 + 32 + 4 + 2048 + 1024 + 2048 + 1024 + 1024 + 512 + 512 + 96) * 4 <= 160 * 1024, "LDS of a CU");
-        auto k8 = rollout_chunk8_h64_kernel<T>;
-        if (smem8 > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, smem8));
-        k8<<<dim3((unsigned)tiles), dim3(512), smem8, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
-    }
-    if (wpb == 1 && !roll2) {  // each net on two waves (round 6)
-        const int smem4 = (2 * FWD_IMG + 4 * 16 * CH_LDX + 32 + 32 + 4 + 1024 + 512 + 512 + 512 + 96) * 4;
-        auto k4 = rollout_chunk4_h64_kernel<T>;
-        if (smem4 > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k4), hipFuncAttributeMaxDynamicSharedMemorySize, smem4));
-        k4<<<dim3((unsigned)tiles), dim3(256), smem4, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
-    }
-    if (wpb == 1) {  // one tile per CU: split the policy and the value net of a tile over two waves
-        const int smem2 = (2 * FWD_IMG + 4 * 16 * CH_LDX + 32 + 32 + 4) * 4;
-        auto k2 = rollout_chunk2_h64_kernel<T>;
-        if (smem2 > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, smem2));
-        k2<<<dim3((unsigned)tiles), dim3(128), smem2, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
-        TMA_LAUNCH_CHECK();
-        return TMA_OK;
-    }
-    auto k = rollout_chunk_h64_kernel<T>;
-    if (smem > 64 * 1024) TMA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    k<<<dim3((unsigned)ceil_div(tiles, wpb)), dim3(64 * wpb), smem, s>>>(env->v, params, L, b, t0, n, rng_seed, rng_step0, gamma, det);
-    TMA_LAUNCH_CHECK();
-    return TMA_OK;
-}
+// the arguments of the two entry points (vn: tma_rollout_collect_norm's handle, else null)
+struct RolloutCall {
+    tma_env *env;
+    tma_vecnorm *vn;
+    int training;
+    const float *params;
+    const tma_policy_dims *d;
+    const tma_rollout_buffers *b;
+    PLayout L;
+    int t_begin, t_end, T;
+    uint32_t rng_seed, rng_step0, env_offset;
+    double gamma;
+    int compute_last_values, det;
+    void *stream;
+};
 
 // the kernel argument of a normalised chunk: the handle's flags, constants and state as vn_step sets them for its one-launch kernel
 static VnChunk vn_chunk_args(const tma_vecnorm *h, int training) {
@@ -2474,26 +2477,25 @@ static VnChunk vn_chunk_args(const tma_vecnorm *h, int training) {
     return c;
 }
 
-// Box-action tasks (Crawler / Ant shapes): policy-only fused chunk + ONE batched value launch + ONE batched bootstrap launch per chunk of up to
-// terminal_obs_slots steps.  f32: rollout_chunk_wide_cont_f32_kernel, else the bf16 kernel.  vn != nullptr (f32 only): the normalised form of the
-// chunk kernel on that handle's statistics (tma_rollout_collect_norm); the value and bootstrap launches then read normalised rows.
-static int collect_chunks_cont(tma_env *env, tma_vecnorm *vn, int training, bool fused_cont_f32, const float *params, const tma_policy_dims *d,
-                               const tma_rollout_buffers *b, const PLayout &L, int t_begin, int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, double gamma,
-                               int compute_last_values, int det, void *stream) {
-    const int64_t N = b->N;
+// The one chunk loop: a chunk runs up to the next reset-ring refill.  batched_value (the policy-only families): ONE batched value launch and ONE
+// batched bootstrap launch per chunk of up to terminal_obs_slots steps.  overlap: the chunk kernel holds the registers of N / 16 (or N / 32) CUs
+// and nothing of the others, and the value pass of chunk c depends only on the observations chunk c left behind -- so it runs on a SIDE stream
+// behind an event on chunk c, beside the chunk kernel of chunk c + 1 on the CUs that one leaves idle; the terminal-observation slots are split
+// in two halves used alternately, so that chunk c + 1 does not overwrite what the bootstrap of chunk c still reads.  The call returns with
+// `stream` waiting for the side stream.  norm_in_chunk: the normalised form of the kernel on the handle's statistics; the value and bootstrap
+// launches then read normalised rows (and touch nothing of the handle).
+static int run_chunks(const RolloutCall &c, const RolloutPlan &p) {
+    tma_env *env = c.env;
+    const tma_rollout_buffers *b = c.b;
+    tma_vecnorm *vn = p.norm_in_chunk ? c.vn : nullptr;
+    int rc = vn ? vn_ensure(vn) : TMA_OK;
+    if (rc) return rc;
     TMA_HIP(hipSetDevice(env->device));
-    ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
-    const int D = d->obs_dim;
-    // The chunk kernel holds the registers of N / 16 (or N / 32) CUs and nothing of the others; the value pass of chunk c depends only on the
-    // observations chunk c left behind.  So it runs on a SIDE stream behind an event on chunk c, beside the chunk kernel of chunk c + 1 on the
-    // CUs that one leaves idle; the terminal-observation slots are split in two halves used alternately, so that chunk c + 1 does not overwrite
-    // what the bootstrap of chunk c still reads.  The call returns with `stream` waiting for the side stream.  (TMA_CONT_SERIAL=1: one stream.)
-    static const bool serial = getenv("TMA_CONT_SERIAL") != nullptr;
-    const int slots = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
-    const bool overlap = !serial && slots >= 2;
-    const int K = overlap ? slots / 2 : slots;
-    hipStream_t mainS = (hipStream_t)stream, sideS = mainS;
-    if (overlap) {
+    const int64_t N = b->N;
+    const int D = c.d->obs_dim, slots = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1, K = p.overlap ? slots / 2 : slots;
+    const ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
+    hipStream_t mainS = (hipStream_t)c.stream, sideS = mainS;
+    if (p.overlap) {
         if (!env->side) {
             TMA_HIP(hipStreamCreateWithFlags(&env->side, hipStreamNonBlocking));
             TMA_HIP(hipEventCreateWithFlags(&env->ev_chunk, hipEventDisableTiming));
@@ -2502,88 +2504,96 @@ static int collect_chunks_cont(tma_env *env, tma_vecnorm *vn, int training, bool
         }
         sideS = env->side;
     }
-    int t = t_begin, half = 0;
+    int t = c.t_begin, half = 0;
     bool used[2] = {false, false};  // ev_side[h] has been recorded behind a bootstrap that reads half h
-    while (t < t_end) {
+    while (t < c.t_end) {
         int left = 0;
-        int rc = tma_env_steps_until_refill(env, &left);
+        rc = tma_env_steps_until_refill(env, &left);
         if (rc) return rc;
-        int n = left < (t_end - t) ? left : (t_end - t);
-        if (n > K) n = K;  // one terminal-observation slot per step of the chunk
-        float *tobs = b->terminal_obs + (overlap ? (int64_t)half * K * N * D : 0);
-        if (overlap && used[half])  // the half about to be rewritten was read by the bootstrap launched two chunks ago
+        int n = left < (c.t_end - t) ? left : (c.t_end - t);
+        if (p.batched_value && n > K) n = K;  // one terminal-observation slot per step of the chunk
+        float *tobs = b->terminal_obs + (p.overlap ? (int64_t)half * K * N * D : 0);
+        if (used[half])  // the half about to be rewritten was read by the bootstrap launched two chunks ago
             TMA_HIP(hipStreamWaitEvent(mainS, env->ev_side[half], 0));
-        const VnChunk vc = vn ? vn_chunk_args(vn, training) : VnChunk{};
-        rc = dispatch_task(env->task, [&](auto task) {
-            using TT = decltype(task);
-            if (fused_cont_f32) return launch_chunk_wide_cont_f32<TT>(env, params, L, cp, tobs, t, n, rng_seed, rng_step0, det, mainS, vn ? &vc : nullptr);
-            return launch_chunk_wide_cont_pi<TT>(env, params, L, cp, tobs, t, n, rng_seed, rng_step0, det, mainS);
-        });
+        const VnChunk vc = vn ? vn_chunk_args(vn, c.training) : VnChunk{};
+        const ChunkCall cc{env->v, c.params, c.L, cp, tobs, t, n, c.rng_seed, c.rng_step0, (float)c.gamma, c.det, mainS, vn ? &vc : nullptr};
+        rc = dispatch_task(env->task, [&](auto task) { return launch_family<decltype(task)>(p, cc); });
         if (rc) return rc;
         if (vn && vc.stats_out) vn->cur ^= 1;  // the chunk left its statistics in the handle's other buffer
-        if (overlap) {
+        if (p.overlap) {
             TMA_HIP(hipEventRecord(env->ev_chunk, mainS));
             TMA_HIP(hipStreamWaitEvent(sideS, env->ev_chunk, 0));
         }
-        rc = tma_policy_values(params, d, b->obs + (int64_t)t * N * D, (int64_t)n * N, b->values + (int64_t)t * N, sideS);
-        if (rc) return rc;
-        rc = tma_policy_bootstrap(params, d, tobs, b->truncated + (int64_t)t * N, (int64_t)n * N, gamma, b->rewards + (int64_t)t * N, sideS);
-        if (rc) return rc;
-        if (overlap) {
+        if (p.batched_value) {
+            rc = tma_policy_values(c.params, c.d, b->obs + (int64_t)t * N * D, (int64_t)n * N, b->values + (int64_t)t * N, sideS);
+            if (rc) return rc;
+            rc = tma_policy_bootstrap(c.params, c.d, tobs, b->truncated + (int64_t)t * N, (int64_t)n * N, c.gamma, b->rewards + (int64_t)t * N, sideS);
+            if (rc) return rc;
+        }
+        if (p.overlap) {
             TMA_HIP(hipEventRecord(env->ev_side[half], sideS));
             used[half] = true;
             half ^= 1;
         }
-        rc = tma_env_internal_after_steps(env, n, stream);
+        rc = tma_env_internal_after_steps(env, n, c.stream);
         if (rc) return rc;
         t += n;
     }
     for (int h = 0; h < 2; h++)
-        if (overlap && used[h]) TMA_HIP(hipStreamWaitEvent(mainS, env->ev_side[h], 0));
-    if (compute_last_values && t_end == T) {
-        if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-        return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
+        if (used[h]) TMA_HIP(hipStreamWaitEvent(mainS, env->ev_side[h], 0));
+    return TMA_OK;
+}
+
+// The one per-step composition: policy forward -> env step (-> VecNormalize step where c.vn) -> timeout bootstrap, launch by launch.
+static int collect_per_step(const RolloutCall &call) {
+    const RolloutCall c = call;  // (a local copy, which the loop's launches cannot alias: its fields stay in registers)
+    const tma_policy_dims *d = c.d;
+    const tma_rollout_buffers *b = c.b;
+    const int64_t N = b->N;
+    const int D = d->obs_dim, A = d->continuous ? d->act_dim : 1, act_kind = d->continuous ? TMA_ACT_F32 : TMA_ACT_I32;
+    const size_t act_elem = d->continuous ? sizeof(float) : sizeof(int32_t);
+    const int K = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
+    // K == 1, sampled actions: the timeout bootstrap of step t-1 (terminal_obs still holds step t-1's, normalised where c.vn) rides in the policy
+    // launch of step t.  Otherwise K terminal-observation slots: step t writes slot (t - w0) of its window [w0, w0 + K); the window's bootstraps are
+    // one launch over its rows (terminal_obs, truncated[w0..] and rewards[w0..] are all contiguous in the step index).
+    const bool carried = K == 1 && !c.det;
+    int w0 = c.t_begin;
+    for (int t = c.t_begin; t < c.t_end; t++) {
+        if (carried) w0 = t;  // (a window of the one slot)
+        const float *obs_t = b->obs + (int64_t)t * N * D;
+        float *obs_next = b->obs + (int64_t)(t + 1) * N * D, *rew_t = b->rewards + (int64_t)t * N;
+        float *tobs = b->terminal_obs + (int64_t)(t - w0) * N * D;
+        uint8_t *term_t = b->terminated + (int64_t)t * N, *trunc_t = b->truncated + (int64_t)t * N;
+        void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
+        int rc = carried ? tma_policy_act_bootstrap(c.params, d, obs_t, N, c.rng_seed, c.rng_step0 + (uint32_t)t, c.env_offset, act_t, b->values + (int64_t)t * N,
+                                                    b->log_probs + (int64_t)t * N, t > 0 ? b->terminal_obs : nullptr, t > 0 ? trunc_t - N : nullptr, c.gamma,
+                                                    t > 0 ? rew_t - N : nullptr, c.stream)
+                         : tma_policy_act(c.params, d, obs_t, N, c.rng_seed, c.rng_step0 + (uint32_t)t, c.env_offset, c.det, act_t, b->values + (int64_t)t * N,
+                                          b->log_probs + (int64_t)t * N, c.stream);
+        if (rc) return rc;
+        rc = tma_env_step(c.env, act_t, act_kind, 0, 0, 1, obs_next, rew_t, term_t, trunc_t, tobs, nullptr, nullptr, c.stream);
+        if (rc) return rc;
+        if (c.vn) rc = vn_step(c.vn, obs_next, rew_t, tobs, term_t, trunc_t, c.training, c.stream);
+        if (rc) return rc;
+        if (carried ? t == c.T - 1 : (t - w0 + 1 == K || t == c.t_end - 1)) {  // (carried: the rollout's last step, nothing follows to carry its bootstrap)
+            rc = tma_policy_bootstrap(c.params, d, b->terminal_obs, b->truncated + (int64_t)w0 * N, (int64_t)(t - w0 + 1) * N, c.gamma,
+                                      b->rewards + (int64_t)w0 * N, c.stream);
+            if (rc) return rc;
+            w0 = t + 1;
+        }
     }
     return TMA_OK;
 }
 
-// The reference's default MLP(256, 256) in f32 on the Discrete tasks: policy-only fused chunk + ONE batched value launch + ONE batched bootstrap
-// launch per chunk of up to terminal_obs_slots steps.  vn != nullptr: the normalised form of the chunk kernel, as in collect_chunks_cont.
-static int collect_chunks_wide_f32(tma_env *env, tma_vecnorm *vn, int training, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b,
-                                   const PLayout &L, int t_begin, int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, double gamma, int compute_last_values,
-                                   int det, void *stream) {
-    const int64_t N = b->N;
-    TMA_HIP(hipSetDevice(env->device));
-    ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
-    const int K = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
-    const int D = d->obs_dim;
-    int t = t_begin;
-    while (t < t_end) {
-        int left = 0;
-        int rc = tma_env_steps_until_refill(env, &left);
-        if (rc) return rc;
-        int n = left < (t_end - t) ? left : (t_end - t);
-        if (n > K) n = K;  // one terminal-observation slot per step of the chunk
-        const VnChunk vc = vn ? vn_chunk_args(vn, training) : VnChunk{};
-        rc = dispatch_task(env->task, [&](auto task) {
-            using TT = decltype(task);
-            return launch_chunk_wide_f32<TT>(env, params, L, cp, b->terminal_obs, t, n, rng_seed, rng_step0, det, (hipStream_t)stream, vn ? &vc : nullptr);
-        });
-        if (rc) return rc;
-        if (vn && vc.stats_out) vn->cur ^= 1;  // the chunk left its statistics in the handle's other buffer
-        rc = tma_policy_values(params, d, b->obs + (int64_t)t * N * D, (int64_t)n * N, b->values + (int64_t)t * N, stream);
-        if (rc) return rc;
-        rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)t * N, (int64_t)n * N, gamma, b->rewards + (int64_t)t * N, stream);
-        if (rc) return rc;
-        rc = tma_env_internal_after_steps(env, n, stream);
-        if (rc) return rc;
-        t += n;
-    }
-    if (compute_last_values && t_end == T) {
-        if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-        return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
-    }
-    return TMA_OK;
+// plan -> the chunk loop or the per-step composition -> the one tail: last_values = V(obs[T])
+static int run_plan(const RolloutCall &c, const RolloutPlan &p) {
+    g_last_plan = p;
+    if (p.family == RolloutFamily::H64) g_roll_waves = p.waves;
+    if (c.vn) g_norm_path = plan_rollout_norm(p);
+    const int rc = p.family == RolloutFamily::PerStep ? collect_per_step(c) : run_chunks(c, p);
+    if (rc || !c.compute_last_values || c.t_end != c.T) return rc;
+    if (!c.b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
+    return tma_policy_values(c.params, c.d, c.b->obs + (int64_t)c.T * c.b->N * c.d->obs_dim, c.b->N, c.b->last_values, c.stream);
 }
 
 }  // namespace tma
@@ -2607,11 +2617,11 @@ extern "C" int tma_debug_poison_lds(unsigned pattern, void *stream) {
     return TMA_OK;
 }
 
+// Which family runs a shape is tma_rollout_plan.h's decision; every family leaves the bits of the per-step composition.
 extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b, int t_begin,
                                    int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, uint32_t env_offset, double gamma,
                                    int compute_last_values, int deterministic, void *stream) {
     using namespace tma;
-    const int det = deterministic ? 1 : 0;
     if (!env || !params || !d || !b) return fail(TMA_ERR_INVALID, "tma_rollout_collect: null argument");
     if (!b->obs || !b->actions || !b->rewards || !b->values || !b->log_probs || !b->terminated || !b->truncated || !b->terminal_obs)
         return fail(TMA_ERR_INVALID, "tma_rollout_collect: rollout buffers has a null plane");
@@ -2619,159 +2629,40 @@ extern "C" int tma_rollout_collect(tma_env *env, const float *params, const tma_
     const int64_t N = b->N;
     if (N != env->v.N) return fail(TMA_ERR_INVALID, "rollout buffers are for %lld envs, the env handle has %lld", (long long)N, (long long)env->v.N);
     const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
-    // (every fused chunk kernel below is tanh code: a policy with another activation runs the per-step composition at the end)
-    const bool fused = L.act == ACT_TANH && L.img_pi >= 0 && env->is_reset &&
-                       (env->task == TMA_TASK_GRIDWORLD || env->task == TMA_TASK_PUSH || env->task == TMA_TASK_BALL3D || env->task == TMA_TASK_WALLJUMP ||
-                        env->task == TMA_TASK_BICYCLE || env->task == TMA_TASK_GLIDER) &&
-                       d->obs_dim == tma_task_obs_dim(env->task) && d->act_dim == tma_task_num_actions(env->task);
-    // 256-wide bf16 policies on the Discrete tasks with observations of up to 32 floats: fused chunk with register-resident weights
-    static const bool no_wide_fused = getenv("TMA_NO_WIDE_FUSED") != nullptr;  // test hook: the per-step composition
-    const bool task_fused = dispatch_task(env->task, [](auto t) { return decltype(t)::FUSED_ROLLOUT ? 1 : 0; }) == 1;
-    const bool fused_disc = task_fused && !d->continuous && env->task != TMA_TASK_CRAWLER && env->task != TMA_TASK_ANT && d->act_dim == tma_task_num_actions(env->task) && d->obs_dim <= 32;
-    // ... and on the Crawler shape (Box actions, 172 observations): layer-1 fragments streamed per step, env state in LDS
-    const bool fused_cont = d->continuous && (env->task == TMA_TASK_CRAWLER || env->task == TMA_TASK_ANT) && d->act_dim == tma_task_act_dim(env->task);
-    const bool fused_wide = !no_wide_fused && L.act == ACT_TANH && L.bf16 && L.H == 256 && env->is_reset && d->obs_dim == tma_task_obs_dim(env->task) && (fused_disc || fused_cont);
-    // ... and in f32 (the reference's dtype), round 6: tiles of eight envs, up to 4096 envs (two block rounds; beyond that the per-step composition)
-    static const bool no_cont_f32 = getenv("TMA_NO_CONT_F32_FUSED") != nullptr;  // A/B switch
-    const bool fused_cont_f32 = !no_wide_fused && !no_cont_f32 && L.act == ACT_TANH && !L.bf16 && L.img_pi < 0 && L.H == 256 && env->is_reset && fused_cont &&
-                                d->obs_dim == tma_task_obs_dim(env->task) && env->v.N <= 4096;
-    // Box-action tasks (Crawler / Ant shapes), round 4: policy-only fused chunk + ONE batched value launch + ONE batched bootstrap launch per
-    // chunk of up to terminal_obs_slots steps (TMA_CONT_TWO_NET=1: the round-2 chunk with both nets in the step loop)
-    static const bool cont_two_net = getenv("TMA_CONT_TWO_NET") != nullptr;
-    if ((fused_wide && fused_cont && !cont_two_net) || fused_cont_f32)
-        return collect_chunks_cont(env, nullptr, 0, fused_cont_f32, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
-    if (fused_wide) {
-        TMA_HIP(hipSetDevice(env->device));
-        ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
-        int t = t_begin;
-        while (t < t_end) {
-            int left = 0;
-            int rc = tma_env_steps_until_refill(env, &left);
-            if (rc) return rc;
-            const int n = left < (t_end - t) ? left : (t_end - t);
-            rc = dispatch_task(env->task, [&](auto task) {
-                using TT = decltype(task);
-                return launch_chunk_wide<TT>(env, params, L, cp, t, n, rng_seed, rng_step0, (float)gamma, det, (hipStream_t)stream);
-            });
-            if (rc) return rc;
-            rc = tma_env_internal_after_steps(env, n, stream);
-            if (rc) return rc;
-            t += n;
-        }
-        if (compute_last_values && t_end == T) {
-            if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-            return tma_policy_values(params, d, b->obs + (int64_t)T * N * d->obs_dim, N, b->last_values, stream);
-        }
-        return TMA_OK;
-    }
-    // the reference's default MLP(256, 256) in f32 on the Discrete tasks (observations of up to 32 floats): policy-only fused chunk + ONE
-    // batched value launch + ONE batched bootstrap launch per chunk of up to terminal_obs_slots steps
-    static const int rows_forced = getenv("TMA_WIDE_F32_ROWS") ? atoi(getenv("TMA_WIDE_F32_ROWS")) : 0;
-    const bool fused_bb = env->task == TMA_TASK_BRICKBREAK && !d->continuous && d->act_dim == tma_task_num_actions(env->task) && env->v.N <= 2048 && rows_forced != 16;
-    const bool fused_wide_f32 = !no_wide_fused && L.act == ACT_TANH && !L.bf16 && L.img_pi < 0 && L.H == 256 && env->is_reset && (fused_disc || fused_bb) &&
-                                d->obs_dim == tma_task_obs_dim(env->task);
-    if (fused_wide_f32)
-        return collect_chunks_wide_f32(env, nullptr, 0, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
-    if (fused) {
-        TMA_HIP(hipSetDevice(env->device));
-        ChunkPtrs cp{b->obs, static_cast<int32_t *>(b->actions), b->rewards, b->values, b->log_probs, b->terminated, b->truncated};
-        int t = t_begin;
-        while (t < t_end) {
-            int left = 0;
-            int rc = tma_env_steps_until_refill(env, &left);
-            if (rc) return rc;
-            const int n = left < (t_end - t) ? left : (t_end - t);
-            if (env->task == TMA_TASK_GRIDWORLD) rc = launch_chunk<GridTask>(env, params, L, cp, t, n, rng_seed, rng_step0, (float)gamma, det, (hipStream_t)stream);
-            else if (env->task == TMA_TASK_PUSH) rc = launch_chunk<PushTask>(env, params, L, cp, t, n, rng_seed, rng_step0, (float)gamma, det, (hipStream_t)stream);
-            else if (env->task == TMA_TASK_WALLJUMP) rc = launch_chunk<WallJumpTask>(env, params, L, cp, t, n, rng_seed, rng_step0, (float)gamma, det, (hipStream_t)stream);
-            else if (env->task == TMA_TASK_BICYCLE) rc = launch_chunk<BicycleTask>(env, params, L, cp, t, n, rng_seed, rng_step0, (float)gamma, det, (hipStream_t)stream);
-            else if (env->task == TMA_TASK_GLIDER) rc = launch_chunk<GliderTask>(env, params, L, cp, t, n, rng_seed, rng_step0, (float)gamma, det, (hipStream_t)stream);
-            else rc = launch_chunk<BallTask>(env, params, L, cp, t, n, rng_seed, rng_step0, (float)gamma, det, (hipStream_t)stream);
-            if (rc) return rc;
-            rc = tma_env_internal_after_steps(env, n, stream);
-            if (rc) return rc;
-            t += n;
-        }
-        if (compute_last_values && t_end == T) {
-            if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-            return tma_policy_values(params, d, b->obs + (int64_t)T * N * d->obs_dim, N, b->last_values, stream);
-        }
-        return TMA_OK;
-    }
-    const int D = d->obs_dim, A = d->continuous ? d->act_dim : 1;
-    const size_t act_elem = d->continuous ? sizeof(float) : sizeof(int32_t);
-    const int K = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
-    if (K == 1 && !det) {
-        for (int t = t_begin; t < t_end; t++) {
-            const float *obs_t = b->obs + (int64_t)t * N * D;
-            float *obs_next = b->obs + (int64_t)(t + 1) * N * D;
-            void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
-            // policy forward of step t; the timeout bootstrap of step t-1 (terminal_obs still holds step t-1's) rides in the same launch
-            int rc = tma_policy_act_bootstrap(params, d, obs_t, N, rng_seed, rng_step0 + (uint32_t)t, env_offset, act_t, b->values + (int64_t)t * N,
-                                              b->log_probs + (int64_t)t * N, t > 0 ? b->terminal_obs : nullptr,
-                                              t > 0 ? b->truncated + (int64_t)(t - 1) * N : nullptr, gamma,
-                                              t > 0 ? b->rewards + (int64_t)(t - 1) * N : nullptr, stream);
-            if (rc) return rc;
-            rc = tma_env_step(env, act_t, d->continuous ? TMA_ACT_F32 : TMA_ACT_I32, 0, 0, 1, obs_next, b->rewards + (int64_t)t * N,
-                              b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, b->terminal_obs, nullptr, nullptr, stream);
-            if (rc) return rc;
-            if (t == T - 1) {  // last step of the rollout: nothing follows to carry its bootstrap
-                rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)t * N, N, gamma, b->rewards + (int64_t)t * N, stream);
-                if (rc) return rc;
-            }
-        }
-    } else {
-        // K terminal-observation slots: step t writes slot (t - w0) of its window [w0, w0 + K); the window's bootstraps are one launch
-        // over the K*N rows (terminal_obs, truncated[w0..] and rewards[w0..] are all contiguous in the step index).
-        int w0 = t_begin;
-        for (int t = t_begin; t < t_end; t++) {
-            const float *obs_t = b->obs + (int64_t)t * N * D;
-            float *obs_next = b->obs + (int64_t)(t + 1) * N * D;
-            void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
-            int rc = tma_policy_act(params, d, obs_t, N, rng_seed, rng_step0 + (uint32_t)t, env_offset, det, act_t, b->values + (int64_t)t * N,
-                                    b->log_probs + (int64_t)t * N, stream);
-            if (rc) return rc;
-            rc = tma_env_step(env, act_t, d->continuous ? TMA_ACT_F32 : TMA_ACT_I32, 0, 0, 1, obs_next, b->rewards + (int64_t)t * N,
-                              b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, b->terminal_obs + (int64_t)(t - w0) * N * D, nullptr,
-                              nullptr, stream);
-            if (rc) return rc;
-            if (t - w0 + 1 == K || t == t_end - 1) {
-                rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)w0 * N, (int64_t)(t - w0 + 1) * N, gamma,
-                                          b->rewards + (int64_t)w0 * N, stream);
-                if (rc) return rc;
-                w0 = t + 1;
-            }
-        }
-    }
-    if (compute_last_values && t_end == T) {
-        if (!b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-        int rc = tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
-        if (rc) return rc;
-    }
-    return TMA_OK;
+    const RolloutCall c{env, nullptr, 0, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, env_offset, gamma, compute_last_values, deterministic ? 1 : 0, stream};
+    return run_plan(c, plan_rollout(env->task, c.L, *d, N, env->is_reset, b->terminal_obs_slots, RolloutNorm::None, read_rollout_switches()));
 }
 
 extern "C" int tma_debug_last_rollout_waves(void) { return tma::g_roll_waves; }
 
-extern "C" int tma_rollout_norm_plan(int task, const tma_policy_dims *d, int64_t N, int training) {
-    using namespace tma;
-    const int rc = tma_check_policy_dims(d);
-    if (rc) return -rc;
-    if (task < TMA_TASK_BASIC || task > TMA_TASK_ANT) return -fail(TMA_ERR_UNKNOWN_TASK, "tma_rollout_norm_plan: unknown task id %d", task);
-    if (N < 1) return -fail(TMA_ERR_INVALID, "tma_rollout_norm_plan: N = %lld envs", (long long)N);
-    return plan_rollout_norm(task, make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation), *d, N, training != 0);
-}
-
 extern "C" int tma_debug_last_rollout_norm_path(void) { return tma::g_norm_path; }
 
-// tma_rollout_collect with a VecNormalize step behind every env step.  Where plan_rollout_norm fuses, the step runs inside the chunk kernel
-// (one launch per chunk + the batched value and bootstrap launches, over normalised rows); everywhere else it is tma_rollout_collect's per-step
-// composition (its last two branches) with vn_step behind tma_env_step.  Both leave the same bits (tests/test_vecnorm_fused_gpu.py).
+// what tma_rollout_norm_plan and tma_debug_plan_rollout refuse, as the real calls do
+static int check_plan_query(const char *who, int task, const tma_policy_dims *d, int64_t N) {
+    using namespace tma;
+    const int rc = tma_check_policy_dims(d);
+    if (rc) return rc;
+    if (task < TMA_TASK_BASIC || task > TMA_TASK_ANT) return fail(TMA_ERR_UNKNOWN_TASK, "%s: unknown task id %d", who, task);
+    if (N < 1) return fail(TMA_ERR_INVALID, "%s: N = %lld envs", who, (long long)N);
+    return TMA_OK;
+}
+
+// (the plan of a reset env handle with every switch off: this query reads none)
+extern "C" int tma_rollout_norm_plan(int task, const tma_policy_dims *d, int64_t N, int training) {
+    using namespace tma;
+    const int rc = check_plan_query("tma_rollout_norm_plan", task, d, N);
+    if (rc) return -rc;
+    const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
+    return plan_rollout_norm(plan_rollout(task, L, *d, N, true, 1, training ? RolloutNorm::Training : RolloutNorm::Frozen, RolloutSwitches{}));
+}
+
+// tma_rollout_collect with a VecNormalize step behind every env step.  Where the plan says norm_in_chunk, the step runs inside the chunk kernel
+// (one launch per chunk + the batched value and bootstrap launches, over normalised rows); everywhere else it is the per-step composition with
+// vn_step behind tma_env_step.  Both leave the same bits (tests/test_vecnorm_fused_gpu.py).
 extern "C" int tma_rollout_collect_norm(tma_env *env, tma_vecnorm *vn, const float *params, const tma_policy_dims *d, const tma_rollout_buffers *b,
                                         int t_begin, int t_end, int T, uint32_t rng_seed, uint32_t rng_step0, uint32_t env_offset, double gamma,
                                         int compute_last_values, int deterministic, int training, void *stream) {
     using namespace tma;
-    const int det = deterministic ? 1 : 0;
     if (!env || !vn || !params || !d || !b) return fail(TMA_ERR_INVALID, "tma_rollout_collect_norm: null argument");
     if (!b->obs || !b->actions || !b->rewards || !b->values || !b->log_probs || !b->terminated || !b->truncated || !b->terminal_obs)
         return fail(TMA_ERR_INVALID, "tma_rollout_collect_norm: rollout buffers has a null plane");
@@ -2781,74 +2672,30 @@ extern "C" int tma_rollout_collect_norm(tma_env *env, tma_vecnorm *vn, const flo
     if (d->obs_dim != vn->D) return fail(TMA_ERR_INVALID, "the policy takes %d observations, the normalisation handle has %d", d->obs_dim, vn->D);
     if (N != env->v.N) return fail(TMA_ERR_INVALID, "rollout buffers are for %lld envs, the env handle has %lld", (long long)N, (long long)env->v.N);
     if (compute_last_values && t_end == T && !b->last_values) return fail(TMA_ERR_INVALID, "last_values is null");
-    // the fused chunks: where the plan says so, on a reset env handle (TMA_NO_NORM_FUSED / TMA_NO_WIDE_FUSED: A/B switches and test hooks, and
-    // the switches that take tma_rollout_collect off these two kernels take this driver off them as well)
-    static const bool no_fused = getenv("TMA_NO_NORM_FUSED") != nullptr || getenv("TMA_NO_WIDE_FUSED") != nullptr;
-    static const bool no_cont_f32 = getenv("TMA_NO_CONT_F32_FUSED") != nullptr;
-    static const bool rows16 = getenv("TMA_WIDE_F32_ROWS") != nullptr && atoi(getenv("TMA_WIDE_F32_ROWS")) == 16;
-    g_norm_path = TMA_ROLLOUT_NORM_PER_STEP;
-    if (!no_fused && env->is_reset && tma_check_policy_dims(d) == TMA_OK) {
-        const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
-        int plan = plan_rollout_norm(env->task, L, *d, N, training != 0);
-        if ((plan == TMA_ROLLOUT_NORM_FUSED_DISC_F32 && rows16) || (plan == TMA_ROLLOUT_NORM_FUSED_CONT_F32 && no_cont_f32)) plan = TMA_ROLLOUT_NORM_PER_STEP;
-        if (plan != TMA_ROLLOUT_NORM_PER_STEP) {
-            const int rc = vn_ensure(vn);
-            if (rc) return rc;
-            g_norm_path = plan;
-            if (plan == TMA_ROLLOUT_NORM_FUSED_CONT_F32)  // (the side-stream overlap of the value / bootstrap launches included: they touch nothing of the handle)
-                return collect_chunks_cont(env, vn, training, true, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
-            return collect_chunks_wide_f32(env, vn, training, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, gamma, compute_last_values, det, stream);
-        }
-    }
-    const int D = d->obs_dim, A = d->continuous ? d->act_dim : 1;
-    const size_t act_elem = d->continuous ? sizeof(float) : sizeof(int32_t);
-    const int K = b->terminal_obs_slots > 1 ? b->terminal_obs_slots : 1;
-    if (K == 1 && !det) {
-        for (int t = t_begin; t < t_end; t++) {
-            const float *obs_t = b->obs + (int64_t)t * N * D;
-            float *obs_next = b->obs + (int64_t)(t + 1) * N * D;
-            void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
-            // policy forward of step t; the timeout bootstrap of step t-1 (terminal_obs and rewards already normalised) rides in the same launch
-            int rc = tma_policy_act_bootstrap(params, d, obs_t, N, rng_seed, rng_step0 + (uint32_t)t, env_offset, act_t, b->values + (int64_t)t * N,
-                                              b->log_probs + (int64_t)t * N, t > 0 ? b->terminal_obs : nullptr,
-                                              t > 0 ? b->truncated + (int64_t)(t - 1) * N : nullptr, gamma,
-                                              t > 0 ? b->rewards + (int64_t)(t - 1) * N : nullptr, stream);
-            if (rc) return rc;
-            rc = tma_env_step(env, act_t, d->continuous ? TMA_ACT_F32 : TMA_ACT_I32, 0, 0, 1, obs_next, b->rewards + (int64_t)t * N,
-                              b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, b->terminal_obs, nullptr, nullptr, stream);
-            if (rc) return rc;
-            rc = vn_step(vn, obs_next, b->rewards + (int64_t)t * N, b->terminal_obs, b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N,
-                         training, stream);
-            if (rc) return rc;
-            if (t == T - 1) {  // last step of the rollout: nothing follows to carry its bootstrap
-                rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)t * N, N, gamma, b->rewards + (int64_t)t * N, stream);
-                if (rc) return rc;
-            }
-        }
-    } else {
-        int w0 = t_begin;
-        for (int t = t_begin; t < t_end; t++) {
-            const float *obs_t = b->obs + (int64_t)t * N * D;
-            float *obs_next = b->obs + (int64_t)(t + 1) * N * D;
-            float *tobs = b->terminal_obs + (int64_t)(t - w0) * N * D;
-            void *act_t = static_cast<char *>(b->actions) + (int64_t)t * N * A * act_elem;
-            int rc = tma_policy_act(params, d, obs_t, N, rng_seed, rng_step0 + (uint32_t)t, env_offset, det, act_t, b->values + (int64_t)t * N,
-                                    b->log_probs + (int64_t)t * N, stream);
-            if (rc) return rc;
-            rc = tma_env_step(env, act_t, d->continuous ? TMA_ACT_F32 : TMA_ACT_I32, 0, 0, 1, obs_next, b->rewards + (int64_t)t * N,
-                              b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, tobs, nullptr, nullptr, stream);
-            if (rc) return rc;
-            rc = vn_step(vn, obs_next, b->rewards + (int64_t)t * N, tobs, b->terminated + (int64_t)t * N, b->truncated + (int64_t)t * N, training, stream);
-            if (rc) return rc;
-            if (t - w0 + 1 == K || t == t_end - 1) {  // the window's bootstraps: one launch over its rows, every one normalised by its own step
-                rc = tma_policy_bootstrap(params, d, b->terminal_obs, b->truncated + (int64_t)w0 * N, (int64_t)(t - w0 + 1) * N, gamma,
-                                          b->rewards + (int64_t)w0 * N, stream);
-                if (rc) return rc;
-                w0 = t + 1;
-            }
-        }
-    }
-    if (compute_last_values && t_end == T) return tma_policy_values(params, d, b->obs + (int64_t)T * N * D, N, b->last_values, stream);
+    const bool dims_ok = tma_check_policy_dims(d) == TMA_OK;  // (dims no kernel takes: the per-step composition, whose first launch refuses them)
+    const PLayout L = dims_ok ? make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation) : PLayout{};
+    const RolloutCall c{env, vn, training, params, d, b, L, t_begin, t_end, T, rng_seed, rng_step0, env_offset, gamma, compute_last_values, deterministic ? 1 : 0, stream};
+    const RolloutNorm norm = training ? RolloutNorm::Training : RolloutNorm::Frozen;
+    return run_plan(c, dims_ok ? plan_rollout(env->task, c.L, *d, N, env->is_reset, b->terminal_obs_slots, norm, read_rollout_switches()) : RolloutPlan{});
+}
+
+// Host-only (ABI 223): what plan_rollout answers for a shape, under this process's switches
+extern "C" int tma_debug_plan_rollout(int task, const tma_policy_dims *d, int64_t N, int is_reset, int terminal_obs_slots, int norm, int32_t *out6) {
+    using namespace tma;
+    if (!out6) return fail(TMA_ERR_INVALID, "tma_debug_plan_rollout: null argument");
+    const int rc = check_plan_query("tma_debug_plan_rollout", task, d, N);
+    if (rc) return rc;
+    if (norm < 0 || norm > 2) return fail(TMA_ERR_INVALID, "tma_debug_plan_rollout: norm %d is none of TMA_ROLLOUT_PLAN_NORM_*", norm);
+    const PLayout L = make_layout(d->obs_dim, d->hidden, d->act_dim, d->continuous, d->mfma_dtype, d->activation);
+    const RolloutPlan p = plan_rollout(task, L, *d, N, is_reset != 0, terminal_obs_slots, (RolloutNorm)norm, read_rollout_switches());
+    out6[0] = (int32_t)p.family, out6[1] = p.waves, out6[2] = p.rows, out6[3] = (int32_t)p.grid, out6[4] = p.block, out6[5] = p.lds;
+    return TMA_OK;
+}
+
+// (ABI 223) family, waves and rows of the calling thread's last tma_rollout_collect / tma_rollout_collect_norm; no GPU work
+extern "C" int tma_debug_last_rollout_plan(int32_t *out3) {
+    if (!out3) return tma::fail(TMA_ERR_INVALID, "tma_debug_last_rollout_plan: null argument");
+    out3[0] = (int32_t)tma::g_last_plan.family, out3[1] = tma::g_last_plan.waves, out3[2] = tma::g_last_plan.rows;
     return TMA_OK;
 }
 

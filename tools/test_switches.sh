@@ -1,5 +1,6 @@
 #!/bin/bash
 # The A/B switches of the library select the kernels of earlier rounds; each must keep passing the tests of the paths it touches.
+# (The rollout driver's ten are gathered in RolloutSwitches, csrc/tma_rollout_plan.h, and read once by read_rollout_switches; the policy dispatchers' in DispatchSwitches.)
 # Run on the GPU box: bash tools/test_switches.sh
 run() { echo "== $1"; env $1 python -m pytest $2 -m gpu -q -x ${3:+-k "$3"} 2>&1 | tail -1; }  # $3: a -k expression (tests that assert WHICH path ran are deselected under the switch that disables it)
 run "TMA_SYNC_EVAL=1" "tests/test_dropin_gpu.py"
