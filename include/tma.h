@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 223
+#define TMA_VERSION 224
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -455,6 +455,63 @@ int tma_ppo_permutation(uint32_t perm_seed, uint32_t perm_epoch, int64_t total, 
 int tma_rollout_gather(const tma_rollout *rb, const float *values /* [T][N], may be NULL */, const tma_policy_dims *d, const tma_minibatch *mb,
                        float *obs_out /* [count][D] */, void *actions_out /* i32 [count] | f32 [count][A] */, float *old_values_out,
                        float *old_log_prob_out, float *advantages_out, float *returns_out, void *stream);
+
+/* ---- replay buffer (ABI 224): SB3's ReplayBuffer / NStepReplayBuffer (3P: stable_baselines3/common/buffers.py, what the reference's DQN
+ *      default keeps, backend/mlagents/training.py:343-360) as device planes -- written without a copy to the host, sampled as dense tensors in
+ *      one launch.  DESIGN.md section 16. ---- */
+/* The storage, caller-owned device memory as with tma_rollout: `capacity` rows R (>= 1) of `n_envs` envs N (>= 1).  obs_dim D and act_dim A in
+ * [1, 4096]; a Discrete buffer (continuous = 0) stores one i32 per action and uses A nowhere.  The ring position and the fill state are NOT
+ * device state: the host keeps them and passes them to each call. */
+typedef struct tma_replay {
+    float *obs;          /* [R][N][D]  the observation the action was chosen from */
+    float *next_obs;     /* [R][N][D]  the observation it led to: the terminal observation where the step ended its episode */
+    void *actions;       /* i32 [R][N] (Discrete) | f32 [R][N][A] (Box) */
+    float *rewards;      /* [R][N] */
+    uint8_t *terminated; /* [R][N] */
+    uint8_t *truncated;  /* [R][N] */
+    int capacity;
+    int64_t n_envs;
+    int obs_dim, act_dim, continuous;
+} tma_replay;
+/* ReplayBuffer.add for one vector step, in ONE launch: row `pos` of every plane.  Per env i:  obs[pos][i] = last_obs_inout[i];
+ * next_obs[pos][i] = (term[i] | trunc[i]) ? term_obs[i] : step_obs[i]  (SB3's terminal_observation substitution in _store_transition);
+ * actions i32[N] | f32[N][A], rewards f32[N] and the two flag rows u8[N] are copied;  then last_obs_inout[i] = step_obs[i], the post-reset
+ * observation the next action is chosen from.  Why last_obs_inout: tma_env_step's outputs are overwritten by the next step, so the buffer's
+ * owner keeps the current observation in memory of its own, and this launch keeps it current.  term_obs may be NULL ONLY IF THE CALLER
+ * GUARANTEES THAT NO FLAG IS SET in term / trunc: next_obs is then step_obs for every env, whatever the flags say.  No atomics, no workspace;
+ * the grid is capped and strides; every offset is 64-bit; nothing synchronises.  Refused with TMA_ERR_INVALID before any HIP call: rb NULL, bad
+ * geometry, a NULL plane, a NULL argument other than term_obs, pos outside [0, R), last_obs_inout overlapping step_obs. */
+int tma_replay_add(const tma_replay *rb, int64_t pos, float *last_obs_inout /* [N][D] */, const void *actions, const float *step_obs /* [N][D] */,
+                   const float *rewards, const uint8_t *term, const uint8_t *trunc, const float *term_obs /* [N][D], may be NULL (above) */, void *stream);
+/* ReplayBuffer.sample / NStepReplayBuffer.sample: draws `count` transitions and gathers them, in ONE launch.
+ * `size`: the number of valid rows -- pos before the ring has wrapped, R afterwards; `newest`: the row last written, in [0, size).
+ * Index draw, counter-based and reproducible (mix32 is the engine's stand-in for np.random.randint): for output row b
+ *   t = (uint64(mix32(seed, b, draw)) * size) >> 32,   i = mix32(seed ^ 0x5EEDBA5E, b, draw) % N.
+ * Bias: the multiply-shift maps 2^32 hash values onto `size` rows, so two rows' probabilities differ by at most 2^-32 (a relative size / 2^32);
+ * the modulo's, N / 2^32 likewise.  Rows are drawn with replacement, as SB3 draws them.
+ * The window of a draw, n = n_step: rows t, t+1, ... (mod R); step k is included while k < n; the window ends behind the first included step
+ * whose terminated | truncated is set, and behind row `newest` (it never crosses the write head into older data).  With L >= 1 steps included:
+ *   rewards_out   = sum_{k<L} gamma^k r_k, accumulated in float64 in k order (gamma^k by repeated float64 multiplication), rounded once to f32;
+ *   next_obs_out  = next_obs of the last included step;   dones_out = its `terminated` as 0.0f / 1.0f (a time-out is not a done: SB3's
+ *   handle_timeout_termination=True);   discounts_out = (float)gamma^L.
+ * With n_step = 1 that is: rewards_out the stored reward, dones_out = terminated, discounts_out = (float)gamma.  obs_out f32[count][D],
+ * actions_out i32[count] | f32[count][A] and next_obs_out f32[count][D] are pure copies: every element has the bits of its source element.
+ * rows_out / envs_out i32[count] return (t, i).  Any output pointer may be NULL and is then skipped.  Observation rows move as dwords, as
+ * float4 where D is a multiple of four and the bases are 16-byte aligned.  No atomics, no workspace; the grid is capped and strides.
+ * Refused with TMA_ERR_INVALID before any HIP call: rb NULL, bad geometry, R * N >= 2^31, size outside [1, R], newest outside [0, size),
+ * count < 1, n_step outside [1, 64], every output NULL, a NULL source plane (rewards, terminated, truncated; obs / actions / next_obs where their
+ * output is asked for). */
+int tma_replay_sample(const tma_replay *rb, int size, int newest, int n_step, double gamma, uint32_t seed, uint32_t draw, int64_t count,
+                      float *obs_out, void *actions_out, float *next_obs_out, float *dones_out, float *rewards_out, float *discounts_out,
+                      int32_t *rows_out, int32_t *envs_out, void *stream);
+/* The epsilon-greedy action pick of SB3's DQN.predict on q f32[n][A] (dense, 2 <= A <= 16), e.g. a Discrete tma_policy_head output.  Per row:
+ * u = (mix32(rng_seed, env_offset + row, rng_step) >> 8) * 2^-24;  u < (float)eps: action = mix32(rng_seed ^ 0xE9517EED, env_offset + row,
+ * rng_step) % A;  else the first maximal column -- tma_policy_head's rule for the deterministic action; a NaN never wins, a row of NaNs gives 0.
+ * The coin is per env (SB3 tosses one per predict call; the two coincide at n = 1).  actions_out i32[n].  Refused with TMA_ERR_INVALID before
+ * any HIP call: q / actions_out NULL, n < 1, A outside [2, 16], eps outside [0, 1] or NaN. */
+int tma_egreedy_actions(const float *q, int64_t n, int A, double eps, uint32_t rng_seed, uint32_t rng_step, uint32_t env_offset, int32_t *actions_out,
+                        void *stream);
+
 /* Profiling aid for bench.py's roofline object: when enabled, tma_ppo_minibatch_grad brackets its DOMINANT kernel (the persistent
  * forward+backward kernel; for two-pass shapes both passes; not the advantage pass, not the slab reduction) with HIP events recorded on
  * the stream it launches on; tma_debug_last_grad_kernel_us waits for the last bracketed launch and returns its duration. */

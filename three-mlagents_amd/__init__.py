@@ -8,7 +8,8 @@ __version__ = "0.2.0"
 
 from .tasks import ENGINE_TASKS, EngineTask, make_env, resolve  # noqa: E402
 
-__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C", "RolloutBuffer", "RolloutBufferSamples"]
+__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C", "RolloutBuffer", "RolloutBufferSamples", "ReplayBuffer",
+           "ReplayBufferSamples"]
 
 
 def __getattr__(name):  # the algorithm classes import torch: on first use, not with the task table
@@ -24,4 +25,8 @@ def __getattr__(name):  # the algorithm classes import torch: on first use, not 
         from . import rollout_buffer
 
         return getattr(rollout_buffer, name)
+    if name in ("ReplayBuffer", "ReplayBufferSamples"):
+        from . import replay_buffer
+
+        return getattr(replay_buffer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

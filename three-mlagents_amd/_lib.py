@@ -52,6 +52,11 @@ class RolloutBuffers(C.Structure):
                 ("truncated", _vp), ("terminal_obs", _vp), ("last_values", _vp), ("N", _i64), ("terminal_obs_slots", _i32)]
 
 
+class Replay(C.Structure):  # include/tma.h tma_replay: the planes of a replay buffer and their geometry
+    _fields_ = [("obs", _vp), ("next_obs", _vp), ("actions", _vp), ("rewards", _vp), ("terminated", _vp), ("truncated", _vp), ("capacity", _i32),
+                ("n_envs", _i64), ("obs_dim", _i32), ("act_dim", _i32), ("continuous", _i32)]
+
+
 _pd = C.POINTER(PolicyDims)
 
 # name -> (restype, argtypes); every symbol include/tma.h declares
@@ -118,6 +123,9 @@ SIGNATURES = {
     "tma_ppo_adam_step_local": (_i32, [_vp, _vp, _vp, _vp, _pd, _i64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _i64]),
     "tma_ppo_permutation": (_i32, [_u32, _u32, _i64, _vp]),
     "tma_rollout_gather": (_i32, [C.POINTER(Rollout), _vp, _pd, C.POINTER(Minibatch), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tma_replay_add": (_i32, [C.POINTER(Replay), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tma_replay_sample": (_i32, [C.POINTER(Replay), _i32, _i32, _i32, _f64, _u32, _u32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tma_egreedy_actions": (_i32, [_vp, _i64, _i32, _f64, _u32, _u32, _u32, _vp, _vp]),
     "tma_ppo_persist_fallbacks": (_i32, [_vp, C.POINTER(_i64), _vp]),
     "tma_ppo_train_epoch_local": (_i32, [_vp, _pd, C.POINTER(Rollout), _u32, _u32, _i64, C.POINTER(PPOHParams), _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64,
                                          _f64, _vp, _vp]),

@@ -13,11 +13,10 @@
 // four floats and both bases are 16-byte aligned, where it moves float4.
 // The grid is capped at GATHER_BLOCKS workgroups (tma_workspace.h) and strides over the row blocks.  Every offset is 64-bit: T*N*D*4 passes
 // 2^32 bytes at the benchmark shapes; T*N itself is below 2^31 (checked), so a row's plane offset travels between lanes as one int.
+#include "tma_gather_rows.h"
 #include "tma_ppo_types.h"
 
 namespace tma {
-
-constexpr int GATHER_WAVES = 4;  // waves per workgroup, each on a row block of its own
 
 struct GatherArgs {
     const float *obs;         // [T][N][D]
@@ -29,34 +28,6 @@ struct GatherArgs {
     int T, D, A, cont, rpw;   // rpw: rows per wave block, 16 or 64
     int64_t N;
 };
-
-// rows [0, rows) of a wave's block, W = width / VEC vectors each: dst is the block's contiguous [rows][W] span, src the plane's base; `off` is
-// lane l's plane row (valid in lanes < rows).  Four vectors a lane are loaded before the first is stored.  (Measured and dropped: eight loads in
-// flight, and the scalars' stores moved behind the walk so that their loads and the walk's share one round trip -- 17.6 / 23.6 us against
-// 16.8 / 22.6 at the two large shapes of DESIGN.md section 15: the round trips of one block are not what bounds the kernel.)
-template <class V>
-__device__ __forceinline__ void gather_rows(const V *__restrict__ src, V *__restrict__ dst, int off, int rows, int W, int lane) {
-    const int n = rows * W;
-    const float inv_w = 1.0f / (float)W;  // e / W without an integer division: e < 64 * 4096 is exact in f32, the quotient is off by one at the most
-    for (int e0 = 0; e0 < n; e0 += 4 * 64) {
-        V v[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int e = e0 + 64 * q + lane;
-            const int ec = e < n ? e : 0;  // (every lane takes part in the cross-lane read; lanes behind the span read element 0 and store nothing)
-            int row = (int)((float)ec * inv_w), c = ec - row * W;
-            if (c < 0) row--, c += W;
-            if (c >= W) row++, c -= W;
-            const int o = __shfl(off, row, 64);
-            v[q] = src[(int64_t)o * W + c];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int e = e0 + 64 * q + lane;
-            if (e < n) dst[e] = v[q];
-        }
-    }
-}
 
 template <int VEC>
 __global__ __launch_bounds__(64 * GATHER_WAVES) void rollout_gather_kernel(GatherArgs g, Minibatch mb) {
