@@ -419,3 +419,76 @@ def test_env_handles_reuse_their_device_blocks():
     assert rows(first[3]) == rows(again[3]) and len(first[3][0]) > 0 and first[3][3] == again[3][3]
     assert first[4][2] == again[4][2] and abs(first[4][0] - again[4][0]) <= 1e-9 * max(1.0, abs(first[4][0])) and first[4][1] == again[4][1]
     assert free0 - free1 < (8 << 20), (free0, free1)  # (nothing accumulates: every close hands its blocks to the next create)
+
+
+def _chain_cases():
+    from _chain_scripts import SCRIPTS
+
+    return [pytest.param(task, which, id=f"{task}-{which}") for task, which in SCRIPTS]
+
+
+@pytest.mark.parametrize("task,which", _chain_cases())
+def test_chain_unhealthy_scripts_against_oracle(task, which):
+    """Crawler / Ant episodes ended by `unhealthy` -- the branch no random-action test reaches (64 envs x 1040 steps of N(0, 1): 0 terminated)
+    -- per-step kernel against the oracle over script length + 2 steps, so that every env terminates, is reset and goes on.  Reached by the
+    scripts of tests/_chain_scripts.py: Crawler z and pitch, Ant z.  Ant's pitch and the roll of both are reached by no script found (see that
+    module); test_chain_unhealthy_by_attitude below injects them."""
+    from _chain_scripts import script_actions, why_unhealthy
+
+    n = 64
+    actions = script_actions(task, which, n)
+    T = len(actions)
+    eng = _engine(task, n, seed=7, ring_depth=4)
+    ref = orc.OracleVecEnv(task, n, seed=7)
+    inexact = _cmp(task, "reset", eng.reset().cpu().numpy(), ref.reset(), 0)
+    dev_actions = torch.from_numpy(actions).cuda()
+    reasons, n_term, resumed = set(), 0, np.zeros(n, bool)
+    for t in range(T):
+        pre = ref.get_state()
+        r = ref.step(actions[t])
+        o = {k: v[0].cpu().numpy() for k, v in eng.step(dev_actions[t]).items()}
+        done = (r["term"] | r["trunc"]).astype(bool)
+        assert np.array_equal(o["term"], r["term"]) and np.array_equal(o["trunc"], r["trunc"]), (task, t)
+        inexact += _cmp(task, "obs", o["obs"], r["obs"], t)
+        inexact += _cmp(task, "rew", o["rew"], r["rew32"], t)
+        inexact += _cmp(task, "term_obs", o["term_obs"][done], r["term_obs"][done], t)
+        inexact += _cmp(task, "ep_ret", o["ep_ret"], r["ep_ret"], t)
+        assert np.array_equal(o["ep_len"], r["ep_len"]), (task, t)
+        # what the case is about, from the ORACLE's outputs
+        assert not r["trunc"].any() and r["ep_len"].max() < orc.max_episode_steps(task)
+        n_term += int(r["term"].sum())
+        for i in np.flatnonzero(r["term"]):
+            reasons |= why_unhealthy(task, pre[i], actions[t, i])
+        if t < T - 1:
+            resumed |= r["term"].astype(bool)
+    assert n_term >= n and which in reasons and resumed.any(), (n_term, reasons)
+    assert np.array_equal(eng.episode_index().cpu().numpy().astype(np.uint32), ref.episode_index())
+    inexact += _cmp(task, "state", eng.get_state().cpu().numpy(), ref.get_state(), "final")
+    print(f"[{task}/{which}] {n_term} unhealthy endings by {sorted(reasons)}, not bit-identical to oracle: {inexact}")
+    eng.close()
+
+
+@pytest.mark.parametrize("task", ["crawler", "ant"])
+def test_chain_unhealthy_by_attitude(task):
+    """|pitch| > 1 and |roll| > 1, each sign, each alone, and the healthy side of both: oracle states with the root attitude overwritten
+    (tests/_chain_scripts.attitude_states), injected on both sides, one step under zero action."""
+    from _chain_scripts import attitude_states, why_unhealthy
+
+    n = 64
+    st, which = attitude_states(task, n, seed=7)
+    eng = _engine(task, n, seed=7, ring_depth=4)
+    ref = orc.OracleVecEnv(task, n, seed=7)
+    eng.reset(), ref.reset()
+    eng.set_state(st), ref.set_state(st)
+    act = np.zeros((n, orc.act_dim(task)), np.float32)
+    r = ref.step(act)
+    o = {k: v[0].cpu().numpy() for k, v in eng.step(torch.from_numpy(act).cuda()).items()}
+    seen = {(w, tuple(sorted(why_unhealthy(task, st[i], act[i])))) for i, w in enumerate(which)}
+    assert seen == {("pitch", ("pitch",)), ("pitch", ()), ("roll", ("roll",)), ("roll", ())}, seen  # from the oracle: each alone, and neither
+    assert r["term"].sum() == n // 2 and not r["trunc"].any()
+    assert np.array_equal(o["term"], r["term"]) and np.array_equal(o["trunc"], r["trunc"])
+    done = r["term"].astype(bool)
+    for name, got, want in (("obs", o["obs"], r["obs"]), ("rew", o["rew"], r["rew32"]), ("term_obs", o["term_obs"][done], r["term_obs"][done]),
+                            ("state", eng.get_state().cpu().numpy(), ref.get_state())):
+        _cmp(task, name, got, want, 0)
+    eng.close()

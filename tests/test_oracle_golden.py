@@ -95,3 +95,76 @@ def _check_rollout(task, g, prefix=""):
 def test_vec_rollout_matches_reference(golden, task):
     _check_rollout(task, golden(task))
     _check_rollout(task, golden(task), prefix="b_")
+
+
+# ---- the branches random action tapes never reach: tests/golden/<task>_edges.npz (tools/gen_golden.py `edges`, labels in tests/_edges.py) ----
+@pytest.mark.parametrize("task", FLOAT_TASKS)
+def test_edge_fixture_covers_every_committed_label(golden, task):
+    """From the fixture alone: every committed branch label is present with one row per action, and each row's recorded reward, flags and
+    post-state are what its label says (goal -> 50 and terminated, a fall at the step limit -> truncated, not terminated, -10, ...)."""
+    from _edges import check_coverage
+
+    assert check_coverage(task, golden(task + "_edges")) > 0
+
+
+@pytest.mark.parametrize("task", FLOAT_TASKS)
+def test_edge_rows_legacy_step(golden, task):
+    """orc.legacy_step on every edge row: post-state, float32 observation, float64 reward, and `done` as the legacy env reports it (the
+    adapter's flags or-ed: it turns a `done` at the limit into a truncation)."""
+    from _edges import LIMIT, STEPS_AT, TERMINAL_REWARDS
+
+    g = golden(task + "_edges")
+    for i, (si, a) in enumerate(zip(g["state_in"], g["action"])):
+        st, obs, r, done = orc.legacy_step(task, si, int(a))
+        ctx = (task, g["labels"][i], int(a))
+        assert np.array_equal(st[: si.size], g["state_out"][i]), (ctx, st, g["state_out"][i])
+        assert np.array_equal(obs, g["obs32"][i]), ctx
+        assert r == g["rew64"][i], (ctx, r, g["rew64"][i])
+        # the legacy `done` (below the adapter) is not in the fixture where the adapter truncated: by the source it is "a terminal reward, or past
+        # the env's own step limit"; where the adapter did not truncate it is the recorded `terminated`
+        legacy_done = float(g["rew64"][i]) in TERMINAL_REWARDS[task] or g["state_out"][i][STEPS_AT[task]] > LIMIT[task]
+        assert done == legacy_done, ctx
+        assert g["truncated"][i] or done == bool(g["terminated"][i]), ctx
+
+
+@pytest.mark.parametrize("task", FLOAT_TASKS)
+def test_edge_rows_vec_env(golden, task):
+    """OracleVecEnv (adapter + DummyVecEnv semantics) with the edge states injected: one step against the adapter-level outputs."""
+    g = golden(task + "_edges")
+    n = len(g["labels"])
+    env = orc.OracleVecEnv(task, n, seed=1)
+    env.reset()
+    env.set_state(g["state_in"])
+    assert np.array_equal(env.get_state()[:, : g["state_in"].shape[1]], g["state_in"])
+    o = env.step(g["action"])
+    done = g["terminated"] | g["truncated"]
+    assert np.array_equal(o["rew32"], g["rew32"]) and np.array_equal(o["rew64"], g["rew64"])
+    assert np.array_equal(o["term"].astype(bool), g["terminated"]) and np.array_equal(o["trunc"].astype(bool), g["truncated"])
+    assert np.array_equal(o["term_obs"][done], g["obs32"][done])
+    assert np.array_equal(o["obs"][~done], g["obs32"][~done])
+    assert np.array_equal(env.get_state()[~done][:, : g["state_in"].shape[1]], g["state_out"][~done])
+    assert np.array_equal(o["ep_len"][done] > 0, np.ones(int(done.sum()), bool)) and np.array_equal(env.episode_index(), done.astype(np.uint32))
+
+
+def test_chain_scripts_end_every_env_by_the_named_condition():
+    """tests/_chain_scripts.py on the CPU: each committed script ends every env's episode on its last step by the condition it is named
+    after, and the states taken one to three steps earlier end within three steps under zero action (what the fused-rollout cases start from)."""
+    from _chain_scripts import SCRIPTS, pre_unhealthy_states, script_actions, why_unhealthy
+
+    for (task, which), (_, _, steps) in SCRIPTS.items():
+        n = 16
+        env = orc.OracleVecEnv(task, n, seed=7)
+        env.reset()
+        actions = script_actions(task, which, n, extra=0)
+        for t in range(steps):
+            pre = env.get_state()
+            o = env.step(actions[t])
+            assert bool(o["term"].all()) == (t == steps - 1) and not o["trunc"].any(), (task, which, t)
+        assert all(which in why_unhealthy(task, pre[i], actions[-1, i]) for i in range(n)), (task, which)
+        st = pre_unhealthy_states(task, which, n, seed=7, leads=(1, 2, 3))
+        env.set_state(st)
+        ended = np.zeros(n, bool)
+        for _ in range(3):
+            ended |= env.step(np.zeros((n, orc.act_dim(task)), np.float32))["term"].astype(bool)
+        # (the oracle is deterministic: the count is exact)
+        assert int(ended.sum()) == {("crawler", "z"): 11, ("crawler", "pitch"): 16, ("ant", "z"): 11}[(task, which)], (task, which, ended)

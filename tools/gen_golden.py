@@ -27,6 +27,8 @@ runs on a host without AVX-512 -- the configuration a plain-C restatement can ma
 generated with numpy's default dispatch, as before.
 
 Usage:  python tools/gen_golden.py [task ...]   (writes tests/golden/<task>.npz; no arguments = every task + the RNG fixture)
+        python tools/gen_golden.py edges        (writes tests/golden/{bicycle,brickbreak,glider}_edges.npz and nothing else: hand-built states
+                                                 at the terminal / clip / time-limit branches, one adapter step each, same child process)
 """
 from __future__ import annotations
 
@@ -365,6 +367,393 @@ def rng_fixture():
     )
 
 
+# ------------------------------------------------------------------------------------------
+# `edges` mode: hand-built states at the branches random action tapes never reach, one step THROUGH THE ADAPTER each
+# (tests/golden/{bicycle,brickbreak,glider}_edges.npz).  Every scenario is built once per action of the task (the action changes where
+# the step lands, so the state is solved per action), unless its label ends in `_a<k>`: then only action k is taken.
+# ------------------------------------------------------------------------------------------
+def set_state(task: str, env, st) -> None:
+    """Inverse of get_state() for the three float tasks; the adapter's own step counter is set to the inner env's."""
+    e = env.env
+    st = np.asarray(st, np.float64)
+    if task == "bicycle":
+        e.x, e.z, e.theta, e.phi, e.phi_dot, e.delta = (float(v) for v in st[:6])
+        e.goal_pos = st[6:8].copy()
+        e.dist_to_goal = np.float64(st[8])
+        e.steps = int(st[9])
+    elif task == "brickbreak":
+        e.paddle_x = float(st[0])
+        e.ball_pos, e.ball_vel = st[1:3].copy(), st[3:5].copy()
+        e.steps = int(st[5])
+        e.bricks = st[6:46].reshape(5, 8).copy()
+    elif task == "glider":
+        e.pos, e.vel, e.rot, e.ang_vel = st[0:3].copy(), st[3:6].copy(), st[6:9].copy(), st[9:12].copy()
+        e.current_waypoint_index = int(st[12])
+        e.steps = int(st[13])
+    else:
+        raise KeyError(task)
+    env.steps = e.steps
+
+
+sys.path.insert(0, os.path.dirname(OUT))
+from _edges import STEPS_AT, actions_of  # noqa: E402  (tests/_edges.py: the label convention and the state layout, defined once)
+
+LO, HI = 1e-6, 1e-3  # margins of a trig / sqrt-dependent deciding quantity from its threshold, relative to max(1, |threshold|)
+
+
+def deciding(task: str, env, st_in):
+    """(name, value, threshold) of every comparison of the step just taken whose left side went through sqrt / sin / cos / tan / arctan2,
+    recomputed from the reference's own state with the reference's own expressions."""
+    e = env.env
+    if task == "bicycle":
+        return [("new_dist", float(e.dist_to_goal), 2.0), ("phi", abs(float(e.phi)), float(e.max_phi))]
+    if task == "glider":
+        dist = float(np.linalg.norm(e.waypoints[int(st_in[12])] - e.pos))
+        v_air = st_in[3:6] - e._wind_model(st_in[0:3])
+        vam = float(np.linalg.norm(v_air))
+        q = [("dist", dist, 15.0), ("dist", dist, 500.0), ("lateral", abs(float(e.pos[1])), 250.0), ("alt", float(e.pos[2]), 250.0),
+             ("alt", float(e.pos[2]), 25.0), ("alt", float(e.pos[2]), 5.0), ("vam", vam, 0.1)]
+        if vam > 0.1 and v_air[0] != 0:
+            q.append(("aoa", abs(float(np.arctan2(-v_air[2], v_air[0]))), float(e.max_aoa)))
+        return q
+    return []  # brickbreak: add / multiply / compare only, its rows sit exactly on the thresholds
+
+
+def record_edges(mod, task: str, rows):
+    """rows: (label, state_in, action, near) with near = names of the deciding quantities the label puts just inside / outside."""
+    env = factory(mod, task)()
+    env.reset(seed=1)
+    out = {k: [] for k in ("state_in", "action", "state_out", "obs64", "obs32", "rew64", "rew32", "terminated", "truncated", "labels")}
+    for label, st_in, act, near in rows:
+        st_in = np.asarray(st_in, np.float64)
+        set_state(task, env, st_in)
+        assert np.array_equal(get_state(task, env), st_in), label
+        o32, r, te, tr, info = env.step(int(act))
+        assert isinstance(r, float) and isinstance(te, bool) and isinstance(tr, bool) and o32.dtype == np.float32
+        assert info["steps"] == env.env.steps == int(st_in[STEPS_AT[task]]) + 1
+        o64 = np.asarray(env.env._get_obs(), np.float64)  # a pure function of the state: the float64 array step() returned
+        assert np.array_equal(o64.astype(np.float32), o32), label
+        found = set()
+        for name, val, thr in deciding(task, env, st_in):
+            scale = max(1.0, abs(thr))
+            assert abs(val - thr) >= LO * scale, (label, act, name, val, thr)
+            if name in near and abs(val - thr) <= HI * scale:
+                found.add(name)
+        assert found == set(near), (label, act, near, found, deciding(task, env, st_in))
+        for k, v in (("state_in", st_in), ("action", act), ("state_out", get_state(task, env)), ("obs64", o64), ("obs32", o32), ("rew64", r),
+                     ("rew32", np.float32(r)), ("terminated", te), ("truncated", tr), ("labels", label)):
+            out[k].append(v)
+    d = dict(state_in=np.stack(out["state_in"]), action=np.array(out["action"], np.int32), state_out=np.stack(out["state_out"]),
+             obs64=np.stack(out["obs64"]), obs32=np.stack(out["obs32"]), rew64=np.array(out["rew64"], np.float64),
+             rew32=np.array(out["rew32"], np.float32), terminated=np.array(out["terminated"], np.bool_),
+             truncated=np.array(out["truncated"], np.bool_), labels=np.array(out["labels"]))
+    return d
+
+
+def bicycle_edges(mod):
+    env = factory(mod, "bicycle")()
+    e = env.env
+    dt, max_phi, max_delta = e.dt, float(e.max_phi), float(e.max_delta)
+    rows = []
+
+    def add(label, *, goal_d=12.0, phi_out=None, steps=10, delta=0.1, x=0.3, z=-0.2, theta=0.4, phi=0.05, near=()):
+        for a in actions_of("bicycle", label):
+            # phi' = phi + (phi_dot + phi_ddot * dt) * dt with phi_ddot free of phi_dot, x' and z' free of phi: one probe step gives both
+            set_state("bicycle", env, [x, z, theta, phi, 0.0, delta, 0.0, 0.0, 0.0, steps])
+            e.step(a)
+            phi_dot = 0.02 if phi_out is None else (phi_out - e.phi) / dt
+            goal = np.array([e.x + goal_d * np.cos(0.7), e.z + goal_d * np.sin(0.7)])
+            dist_in = np.linalg.norm(goal - np.array([x, z]))
+            rows.append((label, [x, z, theta, phi, phi_dot, delta, *goal, dist_in, steps], a, near))
+
+    m = 2e-4
+    add("goal_inside", goal_d=2.0 - m, near=("new_dist",))
+    add("goal_outside", goal_d=2.0 + m, near=("new_dist",))
+    for sign, tag in ((1.0, "pos"), (-1.0, "neg")):
+        add(f"fall_{tag}", phi_out=sign * (max_phi + m), phi=sign * 0.7, near=("phi",))
+        add(f"upright_{tag}", phi_out=sign * (max_phi - m), phi=sign * 0.7, near=("phi",))
+    add("goal_and_fall", goal_d=2.0 - m, phi_out=max_phi + m, phi=0.7, near=("new_dist", "phi"))
+    add("goal_and_upright", goal_d=2.0 - m, phi_out=max_phi - m, phi=0.7, near=("new_dist", "phi"))
+    add("fall_and_goal_outside", goal_d=2.0 + m, phi_out=-(max_phi + m), phi=-0.7, near=("new_dist", "phi"))
+    # the steering clip: delta + steer_change is an addition, the rows may sit anywhere
+    add("delta_clip_hi", delta=max_delta + 0.06)   # clipped under every action
+    add("delta_clip_lo", delta=-(max_delta + 0.06))
+    add("delta_below_clip_hi", delta=max_delta - 0.06)  # clipped under none
+    add("delta_above_clip_lo", delta=-(max_delta - 0.06))
+    add("delta_clip_hi_by_a2", delta=max_delta - 0.02)  # +0.05 crosses it
+    add("delta_clip_lo_by_a0", delta=-(max_delta - 0.02))
+    add("delta_near_clip_hi_a1", delta=max_delta - 0.02)  # the same states under the action that stays inside
+    add("delta_near_clip_lo_a1", delta=-(max_delta - 0.02))
+    for s in (1998, 1999, 2000):
+        add(f"steps{s}_continue", steps=s)
+        add(f"steps{s}_fall", steps=s, phi_out=max_phi + m, phi=0.7, near=("phi",))
+        add(f"steps{s}_goal", steps=s, goal_d=2.0 - m, near=("new_dist",))
+    # landing on the goal: theta' = 0 exactly (delta + steer_change == 0.0, tan(0) == 0), x' = 0 + 5 * 0.02 and z' = 0 + 0 need no libm value that
+    # could differ between hosts, so `new_dist == 0` (and 1e-9) is met by every implementation of the same arithmetic
+    for label, off in (("on_goal_exact", 0.0), ("on_goal_1e-9", 1e-9)):
+        for a in range(3):
+            delta = {0: 0.05, 1: 0.0, 2: -0.05}[a]
+            set_state("bicycle", env, [0.0, 0.0, 0.0, 0.05, 0.02, delta, 5.0, 5.0, 7.0, 10])
+            e.step(a)
+            assert e.theta == 0.0 and e.z == 0.0 and e.delta == 0.0
+            goal = np.array([e.x + off * 0.6, e.z + off * 0.8])
+            rows.append((label, [0.0, 0.0, 0.0, 0.05, 0.02, delta, *goal, np.linalg.norm(goal), 10], a, ()))
+    # start states for multi-step replays: `pre_<x>_a1` is one no-steer step before a state whose outcome (`any_<x>`, recorded from that one
+    # state under every action) does not depend on the action -- margins of 0.05 / 0.01 against an action's 5e-4 on the position and the lean
+    def after(st, actions):
+        set_state("bicycle", env, st)
+        for a in actions:
+            e.step(a)
+        return get_state("bicycle", env)
+
+    def pre_any(tag, st):
+        rows.append((f"pre_{tag}_a1", st, 1, ()))
+        for a in range(3):
+            rows.append((f"any_{tag}", after(st, [1]), a, ()))
+
+    base = [0.3, -0.2, 0.4, 0.05, 0.02, 0.0, 0.0, 0.0, 0.0, 10]
+    two = after(base, [1, 1])
+    goal = [two[0] + 1.95 * np.cos(two[2]), two[1] + 1.95 * np.sin(two[2])]  # 2.05 away after one step, 1.95 after two
+    pre_any("goal", [*base[:6], *goal, np.hypot(goal[0] - base[0], goal[1] - base[1]), 10])
+    far = [base[0] + 12.0 * np.cos(0.7), base[1] + 12.0 * np.sin(0.7)]
+    pre_any("continue", [*base[:6], *far, 12.0, 10])
+    lo, hi = 0.6, 0.8  # phi of the start state by bisection: phi'' = max_phi + 0.01 with phi_dot = 1 rad/s, i.e. phi' ~ max_phi - 0.01
+    for _ in range(60):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if after([0.3, -0.2, 0.4, mid, 1.0, 0.0, *far, 12.0, 10], [1, 1])[3] < max_phi + 0.01 else (lo, mid)
+    pre_any("fall", [0.3, -0.2, 0.4, lo, 1.0, 0.0, *far, 12.0, 10])
+    d = record_edges(mod, "bicycle", rows)
+    nd = d["state_out"][:, 8]
+    assert np.all(nd[d["labels"] == "on_goal_exact"] == 0.0)
+    assert np.all((nd[d["labels"] == "on_goal_1e-9"] > 0) & (nd[d["labels"] == "on_goal_1e-9"] <= 1e-9))
+    return d
+
+
+def brickbreak_edges(mod):
+    def nxt(thr, toward, v=None):
+        """The float64 next to `thr` on the side of `toward` that a ball moving by `v` per step can land on exactly."""
+        t = np.nextafter(thr, toward)
+        while v is not None and (t - v) + v != t:
+            t = np.nextafter(t, toward)
+        assert abs(t - thr) <= 4e-15 * thr
+        return t
+
+    FULL = np.ones((5, 8))
+    rows = []
+
+    def add(label, ball_out, vel, *, paddle_out=8.0, paddle_in=None, steps=10, bricks=FULL):
+        for a in actions_of("brickbreak", label):
+            p_in = paddle_in if paddle_in is not None else paddle_out - {0: -3.0, 1: 0.0, 2: 3.0}[a]
+            ball_out_, vel_ = np.asarray(ball_out, np.float64), np.asarray(vel, np.float64)
+            ball_in = ball_out_ - vel_
+            assert np.array_equal(ball_in + vel_, ball_out_), (label, ball_in, vel_)  # the step lands exactly where the label says
+            rows.append((label, [p_in, *ball_in, *vel_, steps, *np.asarray(bricks, np.float64).flatten()], a, ()))
+
+    def only(*cells):
+        b = np.zeros((5, 8))
+        for r, c in cells:
+            b[r, c] = 1.0
+        return b
+
+    def without(*cells):
+        b = FULL.copy()
+        for r, c in cells:
+            b[r, c] = 0.0
+        return b
+
+    up, down = (0.5, 1.0), (0.25, -1.0)
+    add("win_last_brick", (17.5, 25.0), up, bricks=only((2, 3)))
+    add("win_and_lost", (20.0, 0.5), down, bricks=only())
+    add("win_no_bricks_midair", (20.0, 12.0), up, bricks=only())
+    add("two_bricks_left_hit_one", (17.5, 25.0), up, bricks=only((2, 3), (4, 7)))
+    # walls: `<= ball_radius`, `>= width - ball_radius`, `>= height - ball_radius`
+    add("wall_left_on", (1.0, 12.0), (-0.5, 1.0))
+    add("wall_left_off", (nxt(1.0, 2.0, -0.5), 12.0), (-0.5, 1.0))
+    add("wall_right_on", (39.0, 12.0), (0.5, 1.0))
+    add("wall_right_off", (nxt(39.0, 0.0, 0.5), 12.0), (0.5, 1.0))
+    add("ceiling_on", (12.5, 39.0), (0.5, 1.0))
+    add("ceiling_off", (12.5, nxt(39.0, 0.0, 1.0)), (0.5, 1.0))
+    # paddle: `vel_y < 0`, `ball_y - ball_radius <= 2`, `paddle_x - 4 <= ball_x <= paddle_x + 4`
+    P = 20.0
+    add("paddle_band_on", (21.0, 3.0), down, paddle_out=P)
+    add("paddle_band_off", (21.0, nxt(3.0, 4.0, -1.0)), down, paddle_out=P)
+    add("paddle_left_on", (P - 4.0, 2.5), down, paddle_out=P)
+    add("paddle_left_off", (nxt(P - 4.0, 0.0, 0.25), 2.5), down, paddle_out=P)
+    add("paddle_right_on", (P + 4.0, 2.5), down, paddle_out=P)
+    add("paddle_right_off", (nxt(P + 4.0, 40.0, 0.25), 2.5), down, paddle_out=P)
+    add("paddle_ball_rising", (21.0, 2.5), (0.25, 1.0), paddle_out=P)
+    add("paddle_ball_level", (21.0, 2.5), (0.25, 0.0), paddle_out=P)
+    # lost: `ball_y < ball_radius`
+    add("lost_on", (30.0, 1.0), down)
+    add("lost_off", (30.0, nxt(1.0, 0.0, -1.0)), down)
+    add("paddle_hit_and_lost", (21.0, 0.5), down, paddle_out=P)
+    # the paddle's own clip at paddle_width / 2 and width - paddle_width / 2
+    add("paddle_clip_lo", (20.0, 12.0), up, paddle_in=0.5)
+    add("paddle_clip_hi", (20.0, 12.0), up, paddle_in=39.5)
+    add("paddle_at_lo", (20.0, 12.0), up, paddle_in=4.0)
+    add("paddle_at_hi", (20.0, 12.0), up, paddle_in=36.0)
+    add("paddle_lands_on_lo_a0", (20.0, 12.0), up, paddle_in=7.0)
+    add("paddle_lands_on_hi_a2", (20.0, 12.0), up, paddle_in=33.0)
+    # brick edges, `>=` / `<=` on both axes, and the row-major order of the scan on shared edges
+    add("brick_bottom_on", (17.5, 20.0), up)
+    add("brick_bottom_off", (17.5, nxt(20.0, 0.0, 1.0)), up)
+    add("brick_top_on", (17.5, 30.0), up)
+    add("brick_top_off", (17.5, nxt(30.0, 40.0, 1.0)), up)
+    add("xedge_both", (20.0, 25.0), up)
+    add("xedge_lower_gone", (20.0, 25.0), up, bricks=without((2, 3)))
+    add("xedge_upper_gone", (20.0, 25.0), up, bricks=without((2, 4)))
+    add("xedge_both_gone", (20.0, 25.0), up, bricks=without((2, 3), (2, 4)))
+    add("yedge_both", (17.5, 24.0), up)
+    add("yedge_lower_gone", (17.5, 24.0), up, bricks=without((1, 3)))
+    add("yedge_upper_gone", (17.5, 24.0), up, bricks=without((2, 3)))
+    corner = [(1, 3), (1, 4), (2, 3), (2, 4)]
+    for k in range(5):
+        add(f"corner_gone{k}", (20.0, 24.0), up, bricks=without(*corner[:k]))
+    add("wall_left_and_brick", (0.5, 21.0), (-0.5, 1.0))
+    add("wall_right_and_brick", (39.5, 29.0), (0.5, 1.0))
+    for s in (1998, 1999):
+        add(f"steps{s}_continue", (20.0, 12.0), up, steps=s)
+        add(f"steps{s}_lost", (30.0, 0.5), down, steps=s)
+        add(f"steps{s}_brick", (17.5, 25.0), up, steps=s)
+        add(f"steps{s}_win", (17.5, 25.0), up, steps=s, bricks=only((2, 3)))
+    # start states for multi-step replays (see bicycle_edges): the ball is two steps from its target, out of the paddle's reach either way
+    def pre_any(tag, ball_out, vel, bricks):
+        ball_out, vel = np.asarray(ball_out, np.float64), np.asarray(vel, np.float64)
+        flat = np.asarray(bricks, np.float64).flatten()
+        rows.append((f"pre_{tag}_a1", [8.0, *(ball_out - 2 * vel), *vel, 10, *flat], 1, ()))
+        for a in range(3):
+            rows.append((f"any_{tag}", [8.0, *(ball_out - vel), *vel, 11, *flat], a, ()))
+
+    pre_any("win", (17.5, 21.0), (0.5, 1.5), only((0, 3)))
+    pre_any("lost", (30.0, 0.5), (0.25, -1.0), FULL)
+    pre_any("continue", (20.0, 12.0), (0.5, 1.0), FULL)
+    return record_edges(mod, "brickbreak", rows)
+
+
+def glider_edges(mod):
+    env = factory(mod, "glider")()
+    e = env.env
+    dt, max_aoa = e.dt, float(e.max_aoa)
+    WP = [w.copy() for w in e.waypoints]
+    U = np.array([0.48, 0.6, 0.64])  # a unit vector
+    rows = []
+
+    def va_at(aoa, mag=14.0, side=-0.5):
+        return np.array([mag * np.cos(aoa), side, -mag * np.sin(aoa)])
+
+    def add(label, pos_out, *, va=None, vel_x=None, rot=(0.1, -0.05, 0.3), ang_vel=(0.02, -0.03, 0.01), wp=0, steps=10, near=()):
+        """Solve pos_in so that the step lands on pos_out: pos' = pos + vel' * dt, and vel' depends on pos only through the wind at (x, y)."""
+        va_ = va_at(np.arctan2(1.0, 14.0)) if va is None else np.asarray(va, np.float64)
+        pos_out = np.asarray(pos_out, np.float64)
+        for a in actions_of("glider", label):
+            pos_in = pos_out - np.array([15.0, 0.0, -1.0]) * dt
+            for _ in range(12):
+                vel_in = e._wind_model(pos_in) + va_
+                if vel_x is not None:
+                    vel_in[0] = vel_x  # exactly, whatever the wind
+                st = [*pos_in, *vel_in, *rot, *ang_vel, wp, steps]
+                set_state("glider", env, st)
+                e.step(a)
+                pos_in = pos_in + (pos_out - e.pos)
+            rows.append((label, st, a, near))
+
+    cruise = np.array([10.0, 20.0, 100.0])
+    add("cruise", cruise)
+    for w in (0, 1):
+        add(f"wp{w}_reached", WP[w] + (15.0 - 1.5e-3) * U, wp=w, near=("dist",))
+        add(f"wp{w}_missed", WP[w] + (15.0 + 1.5e-3) * U, wp=w, near=("dist",))
+    for sign, tag in ((1.0, "pos"), (-1.0, "neg")):
+        add(f"corridor_{tag}_outside", [10.0, sign * (250.0 + 0.025), 100.0], near=("lateral",))
+        add(f"corridor_{tag}_inside", [10.0, sign * (250.0 - 0.025), 100.0], near=("lateral",))
+        add(f"corridor_{tag}_far", [10.0, sign * 300.0, 100.0])
+    add("alt_high_over", [10.0, 20.0, 250.0 + 0.025], near=("alt",))
+    add("alt_high_under", [10.0, 20.0, 250.0 - 0.025], near=("alt",))
+    add("alt_high_far", [10.0, 20.0, 300.0])
+    add("alt_low_under", [10.0, 20.0, 25.0 - 2.5e-3], near=("alt",))
+    add("alt_low_over", [10.0, 20.0, 25.0 + 2.5e-3], near=("alt",))
+    add("crash", [10.0, 20.0, 5.0 - 5e-4], near=("alt",))
+    add("no_crash", [10.0, 20.0, 5.0 + 5e-4], near=("alt",))
+    for sign, tag in ((1.0, "pos"), (-1.0, "neg")):
+        add(f"stall_{tag}", cruise, va=va_at(sign * (max_aoa + 1e-4)), near=("aoa",))
+        add(f"no_stall_{tag}", cruise, va=va_at(sign * (max_aoa - 1e-4)), near=("aoa",))
+    far = WP[0] + np.array([500.0, 0.0, 0.0])
+    add("too_far", far + [0.05, 0.0, 0.0], near=("dist",))
+    add("not_too_far", far - [0.05, 0.0, 0.0], near=("dist",))
+    add("crash_and_stall", [10.0, 20.0, 5.0 - 5e-4], va=va_at(max_aoa + 1e-4), near=("alt", "aoa"))
+    add("crash_and_too_far", [far[0] + 0.5, 0.0, 5.0 - 5e-4], near=("alt",))
+    add("stall_and_too_far", far + [0.05, 0.0, 0.0], va=va_at(-(max_aoa + 1e-4)), near=("dist", "aoa"))
+    add("crash_stall_too_far", [far[0] + 0.5, 0.0, 5.0 - 5e-4], va=va_at(max_aoa + 1e-4), near=("alt", "aoa"))
+    # `v_air_mag > 0.1`: below it the aerodynamic force and the angle of attack are dropped, so a 30-degree v_air stalls on one side only
+    add("vair_over_steep", cruise, va=va_at(np.pi / 6, mag=0.1 + 1e-4, side=0.0), near=("vam",))
+    add("vair_under_steep", cruise, va=va_at(np.pi / 6, mag=0.1 - 1e-4, side=0.0), near=("vam",))
+    add("vair_over_level", cruise, va=va_at(0.0, mag=0.1 + 1e-4, side=0.0), near=("vam",))
+    add("vair_under_level", cruise, va=va_at(0.0, mag=0.1 - 1e-4, side=0.0), near=("vam",))
+    # `v_air[0] != 0`: vel[0] == 1.0 exactly against the wind's constant 1.0 (a subtraction, no margin needed) drops an angle of attack of 56 degrees
+    add("vair_x_zero", cruise, va=(0.0, 2.0, -3.0), vel_x=1.0)
+    add("vair_x_tiny", cruise, va=(0.0, 2.0, -3.0), vel_x=1.0 + 1e-3)
+    # roll / pitch clamps (additions and a clip: the rows may sit anywhere): 0.95 * (2 -+ 0.3) * 0.02 carries every action past the bound
+    add("roll_clamp_hi", cruise, rot=(float(e.max_roll) - 1e-3, -0.05, 0.3), ang_vel=(2.0, -0.03, 0.01))
+    add("roll_clamp_lo", cruise, rot=(-float(e.max_roll) + 1e-3, -0.05, 0.3), ang_vel=(-2.0, -0.03, 0.01))
+    add("pitch_clamp_hi", cruise, rot=(0.1, float(e.max_pitch) - 1e-3, 0.3), ang_vel=(0.02, 2.0, 0.01))
+    add("pitch_clamp_lo", cruise, rot=(0.1, -float(e.max_pitch) + 1e-3, 0.3), ang_vel=(0.02, -2.0, 0.01))
+    for s in (3998, 3999):
+        add(f"steps{s}_cruise", cruise, steps=s)
+        add(f"steps{s}_crash", [10.0, 20.0, 5.0 - 5e-4], steps=s, near=("alt",))
+        add(f"steps{s}_wp_reached", WP[1] + (15.0 - 1.5e-3) * U, wp=1, steps=s, near=("dist",))
+    # start states for multi-step replays (see bicycle_edges): `pre_<x>_a0` lands on `any_<x>`'s state, whose next step crosses 5 m / the 15 m
+    # waypoint sphere by 8e-3 / 0.1 -- an action moves that step's landing point by 2e-5
+    def solve_two(pos_two, wp):
+        pos_two = np.asarray(pos_two, np.float64)
+        pos_in = pos_two - 2 * np.array([15.0, 0.0, -1.0]) * dt
+        for _ in range(12):
+            st = [*pos_in, *(e._wind_model(pos_in) + va_at(np.arctan2(1.0, 14.0))), 0.1, -0.05, 0.3, 0.02, -0.03, 0.01, wp, 10]
+            set_state("glider", env, st)
+            e.step(0)
+            mid = get_state("glider", env)
+            e.step(0)
+            pos_in = pos_in + (pos_two - e.pos)
+        return st, mid
+
+    def pre_any(tag, pos_two, wp=0):
+        st, mid = solve_two(pos_two, wp)
+        rows.append((f"pre_{tag}_a0", st, 0, ()))
+        for a in range(5):
+            rows.append((f"any_{tag}", mid, a, ()))
+
+    _, mid = solve_two([-40.0, 20.0, 5.0], 0)  # (x = -40: an 8 m/s downdraft of the wind model, the glider sinks through both steps)
+    sink = mid[2] - 5.0  # height lost per step on this glide path: the crash row crosses 5 m in the middle of its second step
+    assert sink > 4e-3, sink
+    pre_any("crash", [-40.0, 20.0, 5.0 - sink / 2])
+    pre_any("cruise", cruise)
+    pre_any("wp_reached", WP[1] - 14.9 * np.array([15.0, 0.0, -1.0]) / np.linalg.norm([15.0, 0.0, -1.0]), wp=1)
+    return record_edges(mod, "glider", rows)
+
+
+def save_npz_reproducible(path: str, d: dict) -> None:
+    """np.savez_compressed stamps every member with the wall clock; this writes the same container with a fixed stamp, so that a second
+    run gives the same bytes."""
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key, val in d.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w", force_zip64=True) as fid:
+                np.lib.format.write_array(fid, np.asanyarray(val), allow_pickle=False)
+
+
+def edges_main():
+    mod = load_reference_envs()
+    for task, build in (("bicycle", bicycle_edges), ("brickbreak", brickbreak_edges), ("glider", glider_edges)):
+        d = build(mod)
+        path = os.path.join(OUT, f"{task}_edges.npz")
+        save_npz_reproducible(path, d)
+        labels, counts = np.unique(d["labels"], return_counts=True)
+        print(task, "edges:", len(d["labels"]), "rows,", len(labels), "labels ->", path, os.path.getsize(path), "B")
+        print("   ", ", ".join(f"{l} x{c}" for l, c in zip(labels, counts)))
+
+
 FLOAT_TASKS = ("bicycle", "brickbreak", "glider")
 NO_AVX512 = "AVX512F AVX512CD AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL AVX512_SPR"
 
@@ -372,6 +761,12 @@ NO_AVX512 = "AVX512F AVX512CD AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL AVX512
 def main():
     os.makedirs(OUT, exist_ok=True)
     want = sys.argv[1:]
+    if want == ["edges"]:  # the edge fixtures only; none of the files below is touched
+        if os.environ.get("NPY_DISABLE_CPU_FEATURES") != NO_AVX512:
+            subprocess.check_call([sys.executable, os.path.abspath(__file__), "edges"], env={**os.environ, "NPY_DISABLE_CPU_FEATURES": NO_AVX512})
+        else:
+            edges_main()
+        return
     cfg = {
         # task: (n_envs, T, base_seed, tape_seed)
         "basic": (8, 400, 1, 11),
