@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 224
+#define TMA_VERSION 225
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -511,6 +511,101 @@ int tma_replay_sample(const tma_replay *rb, int size, int newest, int n_step, do
  * any HIP call: q / actions_out NULL, n < 1, A outside [2, 16], eps outside [0, 1] or NaN. */
 int tma_egreedy_actions(const float *q, int64_t n, int A, double eps, uint32_t rng_seed, uint32_t rng_step, uint32_t env_offset, int32_t *actions_out,
                         void *stream);
+
+/* ---- DQN (ABI 225): SB3's DQN (3P: stable_baselines3/dqn/dqn.py; the reference's default for its Discrete tasks, backend/mlagents/training.py:343-360)
+ *      -- csrc/tma_dqn.hip, DESIGN.md section 17.
+ * The Q-network is the `pi.*` segment of a Discrete tma_policy_dims parameter buffer: pi.W1 ... pi.b3 is SB3's QNetwork features -> H -> H -> A; the
+ * `vf.*` segment is never read.  The target net is a second buffer of the same layout (tma_policy_param_count floats).  Shapes: continuous 0,
+ * mfma_dtype 0, activation tanh or ReLU, hidden 64 / 128 / 256, 2 <= act_dim <= 16, obs_dim <= 128.  Everything else is refused with
+ * TMA_ERR_INVALID and a message before any HIP call, as are the NULLs and ranges each entry lists. */
+/* The Q forward of the pi segment and the epsilon-greedy pick in ONE launch.  Per row exactly tma_egreedy_actions' rule and hash on this launch's
+ * own Q row (same rng_seed / rng_step / env_offset meaning, first maximal column, a NaN never wins).  actions_out i32[n]; q_out f32[n][act_dim] or
+ * NULL (skipped).  A workgroup of four waves per 16-row tile, the hidden columns split over the waves; the grid is capped and strides.  The Q of
+ * a row has the bits tma_dqn_td_grad's online forward gives the same row (one device function), whatever the batch either came in.
+ * Refused: NULL d / params / obs / actions_out, n < 1, eps outside [0, 1] or NaN. */
+int tma_dqn_act(const float *params, const tma_policy_dims *d, const float *obs, int64_t n, double eps, uint32_t rng_seed, uint32_t rng_step,
+                uint32_t env_offset, int32_t *actions_out, float *q_out, void *stream);
+/* The loss side of DQN.train for one batch, the inputs being what tma_replay_sample writes (obs f32[n][D], actions i32[n], next_obs f32[n][D], dones,
+ * rewards, discounts f32[n]):
+ *   y_i = rewards_i + (1 - dones_i) * discounts_i * max_a Q_target(next_obs_i, a)     (no gradient through y)
+ *   delta_i = Q(obs_i, actions_i) - y_i;   loss = mean_i smooth_l1(delta_i), beta = 1: the cotangent clamp(delta_i, -1, 1) / n on column actions_i
+ * and the gradient with respect to the pi segment.  grad_out[n_trainable] is OVERWRITTEN, the vf segment (and log_std: none, Discrete) with exact
+ * zeros.  stats_out (device, may be NULL): three float64 -- sum_i smooth_l1(delta_i), sum_i Q(obs_i, actions_i), n -- so loss = stats[0] / stats[2].
+ * q_out (may be NULL): f32[n][act_dim], the online Q the loss used (the bits tma_dqn_act gives the same rows).
+ * `params` must be synced (the [out][in] copies of pi.W2 / pi.W3 are read); of target_params only the trainable [in][out] matrices are read.
+ * An action outside [0, act_dim) is only ever compared with column indices (it never addresses memory): its cotangent lands in no column, so the row
+ * adds nothing to the gradient, and its Q taken is NaN, which the two sums of stats_out then carry (tma_policy_evaluate_actions' rule).
+ * Two launches; both forwards, the loss and the backward inside the first.  No float atomics: a gradient element is summed over the rows of a tile in
+ * row order, over a workgroup's tiles in order, over the workgroups (at most 64: then they stride) in order -- equal inputs give equal bits.
+ * `workspace`: tma_dqn_workspace_bytes(d, n) bytes of device memory, bounded whatever n (64 x the pi segment + 64 x 24 bytes at the most; 0 + message
+ * for refused dims / n < 1).  Refused: NULL d / params / target_params / any input / grad_out, n < 1, a workspace that is NULL or too small. */
+int64_t tma_dqn_workspace_bytes(const tma_policy_dims *d, int64_t n);
+int tma_dqn_td_grad(const float *params, const float *target_params, const tma_policy_dims *d, const float *obs, const int32_t *actions,
+                    const float *next_obs, const float *dones, const float *rewards, const float *discounts, int64_t n, float *grad_out,
+                    double *stats_out, float *q_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* SB3's polyak_update over the trainable vector, element-wise in f32: target = tau * params + (1 - tau) * target (two products and a sum, nothing
+ * fused); tau == 1 is a pure copy with the source's bits.  Then tma_policy_sync(target_params): the derived copies the tma_policy_* kernels read
+ * from the target buffer (the DQN kernels read none of them).  Refused: NULL buffers, params == target_params, tau outside (0, 1] or NaN. */
+int tma_dqn_target_update(const float *params, float *target_params, const tma_policy_dims *d, double tau, void *stream);
+typedef struct {
+    int64_t total_timesteps;        /* SB3's _total_timesteps: the denominator of the exploration schedule */
+    int64_t learning_starts;
+    int64_t batch_size;
+    int64_t target_update_interval; /* in env steps: the target update runs when n_calls % max(target_update_interval / n_envs, 1) == 0 */
+    int train_freq;                 /* vector steps collected per iteration */
+    int gradient_steps;             /* optimizer steps per iteration; -1: train_freq */
+    int n_step;                     /* tma_replay_sample's n_step */
+    double tau, gamma;
+    double exploration_fraction, exploration_initial_eps, exploration_final_eps;
+    double learning_rate, max_grad_norm;
+    uint32_t rng_seed;              /* tma_dqn_act's rng_seed */
+    uint32_t sample_seed;           /* tma_replay_sample's seed */
+    uint32_t env_offset;
+} tma_dqn_hparams;
+/* Device memory the native loop works in, all caller-owned.  N = the replay view's n_envs, D = obs_dim, B = batch_size. */
+typedef struct {
+    float *last_obs;      /* [N][D] in/out: the observation the next action is chosen from (ReplayBuffer.last_obs) */
+    int32_t *actions;     /* [N] */
+    float *step_obs;      /* [N][D] */
+    float *rewards;       /* [N] */
+    uint8_t *term, *trunc; /* [N] */
+    float *term_obs;      /* [N][D] */
+    float *s_obs;         /* [B][D]  the sampled batch */
+    int32_t *s_actions;   /* [B] */
+    float *s_next_obs;    /* [B][D] */
+    float *s_dones, *s_rewards, *s_discounts; /* [B] */
+    float *grad, *exp_avg, *exp_avg_sq; /* [n_trainable] */
+    double *stats;        /* [3] tma_dqn_td_grad's stats_out of the last optimizer step; may be NULL */
+    void *td_workspace;   /* tma_dqn_workspace_bytes(d, B) */
+    int64_t td_workspace_bytes;
+    void *opt_workspace;  /* tma_ppo_workspace_bytes(d): tma_ppo_adam_step_local's */
+} tma_dqn_buffers;
+/* Host counters, in/out: every decision of the loop is host arithmetic on them. */
+typedef struct {
+    int64_t num_timesteps; /* env steps taken (SB3's num_timesteps) */
+    int64_t n_calls;       /* vector steps taken (SB3's _n_calls) */
+    int64_t pos;           /* the ring row the next vector step is written to */
+    int32_t full;          /* the ring has wrapped */
+    uint32_t draw;         /* tma_replay_sample's draw counter of the next batch */
+    uint32_t collect_step; /* tma_dqn_act's rng_step of the next vector step */
+    int64_t adam_step;     /* optimizer steps taken: the next one is Adam step adam_step + 1 */
+    int64_t n_updates;     /* SB3's _n_updates */
+} tma_dqn_counters;
+/* The exploration rate of the vector step taken at `num_timesteps` (host arithmetic, no GPU): 1 below learning_starts (SB3's uniform warm-up), else
+ * SB3's get_linear_fn(initial, final, fraction) at progress_remaining = 1 - num_timesteps / total_timesteps, taken BEFORE the step. */
+double tma_dqn_epsilon(const tma_dqn_hparams *hp, int64_t num_timesteps);
+/* n_iters iterations of SB3's DQN.learn in one call, on the caller's stream, with no device -> host read and no synchronisation.  An iteration:
+ * train_freq vector steps of  tma_dqn_act(last_obs, eps = tma_dqn_epsilon(hp, num_timesteps), rng_step = collect_step) -> tma_env_step (one step,
+ * with term_obs) -> tma_replay_add(pos);  then collect_step += 1, pos advances (wraps, sets full), num_timesteps += N, n_calls += 1, and
+ * tma_dqn_target_update(tau) where n_calls % max(target_update_interval / N, 1) == 0.  Then, if num_timesteps > learning_starts, gradient_steps times:
+ * tma_replay_sample(size, newest from pos / full; draw) -> tma_dqn_td_grad -> tma_ppo_adam_step_local(step adam_step + 1, beta (0.9, 0.999),
+ * eps 1e-8 -- torch Adam's default, which SB3's DQN uses --, max_grad_norm, last_count 0: the norm is taken from the gradient itself);  draw,
+ * adam_step and n_updates advance.  The same launches in the same order as the calls issued one by one, hence the same bits.  `params` must be
+ * synced on entry and is on return.  Refused before any HIP call: NULL arguments or buffers, bad dims, n_iters < 1, train_freq / batch_size /
+ * target_update_interval < 1, gradient_steps 0 or below -1, exploration_fraction outside (0, 1], a replay view that is Box or of another obs_dim,
+ * counters out of range.  The env handle, tau, n_step and the sample geometry are checked by the calls they go to. */
+int tma_dqn_iterations_local(tma_env *env, float *params, float *target_params, const tma_policy_dims *d, const tma_replay *rb, const tma_dqn_buffers *b,
+                             const tma_dqn_hparams *hp, tma_dqn_counters *c, int n_iters, void *stream);
 
 /* Profiling aid for bench.py's roofline object: when enabled, tma_ppo_minibatch_grad brackets its DOMINANT kernel (the persistent
  * forward+backward kernel; for two-pass shapes both passes; not the advantage pass, not the slab reduction) with HIP events recorded on

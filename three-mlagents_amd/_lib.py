@@ -57,6 +57,25 @@ class Replay(C.Structure):  # include/tma.h tma_replay: the planes of a replay b
                 ("n_envs", _i64), ("obs_dim", _i32), ("act_dim", _i32), ("continuous", _i32)]
 
 
+class DQNHParams(C.Structure):  # include/tma.h tma_dqn_hparams
+    _fields_ = [("total_timesteps", _i64), ("learning_starts", _i64), ("batch_size", _i64), ("target_update_interval", _i64), ("train_freq", _i32),
+                ("gradient_steps", _i32), ("n_step", _i32), ("tau", _f64), ("gamma", _f64), ("exploration_fraction", _f64),
+                ("exploration_initial_eps", _f64), ("exploration_final_eps", _f64), ("learning_rate", _f64), ("max_grad_norm", _f64),
+                ("rng_seed", _u32), ("sample_seed", _u32), ("env_offset", _u32)]
+
+
+class DQNBuffers(C.Structure):  # include/tma.h tma_dqn_buffers
+    _fields_ = [("last_obs", _vp), ("actions", _vp), ("step_obs", _vp), ("rewards", _vp), ("term", _vp), ("trunc", _vp), ("term_obs", _vp),
+                ("s_obs", _vp), ("s_actions", _vp), ("s_next_obs", _vp), ("s_dones", _vp), ("s_rewards", _vp), ("s_discounts", _vp),
+                ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("stats", _vp), ("td_workspace", _vp), ("td_workspace_bytes", _i64),
+                ("opt_workspace", _vp)]
+
+
+class DQNCounters(C.Structure):  # include/tma.h tma_dqn_counters
+    _fields_ = [("num_timesteps", _i64), ("n_calls", _i64), ("pos", _i64), ("full", _i32), ("draw", _u32), ("collect_step", _u32),
+                ("adam_step", _i64), ("n_updates", _i64)]
+
+
 _pd = C.POINTER(PolicyDims)
 
 # name -> (restype, argtypes); every symbol include/tma.h declares
@@ -126,6 +145,13 @@ SIGNATURES = {
     "tma_replay_add": (_i32, [C.POINTER(Replay), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tma_replay_sample": (_i32, [C.POINTER(Replay), _i32, _i32, _i32, _f64, _u32, _u32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tma_egreedy_actions": (_i32, [_vp, _i64, _i32, _f64, _u32, _u32, _u32, _vp, _vp]),
+    "tma_dqn_act": (_i32, [_vp, _pd, _vp, _i64, _f64, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "tma_dqn_workspace_bytes": (_i64, [_pd, _i64]),
+    "tma_dqn_td_grad": (_i32, [_vp, _vp, _pd, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tma_dqn_target_update": (_i32, [_vp, _vp, _pd, _f64, _vp]),
+    "tma_dqn_epsilon": (_f64, [C.POINTER(DQNHParams), _i64]),
+    "tma_dqn_iterations_local": (_i32, [_vp, _vp, _vp, _pd, C.POINTER(Replay), C.POINTER(DQNBuffers), C.POINTER(DQNHParams), C.POINTER(DQNCounters),
+                                        _i32, _vp]),
     "tma_ppo_persist_fallbacks": (_i32, [_vp, C.POINTER(_i64), _vp]),
     "tma_ppo_train_epoch_local": (_i32, [_vp, _pd, C.POINTER(Rollout), _u32, _u32, _i64, C.POINTER(PPOHParams), _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64,
                                          _f64, _vp, _vp]),

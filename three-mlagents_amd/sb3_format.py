@@ -85,12 +85,13 @@ def serialized(blob: bytes, type_name: str, **readable) -> dict[str, Any]:
     return {":type:": type_name, ":serialized:": base64.b64encode(blob).decode(), **readable}
 
 
-def data_members(observation_space, action_space) -> dict[str, Any]:
-    """The three members of `data` BaseAlgorithm.load needs as live objects."""
+def data_members(observation_space, action_space, policy_class: tuple[str, str] = POLICY_CLASS) -> dict[str, Any]:
+    """The three members of `data` BaseAlgorithm.load needs as live objects.  policy_class: (module, name) of the class SB3 would pickle by
+    reference -- ActorCriticPolicy for PPO / A2C, `("stable_baselines3.dqn.policies", "DQNPolicy")` for DQN."""
     om, on, _ = space_state(observation_space)
     am, an, _ = space_state(action_space)
     return {
-        "policy_class": serialized(class_reference_pickle(*POLICY_CLASS), "<class 'abc.ABCMeta'>", __module__=POLICY_CLASS[0]),
+        "policy_class": serialized(class_reference_pickle(*policy_class), "<class 'abc.ABCMeta'>", __module__=policy_class[0]),
         "observation_space": serialized(space_pickle(observation_space), f"<class '{om}.{on}'>", _shape=list(observation_space.shape)),
         "action_space": serialized(space_pickle(action_space), f"<class '{am}.{an}'>", _shape=list(action_space.shape)),
     }
