@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 225
+#define TMA_VERSION 226
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -606,6 +606,133 @@ double tma_dqn_epsilon(const tma_dqn_hparams *hp, int64_t num_timesteps);
  * counters out of range.  The env handle, tau, n_step and the sample geometry are checked by the calls they go to. */
 int tma_dqn_iterations_local(tma_env *env, float *params, float *target_params, const tma_policy_dims *d, const tma_replay *rb, const tma_dqn_buffers *b,
                              const tma_dqn_hparams *hp, tma_dqn_counters *c, int n_iters, void *stream);
+
+/* ---- SAC (ABI 226): SB3's SAC (3P: stable_baselines3/sac/sac.py, SquashedDiagGaussianDistribution; the reference's off-policy choice for its Box
+ *      tasks, backend/mlagents/training.py:392-403) -- csrc/tma_sac.hip, DESIGN.md section 18.
+ * Shapes: hidden 64 / 128 / 256, 1 <= act_dim <= 8 (mu and log_std share one 16-column head tile), obs_dim + act_dim <= 128 (the critic's input
+ * tile), f32, activation ReLU (SB3's SAC default) or tanh, exactly two critics.  Everything else is refused with TMA_ERR_INVALID and a message
+ * before any HIP call, as are the NULLs and ranges each entry lists. */
+typedef struct tma_sac_dims {
+    int obs_dim, act_dim, hidden;
+    int activation; /* TMA_ACT_TANH | TMA_ACT_RELU */
+    int device;     /* HIP device ordinal, or -1: the current device */
+} tma_sac_dims;
+/* Float offsets into the flat [in][out] buffers, in SB3's tensor order.  Actor (n_actor floats): W1[D][H] b1 W2[H][H] b2 Wmu[H][A] bmu Wls[H][A]
+ * bls = actor.latent_pi.{0,2}, actor.mu, actor.log_std.  Critic (n_critic = 2 n_q floats): qf0 then qf1 (at n_q), each W1[D+A][H] b1 W2[H][H] b2
+ * W3[H][1] b3 with the observation rows of W1 first, then the action rows (SB3 concatenates obs | action); the q_* offsets are those inside ONE
+ * critic.  The critic target is a second buffer of the critic layout.  There are no derived copies: nothing needs a sync after a write. */
+typedef struct tma_sac_offsets {
+    int a_W1, a_b1, a_W2, a_b2, a_Wmu, a_bmu, a_Wls, a_bls, n_actor;
+    int q_W1, q_b1, q_W2, q_b2, q_W3, q_b3, n_q, n_critic;
+} tma_sac_offsets;
+int tma_sac_param_offsets(const tma_sac_dims *d, tma_sac_offsets *out);
+/* The arithmetic of one row, with noise z f32[A]:  ls = clamp(log_std_head, -20, 2);  u = mu + exp(ls) z;  a = tanh(u);
+ *   logp = sum_j (-z_j^2 / 2 - ls_j - log sqrt(2 pi)) - sum_j log(1 - a_j^2 + 1e-6)
+ * with expf / logf / tanhf (not the fast intrinsics).  Noise: every noise-consuming entry takes noise_in f32[n][A] (may be NULL) and noise_out
+ * (may be NULL).  With noise_in NULL, z of (row, column) is a Box-Muller pair of mix32 hashes of (seed ^ stream key, row id, draw), the stream key
+ * being distinct for tma_sac_act (collect), tma_sac_critic_grad (next action) and tma_sac_actor_grad (pi action); feeding a call's noise_out back
+ * as noise_in gives equal bits everywhere.  head_out (may be NULL): f32[n][2 A], the actor's mu then its log_std BEFORE the clamp -- one device
+ * function in all three entries, so a row has the same bits in all three whatever the batch it came in. */
+enum { TMA_SAC_SAMPLE = 0, TMA_SAC_DETERMINISTIC = 1, TMA_SAC_UNIFORM = 2 };
+/* Actor forward plus squash in ONE launch.  mode SAMPLE: the row id of the hash is row_offset + row;  DETERMINISTIC: z = 0, a = tanh(mu) (noise_in
+ * must be NULL; noise_out receives zeros);  UNIFORM: SB3's warm-up below learning_starts, a = 2 u01(mix32) - 1 in [-1, 1) per element without
+ * reading the net (actor / obs may be NULL; noise_in, logp_out, noise_out, head_out must be).  actions_out f32[n][A]; logp_out f32[n] or NULL.
+ * A workgroup of four waves per 16-row tile; the grid is capped and strides.  Refused: NULL d / actions_out, NULL actor / obs outside UNIFORM,
+ * n < 1, an unknown mode. */
+int tma_sac_act(const float *actor, const tma_sac_dims *d, const float *obs, int64_t n, int mode, uint32_t seed, uint32_t draw, uint32_t row_offset,
+                const float *noise_in, float *actions_out, float *logp_out, float *noise_out, float *head_out, void *stream);
+/* Bytes of device workspace either gradient call needs for n rows: at most 64 x (the wider of the critic pair and the actor) floats + 64 x 32
+ * bytes, bounded whatever n (0 + message for refused dims / n < 1). */
+int64_t tma_sac_workspace_bytes(const tma_sac_dims *d, int64_t n);
+/* The critic side of SAC.train for one batch (what tma_replay_sample writes: obs f32[n][D], actions f32[n][A], next_obs f32[n][D], dones,
+ * rewards, discounts f32[n]), with alpha = exp(log_ent_coef[0]) read from the device:
+ *   a', logp' = the actor on next_obs (row id = row);   y = rewards + (1 - dones) * discounts * (min(Qt0, Qt1)(next_obs, a') - alpha logp')
+ *   loss = 1/2 sum_i mean((Q_i(obs, actions) - y)^2)   (no gradient through y)
+ * grad_out[n_critic] is OVERWRITTEN with its gradient.  stats_out (device, may be NULL): four float64 -- the sum over rows of
+ * 1/2 ((Q0 - y)^2 + (Q1 - y)^2), sum Q0, sum Q1, n -- so critic_loss = stats[0] / stats[3].  q_out f32[n][2], target_out f32[n] (= y): optional.
+ * Two launches (tile pass, slab fold).  No float atomics: a gradient element is summed over the rows of a tile in row order, over a workgroup's
+ * tiles in order, over the workgroups (at most 64: then they stride) in order -- equal inputs give equal bits.
+ * Refused: NULL d / any parameter buffer / any input / grad_out, n < 1, a workspace that is NULL or below tma_sac_workspace_bytes(d, n). */
+int tma_sac_critic_grad(const float *actor, const float *critic, const float *critic_target, const float *log_ent_coef, const tma_sac_dims *d, const float *obs,
+                        const float *actions, const float *next_obs, const float *dones, const float *rewards, const float *discounts, int64_t n, uint32_t seed,
+                        uint32_t draw, const float *noise_in, float *grad_out, double *stats_out, float *q_out, float *target_out, float *noise_out,
+                        float *head_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* The actor side:  a_pi, logp_pi = the actor on obs;  loss = mean(alpha logp_pi - min(Q0, Q1)(obs, a_pi)), on a tie qf0 carries the gradient.  The
+ * backward goes through the winning critic's input gradient to the action rows only (no critic weight gradient is formed), then through the
+ * squash and logp (the clamp passes the gradient where -20 <= log_std_head <= 2, torch's rule) into the actor.  grad_out[n_actor] is OVERWRITTEN.
+ * stats_out (may be NULL): three float64 -- sum of (alpha logp_pi - min Q), sum of logp_pi, n.  actions_out f32[n][A], logp_out f32[n]: optional.
+ * Launches, order of sums, workspace and refusals as tma_sac_critic_grad. */
+int tma_sac_actor_grad(const float *actor, const float *critic, const float *log_ent_coef, const tma_sac_dims *d, const float *obs, int64_t n, uint32_t seed,
+                       uint32_t draw, const float *noise_in, float *grad_out, double *stats_out, float *actions_out, float *logp_out, float *noise_out,
+                       float *head_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* ent_coef="auto":  grad_out[0] = d/d log_ent_coef of -(log_ent_coef * (logp_pi + target_entropy)).mean() = -(stats[1] / stats[2] +
+ * target_entropy), the mean taken in float64 from tma_sac_actor_grad's stats_out, rounded once to f32.  One launch of one thread. */
+int tma_sac_ent_coef_grad(const double *actor_stats, double target_entropy, float *grad_out, void *stream);
+/* torch.optim.Adam (no weight decay, no amsgrad, no clipping) on a flat f32 vector of n >= 1 elements, element-wise with the IEEE square root and
+ * division:  m += (g - m)(1 - beta1);  v = v beta2 + g^2 (1 - beta2);  p -= (lr / (1 - beta1^step)) * (m / (sqrt(v) / sqrt(1 - beta2^step) + eps)),
+ * the two bias corrections worked out on the host in double.  Steps the actor, the critic pair and the single log_ent_coef; there are no derived
+ * copies to refresh.  Refused: NULL buffers, n < 1, step < 1, lr / eps below 0 or NaN, a beta outside [0, 1). */
+int tma_adam_step_flat(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, double lr, double beta1, double beta2,
+                       double eps, void *stream);
+/* SB3's polyak_update on a flat range with tma_dqn_target_update's arithmetic: target = tau * params + (1 - tau) * target in f32 (two rounded
+ * products and a sum, nothing fused); tau == 1 copies bits.  Refused: NULL buffers, n < 1, tau outside (0, 1] or NaN, params == target. */
+int tma_polyak_update(const float *params, float *target, int64_t n, double tau, void *stream);
+typedef struct {
+    int64_t learning_starts;
+    int64_t batch_size;
+    int64_t target_update_interval; /* in optimizer steps: the polyak update follows the step taken at n_updates % interval == 0 */
+    int train_freq;                 /* vector steps collected per iteration */
+    int gradient_steps;             /* optimizer steps per iteration; -1: train_freq, one per VECTOR step collected (SB3: train_freq * n_envs) */
+    int n_step;                     /* tma_replay_sample's n_step */
+    int auto_ent_coef;              /* 1: ent_coef="auto" (the log_ent_coef step runs); 0: a fixed alpha */
+    double tau, gamma, learning_rate, target_entropy;
+    uint32_t rng_seed;              /* the noise seed of the three streams */
+    uint32_t sample_seed;           /* tma_replay_sample's seed */
+    uint32_t env_offset;            /* tma_sac_act's row_offset */
+} tma_sac_hparams;
+/* Device memory the native loop works in, all caller-owned.  N = the replay view's n_envs, D = obs_dim, A = act_dim, B = batch_size. */
+typedef struct {
+    float *last_obs;      /* [N][D] in/out: the observation the next action is chosen from */
+    float *actions;       /* [N][A] */
+    float *step_obs;      /* [N][D] */
+    float *rewards;       /* [N] */
+    uint8_t *term, *trunc; /* [N] */
+    float *term_obs;      /* [N][D] */
+    float *s_obs;         /* [B][D]  the sampled batch */
+    float *s_actions;     /* [B][A] */
+    float *s_next_obs;    /* [B][D] */
+    float *s_dones, *s_rewards, *s_discounts; /* [B] */
+    float *actor_grad, *actor_exp_avg, *actor_exp_avg_sq;    /* [n_actor] */
+    float *critic_grad, *critic_exp_avg, *critic_exp_avg_sq; /* [n_critic] */
+    float *ent_grad, *ent_exp_avg, *ent_exp_avg_sq;          /* [1] */
+    double *critic_stats; /* [4] tma_sac_critic_grad's stats_out of the last optimizer step */
+    double *actor_stats;  /* [3] tma_sac_actor_grad's */
+    void *workspace;      /* tma_sac_workspace_bytes(d, B) */
+    int64_t workspace_bytes;
+} tma_sac_buffers;
+/* Host counters, in/out: every decision of the loop is host arithmetic on them. */
+typedef struct {
+    int64_t num_timesteps; /* env steps taken */
+    int64_t n_calls;       /* vector steps taken */
+    int64_t pos;           /* the ring row the next vector step is written to */
+    int32_t full;          /* the ring has wrapped */
+    uint32_t draw;         /* tma_replay_sample's draw counter of the next batch, and the draw of its two noise streams */
+    uint32_t collect_step; /* tma_sac_act's draw of the next vector step */
+    int64_t adam_step;     /* optimizer steps taken: the next one is Adam step adam_step + 1 of all three optimizers */
+    int64_t n_updates;     /* SB3's _n_updates */
+} tma_sac_counters;
+/* n_iters iterations of SB3's SAC.learn in one call, on the caller's stream, with no device -> host read and no synchronisation.  An iteration:
+ * train_freq vector steps of  tma_sac_act(last_obs; UNIFORM while num_timesteps < learning_starts, else SAMPLE; draw = collect_step, row_offset =
+ * env_offset) -> tma_env_step (one step, f32 actions, with term_obs) -> tma_replay_add(pos);  then collect_step += 1, pos advances (wraps, sets
+ * full), num_timesteps += N, n_calls += 1.  Then, if num_timesteps > learning_starts, gradient_steps times:  tma_replay_sample(size, newest from
+ * pos / full; draw) -> tma_sac_critic_grad(draw) -> tma_adam_step_flat(critic) -> tma_sac_actor_grad(draw; the critics AFTER their step, as SB3)
+ * -> tma_adam_step_flat(actor) -> [auto_ent_coef: tma_sac_ent_coef_grad -> tma_adam_step_flat(log_ent_coef); both gradient kernels have read
+ * the pre-step alpha by then] -> tma_polyak_update(critic -> critic_target, tau) where n_updates % target_update_interval == 0;  Adam with beta
+ * (0.9, 0.999), eps 1e-8, step adam_step + 1;  then draw, adam_step and n_updates advance.  The same launches in the same order as the calls
+ * issued one by one, hence the same bits.  Refused before any HIP call: NULL arguments or buffers, bad dims, n_iters < 1, train_freq /
+ * batch_size / target_update_interval < 1, gradient_steps 0 or below -1, a replay view that is Discrete or of other dims, counters out of range. */
+int tma_sac_iterations_local(tma_env *env, float *actor, float *critic, float *critic_target, float *log_ent_coef, const tma_sac_dims *d, const tma_replay *rb,
+                             const tma_sac_buffers *b, const tma_sac_hparams *hp, tma_sac_counters *c, int n_iters, void *stream);
 
 /* Profiling aid for bench.py's roofline object: when enabled, tma_ppo_minibatch_grad brackets its DOMINANT kernel (the persistent
  * forward+backward kernel; for two-pass shapes both passes; not the advantage pass, not the slab reduction) with HIP events recorded on

@@ -8,7 +8,7 @@ __version__ = "0.2.0"
 
 from .tasks import ENGINE_TASKS, EngineTask, make_env, resolve  # noqa: E402
 
-__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C", "DQN", "RolloutBuffer", "RolloutBufferSamples", "ReplayBuffer",
+__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C", "DQN", "SAC", "RolloutBuffer", "RolloutBufferSamples", "ReplayBuffer",
            "ReplayBufferSamples"]
 
 
@@ -25,6 +25,10 @@ def __getattr__(name):  # the algorithm classes import torch: on first use, not 
         from .dqn import DQN
 
         return DQN
+    if name == "SAC":
+        from .sac import SAC
+
+        return SAC
     if name in ("RolloutBuffer", "RolloutBufferSamples"):
         from . import rollout_buffer
 

@@ -76,7 +76,39 @@ class DQNCounters(C.Structure):  # include/tma.h tma_dqn_counters
                 ("adam_step", _i64), ("n_updates", _i64)]
 
 
+SAC_SAMPLE, SAC_DETERMINISTIC, SAC_UNIFORM = 0, 1, 2  # include/tma.h TMA_SAC_*: tma_sac_act's mode
+SAC_GRID_CAP = 64  # csrc/tma_sac.hip SAC_GRID_CAP: workgroups of a gradient kernel at the most; the tests size a case past it
+
+
+class SACDims(C.Structure):  # include/tma.h tma_sac_dims
+    _fields_ = [("obs_dim", _i32), ("act_dim", _i32), ("hidden", _i32), ("activation", _i32), ("device", _i32)]
+
+
+class SACOffsets(C.Structure):  # include/tma.h tma_sac_offsets
+    _fields_ = [(k, _i32) for k in ("a_W1", "a_b1", "a_W2", "a_b2", "a_Wmu", "a_bmu", "a_Wls", "a_bls", "n_actor",
+                                    "q_W1", "q_b1", "q_W2", "q_b2", "q_W3", "q_b3", "n_q", "n_critic")]
+
+
+class SACHParams(C.Structure):  # include/tma.h tma_sac_hparams
+    _fields_ = [("learning_starts", _i64), ("batch_size", _i64), ("target_update_interval", _i64), ("train_freq", _i32), ("gradient_steps", _i32),
+                ("n_step", _i32), ("auto_ent_coef", _i32), ("tau", _f64), ("gamma", _f64), ("learning_rate", _f64), ("target_entropy", _f64),
+                ("rng_seed", _u32), ("sample_seed", _u32), ("env_offset", _u32)]
+
+
+class SACBuffers(C.Structure):  # include/tma.h tma_sac_buffers
+    _fields_ = [(k, _vp) for k in ("last_obs", "actions", "step_obs", "rewards", "term", "trunc", "term_obs", "s_obs", "s_actions", "s_next_obs", "s_dones",
+                                   "s_rewards", "s_discounts", "actor_grad", "actor_exp_avg", "actor_exp_avg_sq", "critic_grad", "critic_exp_avg",
+                                   "critic_exp_avg_sq", "ent_grad", "ent_exp_avg", "ent_exp_avg_sq", "critic_stats", "actor_stats", "workspace")] + [
+                                       ("workspace_bytes", _i64)]
+
+
+class SACCounters(C.Structure):  # include/tma.h tma_sac_counters
+    _fields_ = [("num_timesteps", _i64), ("n_calls", _i64), ("pos", _i64), ("full", _i32), ("draw", _u32), ("collect_step", _u32),
+                ("adam_step", _i64), ("n_updates", _i64)]
+
+
 _pd = C.POINTER(PolicyDims)
+_sd = C.POINTER(SACDims)
 
 # name -> (restype, argtypes); every symbol include/tma.h declares
 SIGNATURES = {
@@ -151,6 +183,16 @@ SIGNATURES = {
     "tma_dqn_target_update": (_i32, [_vp, _vp, _pd, _f64, _vp]),
     "tma_dqn_epsilon": (_f64, [C.POINTER(DQNHParams), _i64]),
     "tma_dqn_iterations_local": (_i32, [_vp, _vp, _vp, _pd, C.POINTER(Replay), C.POINTER(DQNBuffers), C.POINTER(DQNHParams), C.POINTER(DQNCounters),
+                                        _i32, _vp]),
+    "tma_sac_param_offsets": (_i32, [_sd, C.POINTER(SACOffsets)]),
+    "tma_sac_act": (_i32, [_vp, _sd, _vp, _i64, _i32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tma_sac_workspace_bytes": (_i64, [_sd, _i64]),
+    "tma_sac_critic_grad": (_i32, [_vp, _vp, _vp, _vp, _sd, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tma_sac_actor_grad": (_i32, [_vp, _vp, _vp, _sd, _vp, _i64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tma_sac_ent_coef_grad": (_i32, [_vp, _f64, _vp, _vp]),
+    "tma_adam_step_flat": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _f64, _f64, _f64, _f64, _vp]),
+    "tma_polyak_update": (_i32, [_vp, _vp, _i64, _f64, _vp]),
+    "tma_sac_iterations_local": (_i32, [_vp, _vp, _vp, _vp, _vp, _sd, C.POINTER(Replay), C.POINTER(SACBuffers), C.POINTER(SACHParams), C.POINTER(SACCounters),
                                         _i32, _vp]),
     "tma_ppo_persist_fallbacks": (_i32, [_vp, C.POINTER(_i64), _vp]),
     "tma_ppo_train_epoch_local": (_i32, [_vp, _pd, C.POINTER(Rollout), _u32, _u32, _i64, C.POINTER(PPOHParams), _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64,

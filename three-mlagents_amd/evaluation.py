@@ -60,6 +60,10 @@ def evaluate_policy_begin(model, env, n_eval_episodes: int = 10, deterministic: 
     eng = env.engine
     if getattr(model, "env", None) is env:  # the training env: its episode log feeds the Monitor file -- leave it alone
         return {"stepwise": evaluate_policy_stepwise(model, env, n_eval_episodes, deterministic, True, True, max_steps)}
+    from .ppo import HipActorCriticPolicy
+
+    if not isinstance(model.policy, HipActorCriticPolicy):  # (SAC's policy: the chunked rollout is tied to tma_policy_dims)
+        return {"stepwise": evaluate_policy_stepwise(model, env, n_eval_episodes, deterministic, True, True, max_steps)}
     n = eng.num_envs
     pol = model.policy
     if pol.device != eng.device:

@@ -26,10 +26,11 @@ from .callbacks import CallbackList, EvalCallback
 from .evaluation import evaluate_policy
 from .a2c import A2C
 from .ppo import PPO
+from .sac import SAC
 from .vec_env import HipVecEnv
 
 POLICIES_DIR, RUNS_DIR = (Path(name) for name in ("policies", "runs"))
-ALGORITHMS = dict(ppo=PPO, a2c=A2C)  # the algorithms with an MI355X implementation (the reference's table: training.py:31-37)
+ALGORITHMS = dict(ppo=PPO, a2c=A2C, sac=SAC)  # the algorithms with an MI355X implementation (the reference's table: training.py:31-37)
 EVAL_ENVS = int(os.environ.get("TMA_EVAL_ENVS", "128"))  # width of the evaluation vector (train_task / evaluate_model): up to one env per episode
 _SB3_NAMES = {"a2c", "dqn", "ppo", "sac", "td3"}  # what the reference's table accepts (training.py:31-37)
 
@@ -70,14 +71,21 @@ def ppo_defaults(task: tasks.EngineTask, n_envs: int | None = None) -> dict[str,
                 ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5, policy_kwargs={"net_arch": {"pi": width, "vf": list(width)}, **extra})
 
 
-def model_defaults(algo: str, task: tasks.EngineTask, n_envs: int | None = None) -> dict[str, Any]:
+def model_defaults(algo: str, task: tasks.EngineTask, n_envs: int | None = None, total_timesteps: int | None = None) -> dict[str, Any]:
     """Hyper-parameters per algorithm, next to tensorboard_log and verbose: PPO's value table; nothing for A2C, which the reference constructs with
-    SB3's defaults (its _default_model_kwargs returns only those two)."""
+    SB3's defaults (its _default_model_kwargs returns only those two); SAC's value table (training.py:392-403), which depends on the budget."""
+    if algo == "sac":
+        budget = int(total_timesteps or task.total_timesteps)
+        return dict(learning_rate=3e-4, buffer_size=max(100_000, min(1_000_000, budget)), learning_starts=min(10_000, max(1_000, budget // 20)),
+                    batch_size=256, gamma=0.99, tau=0.005, train_freq=1, gradient_steps=1)
     return ppo_defaults(task, n_envs) if algo == "ppo" else {}
 
 
 def _schedule(algo: str, model, n_envs: int, model_kwargs) -> dict[str, Any]:
-    """metadata.json `schedule`: how a rollout is cut into optimizer steps."""
+    """metadata.json `schedule`: how a rollout is cut into optimizer steps (SAC: how collected steps and optimizer steps alternate)."""
+    if algo == "sac":
+        return dict(batch_size=model.batch_size, train_freq=model.train_freq, gradient_steps=model.gradient_steps, learning_starts=model.learning_starts,
+                    buffer_size=model.buffer_size, n_envs=n_envs)
     if algo != "ppo":  # A2C: one optimizer step over the whole rollout
         return dict(n_steps=model.n_steps, n_envs=n_envs, samples_per_update=n_envs * model.n_steps, updates_per_rollout=1)
     return dict(batch_size=model.batch_size, n_steps=model.n_steps, n_epochs=model.n_epochs, n_envs=n_envs,
@@ -146,6 +154,14 @@ def train_task(config, *, callback=None, model_kwargs=None):
                       f"(recorded as substituted_for in metadata.json)", stacklevel=2)
     budget = int(config.total_timesteps or task.total_timesteps)
     n_envs = int(config.n_envs or task.n_envs)
+    if algo == "sac":
+        n_envs = 1  # the reference trains its off-policy algorithms on one env (training.py:118-119)
+        from .spaces import task_spaces
+
+        if hasattr(task_spaces(task.kernel)[1], "n"):
+            raise ValueError(f"algorithm 'sac' needs a Box action space; task '{task.id}' has a Discrete one")
+        if config.normalize:
+            raise ValueError("normalize=True is not supported with algorithm 'sac' (SAC has no VecNormalize form)")
     episodes = int(config.eval_episodes or task.eval_episodes)
     run = _Run(task, config.run_name or f"{task.id}_{algo}_{time.strftime('%Y%m%d_%H%M%S')}_{secrets.token_hex(4)}")
     with contextlib.ExitStack() as stack:
@@ -163,7 +179,7 @@ def train_task(config, *, callback=None, model_kwargs=None):
         # With config.normalize, SB3's recipe: VecNormalize around the training vector; the evaluation vector gets a frozen one (training=False)
         # whose statistics are synced from the training one before each evaluation (EvalCallback; below for the final one).
         venv, eval_env = opened(n_envs, 0, run.monitor), opened(max(1, min(EVAL_ENVS, episodes)), 10_000, training=False)
-        hp = {**model_defaults(algo, task, n_envs), "tensorboard_log": str(run.tb), "verbose": config.verbose, **(model_kwargs or {})}
+        hp = {**model_defaults(algo, task, n_envs, budget), "tensorboard_log": str(run.tb), "verbose": config.verbose, **(model_kwargs or {})}
         model = ALGORITHMS[algo](config.policy or "MlpPolicy", venv, seed=config.seed, **hp)
         ev = dict(n_eval_episodes=episodes, deterministic=config.deterministic_eval)
         hooks = [EvalCallback(eval_env, log_path=str(run.eval), best_model_save_path=str(run.best), verbose=config.verbose,
