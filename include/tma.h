@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define TMA_VERSION 226
+#define TMA_VERSION 227
 
 enum { TMA_OK = 0, TMA_ERR_INVALID = 1, TMA_ERR_UNKNOWN_TASK = 2, TMA_ERR_HIP = 3 };
 
@@ -733,6 +733,115 @@ typedef struct {
  * batch_size / target_update_interval < 1, gradient_steps 0 or below -1, a replay view that is Discrete or of other dims, counters out of range. */
 int tma_sac_iterations_local(tma_env *env, float *actor, float *critic, float *critic_target, float *log_ent_coef, const tma_sac_dims *d, const tma_replay *rb,
                              const tma_sac_buffers *b, const tma_sac_hparams *hp, tma_sac_counters *c, int n_iters, void *stream);
+
+/* ---- TD3 (ABI 227): SB3's TD3 (3P: stable_baselines3/td3/td3.py; the reference's fifth algorithm, with SAC's value table,
+ *      backend/mlagents/training.py:31-37, 392-403) -- csrc/tma_td3.hip, DESIGN.md section 19.
+ * Shapes: tma_sac_dims and its contract (hidden 64 / 128 / 256, 1 <= act_dim <= 8, obs_dim + act_dim <= 128, f32, ReLU -- SB3's TD3 default -- or
+ * tanh, exactly two critics), refused the same way.  Four flat [in][out] buffers in SB3's tensor order: the actor (n_actor floats) W1[D][H] b1
+ * W2[H][H] b2 Wmu[H][A] bmu = actor.mu.{0,2,4}; the actor target, a second buffer of that layout; the critic pair and the critic target in SAC's
+ * critic layout exactly (the q_* offsets equal tma_sac_param_offsets').  No derived copies. */
+typedef struct tma_td3_offsets {
+    int a_W1, a_b1, a_W2, a_b2, a_Wmu, a_bmu, n_actor;
+    int q_W1, q_b1, q_W2, q_b2, q_W3, q_b3, n_q, n_critic;
+} tma_td3_offsets;
+int tma_td3_param_offsets(const tma_sac_dims *d, tma_td3_offsets *out);
+/* SB3's NormalActionNoise per action column: noise_j = mean[j] + sigma[j] z_j.  Read on the host at the call and handed to the kernel by value;
+ * columns at and behind act_dim are ignored. */
+typedef struct tma_td3_noise {
+    float mean[8], sigma[8];
+} tma_td3_noise;
+enum { TMA_TD3_DETERMINISTIC = 0, TMA_TD3_NOISY = 1, TMA_TD3_UNIFORM = 2 };
+/* Actor forward and tanh in ONE launch: mu = the actor on obs, a = tanhf(mu).  mode DETERMINISTIC: a alone (noise_in must be NULL; noise_out
+ * receives zeros; action_noise is ignored);  NOISY: a = clamp(tanhf(mu) + (mean_j + sigma_j z), -1, 1), SB3's action noise on the squashed action
+ * -- z f32[n][A] from noise_in, or with noise_in NULL a Box-Muller pair of mix32 hashes of (seed ^ the collect stream key, row_offset + row,
+ * draw), tma_sac_act's generator under a key of its own; action_noise must not be NULL, its sigmas at least 0;  UNIFORM: SB3's warm-up below
+ * learning_starts with tma_sac_act's arithmetic and bits, the net is not read (actor / obs / action_noise may be NULL; noise_in, noise_out,
+ * head_out must be).  actions_out f32[n][A];  noise_out f32[n][A] (z) and head_out f32[n][A] (mu BEFORE the tanh) may be NULL.  The actor
+ * forward is one device function in all three TD3 entries: a row's mu has the same bits in each, whatever the batch it came in.  A workgroup of
+ * four waves per 16-row tile; the grid is capped and strides.  Refused: NULL d / actions_out, NULL actor / obs outside UNIFORM, n < 1, an unknown
+ * mode, NOISY without action_noise or with a negative / NaN sigma or a NaN mean. */
+int tma_td3_act(const float *actor, const tma_sac_dims *d, const float *obs, int64_t n, int mode, const tma_td3_noise *action_noise, uint32_t seed,
+                uint32_t draw, uint32_t row_offset, const float *noise_in, float *actions_out, float *noise_out, float *head_out, void *stream);
+/* Bytes of device workspace either gradient call needs for n rows: at most 64 x (the wider of the critic pair and the actor) floats + 64 x 32
+ * bytes, bounded whatever n (0 + message for refused dims / n < 1). */
+int64_t tma_td3_workspace_bytes(const tma_sac_dims *d, int64_t n);
+/* The critic side of TD3.train for one batch (what tma_replay_sample writes), no gradient through y:
+ *   eps = clamp(target_policy_noise z, -target_noise_clip, +target_noise_clip);   a' = clamp(tanhf(mu_target(next_obs)) + eps, -1, 1)
+ *   y = rewards + (1 - dones) * discounts * min(Qt0, Qt1)(next_obs, a');          loss = sum_i mean((Q_i(obs, actions) - y)^2)
+ * SB3's sum(F.mse_loss(...)): the cotangent of Q_i is 2 (Q_i - y) / n (SAC's carries a 1/2).  z f32[n][A] from noise_in, or with noise_in NULL
+ * generated from (seed ^ the target stream key, row, draw) -- a key distinct from tma_td3_act's.  grad_out[n_critic] is OVERWRITTEN.  stats_out
+ * (device, may be NULL): four float64 -- the sum over rows of (Q0 - y)^2 + (Q1 - y)^2, sum Q0, sum Q1, n -- so critic_loss = stats[0] /
+ * stats[3].  Optional: q_out f32[n][2], target_out f32[n] (= y), noise_out f32[n][A] (z), head_out f32[n][A] (mu_target(next_obs)).  Two
+ * launches (tile pass, slab fold).  No float atomics; order of sums as tma_sac_critic_grad.  Refused: NULL d / any parameter buffer / any input /
+ * grad_out, n < 1, a negative or NaN target_policy_noise / target_noise_clip, a workspace that is NULL or below tma_td3_workspace_bytes(d, n). */
+int tma_td3_critic_grad(const float *actor_target, const float *critic, const float *critic_target, const tma_sac_dims *d, const float *obs, const float *actions,
+                        const float *next_obs, const float *dones, const float *rewards, const float *discounts, int64_t n, double target_policy_noise,
+                        double target_noise_clip, uint32_t seed, uint32_t draw, const float *noise_in, float *grad_out, double *stats_out, float *q_out,
+                        float *target_out, float *noise_out, float *head_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* The actor side:  loss = -mean(Q0(obs, tanhf(mu(obs)))).  Only qf0 (the front n_q floats of `critic`) is read: its forward, its input gradient
+ * down to the action rows of its W1 (no critic weight gradient is formed), through the tanh, then the actor's backward.  grad_out[n_actor] is
+ * OVERWRITTEN.  stats_out (may be NULL): two float64 -- the sum of -Q0, n.  Optional: actions_out f32[n][A], head_out f32[n][A] (mu).  Launches,
+ * order of sums, workspace and refusals as tma_td3_critic_grad. */
+int tma_td3_actor_grad(const float *actor, const float *critic, const tma_sac_dims *d, const float *obs, int64_t n, float *grad_out, double *stats_out,
+                       float *actions_out, float *head_out, void *workspace, int64_t workspace_bytes, void *stream);
+typedef struct {
+    int64_t learning_starts;
+    int64_t batch_size;
+    int64_t policy_delay;     /* the actor step and both target updates follow the critic step where n_updates % policy_delay == 0 */
+    int train_freq;           /* vector steps collected per iteration */
+    int gradient_steps;       /* optimizer steps per iteration; -1: train_freq, one per VECTOR step collected */
+    int n_step;               /* tma_replay_sample's n_step */
+    int use_action_noise;     /* 1: collect in the NOISY mode with action_noise; 0: DETERMINISTIC */
+    double tau, gamma, learning_rate, target_policy_noise, target_noise_clip;
+    tma_td3_noise action_noise;
+    uint32_t rng_seed;        /* the noise seed of both streams and of the warm-up */
+    uint32_t sample_seed;     /* tma_replay_sample's seed */
+    uint32_t env_offset;      /* tma_td3_act's row_offset */
+} tma_td3_hparams;
+/* Device memory the native loop works in, all caller-owned; the fields of tma_sac_buffers without the entropy coefficient's. */
+typedef struct {
+    float *last_obs;      /* [N][D] in/out */
+    float *actions;       /* [N][A] */
+    float *step_obs;      /* [N][D] */
+    float *rewards;       /* [N] */
+    uint8_t *term, *trunc; /* [N] */
+    float *term_obs;      /* [N][D] */
+    float *s_obs;         /* [B][D]  the sampled batch */
+    float *s_actions;     /* [B][A] */
+    float *s_next_obs;    /* [B][D] */
+    float *s_dones, *s_rewards, *s_discounts; /* [B] */
+    float *actor_grad, *actor_exp_avg, *actor_exp_avg_sq;    /* [n_actor] */
+    float *critic_grad, *critic_exp_avg, *critic_exp_avg_sq; /* [n_critic] */
+    double *critic_stats; /* [4] tma_td3_critic_grad's stats_out of the last optimizer step */
+    double *actor_stats;  /* [2] tma_td3_actor_grad's, of the last actor step */
+    void *workspace;      /* tma_td3_workspace_bytes(d, B) */
+    int64_t workspace_bytes;
+} tma_td3_buffers;
+/* Host counters, in/out: every decision of the loop is host arithmetic on them. */
+typedef struct {
+    int64_t num_timesteps;    /* env steps taken */
+    int64_t n_calls;          /* vector steps taken */
+    int64_t pos;              /* the ring row the next vector step is written to */
+    int32_t full;             /* the ring has wrapped */
+    uint32_t draw;            /* tma_replay_sample's draw counter of the next batch, and the draw of its target noise */
+    uint32_t collect_step;    /* tma_td3_act's draw of the next vector step */
+    int64_t critic_adam_step; /* critic steps taken: the next one is Adam step critic_adam_step + 1 */
+    int64_t actor_adam_step;  /* actor steps taken (one per policy_delay critic steps) */
+    int64_t n_updates;        /* SB3's _n_updates */
+} tma_td3_counters;
+/* n_iters iterations of SB3's TD3.learn in one call, on the caller's stream, with no device -> host read and no synchronisation.  An iteration:
+ * train_freq vector steps of  tma_td3_act(last_obs; UNIFORM while num_timesteps < learning_starts, else NOISY where use_action_noise, else
+ * DETERMINISTIC; draw = collect_step, row_offset = env_offset) -> tma_env_step (one step, f32 actions, with term_obs) -> tma_replay_add(pos);
+ * then collect_step += 1, pos advances (wraps, sets full), num_timesteps += N, n_calls += 1.  Then, if num_timesteps > learning_starts,
+ * gradient_steps times:  n_updates += 1 -> tma_replay_sample(size, newest from pos / full; draw) -> tma_td3_critic_grad(actor_target; draw) ->
+ * tma_adam_step_flat(critic, step critic_adam_step + 1) -> where n_updates % policy_delay == 0: tma_td3_actor_grad (the critics AFTER their
+ * step, as SB3) -> tma_adam_step_flat(actor, step actor_adam_step + 1) -> tma_polyak_update(critic -> critic_target, tau) ->
+ * tma_polyak_update(actor -> actor_target, tau).  Adam with beta (0.9, 0.999), eps 1e-8.  The same launches in the same order as the calls issued
+ * one by one, hence the same bits.  Refused before any HIP call: NULL arguments or buffers, bad dims, n_iters < 1, train_freq / batch_size /
+ * policy_delay < 1, gradient_steps 0 or below -1, a negative target_policy_noise / target_noise_clip, a replay view that is Discrete or of other
+ * dims, counters out of range. */
+int tma_td3_iterations_local(tma_env *env, float *actor, float *actor_target, float *critic, float *critic_target, const tma_sac_dims *d, const tma_replay *rb,
+                             const tma_td3_buffers *b, const tma_td3_hparams *hp, tma_td3_counters *c, int n_iters, void *stream);
 
 /* Profiling aid for bench.py's roofline object: when enabled, tma_ppo_minibatch_grad brackets its DOMINANT kernel (the persistent
  * forward+backward kernel; for two-pass shapes both passes; not the advantage pass, not the slab reduction) with HIP events recorded on

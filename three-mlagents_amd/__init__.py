@@ -8,7 +8,7 @@ __version__ = "0.2.0"
 
 from .tasks import ENGINE_TASKS, EngineTask, make_env, resolve  # noqa: E402
 
-__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C", "DQN", "SAC", "RolloutBuffer", "RolloutBufferSamples", "ReplayBuffer",
+__all__ = ["ENGINE_TASKS", "EngineTask", "make_env", "resolve", "__version__", "PPO", "A2C", "DQN", "SAC", "TD3", "NormalActionNoise", "RolloutBuffer", "RolloutBufferSamples", "ReplayBuffer",
            "ReplayBufferSamples"]
 
 
@@ -29,6 +29,14 @@ def __getattr__(name):  # the algorithm classes import torch: on first use, not 
         from .sac import SAC
 
         return SAC
+    if name == "TD3":
+        from .td3 import TD3
+
+        return TD3
+    if name == "NormalActionNoise":
+        from .td3 import NormalActionNoise
+
+        return NormalActionNoise
     if name in ("RolloutBuffer", "RolloutBufferSamples"):
         from . import rollout_buffer
 

@@ -107,6 +107,34 @@ class SACCounters(C.Structure):  # include/tma.h tma_sac_counters
                 ("adam_step", _i64), ("n_updates", _i64)]
 
 
+TD3_DETERMINISTIC, TD3_NOISY, TD3_UNIFORM = 0, 1, 2  # include/tma.h TMA_TD3_*: tma_td3_act's mode
+
+
+class TD3Offsets(C.Structure):  # include/tma.h tma_td3_offsets
+    _fields_ = [(k, _i32) for k in ("a_W1", "a_b1", "a_W2", "a_b2", "a_Wmu", "a_bmu", "n_actor", "q_W1", "q_b1", "q_W2", "q_b2", "q_W3", "q_b3", "n_q", "n_critic")]
+
+
+class TD3Noise(C.Structure):  # include/tma.h tma_td3_noise
+    _fields_ = [("mean", C.c_float * 8), ("sigma", C.c_float * 8)]
+
+
+class TD3HParams(C.Structure):  # include/tma.h tma_td3_hparams
+    _fields_ = [("learning_starts", _i64), ("batch_size", _i64), ("policy_delay", _i64), ("train_freq", _i32), ("gradient_steps", _i32), ("n_step", _i32),
+                ("use_action_noise", _i32), ("tau", _f64), ("gamma", _f64), ("learning_rate", _f64), ("target_policy_noise", _f64),
+                ("target_noise_clip", _f64), ("action_noise", TD3Noise), ("rng_seed", _u32), ("sample_seed", _u32), ("env_offset", _u32)]
+
+
+class TD3Buffers(C.Structure):  # include/tma.h tma_td3_buffers
+    _fields_ = [(k, _vp) for k in ("last_obs", "actions", "step_obs", "rewards", "term", "trunc", "term_obs", "s_obs", "s_actions", "s_next_obs", "s_dones",
+                                   "s_rewards", "s_discounts", "actor_grad", "actor_exp_avg", "actor_exp_avg_sq", "critic_grad", "critic_exp_avg",
+                                   "critic_exp_avg_sq", "critic_stats", "actor_stats", "workspace")] + [("workspace_bytes", _i64)]
+
+
+class TD3Counters(C.Structure):  # include/tma.h tma_td3_counters
+    _fields_ = [("num_timesteps", _i64), ("n_calls", _i64), ("pos", _i64), ("full", _i32), ("draw", _u32), ("collect_step", _u32),
+                ("critic_adam_step", _i64), ("actor_adam_step", _i64), ("n_updates", _i64)]
+
+
 _pd = C.POINTER(PolicyDims)
 _sd = C.POINTER(SACDims)
 
@@ -193,6 +221,13 @@ SIGNATURES = {
     "tma_adam_step_flat": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _f64, _f64, _f64, _f64, _vp]),
     "tma_polyak_update": (_i32, [_vp, _vp, _i64, _f64, _vp]),
     "tma_sac_iterations_local": (_i32, [_vp, _vp, _vp, _vp, _vp, _sd, C.POINTER(Replay), C.POINTER(SACBuffers), C.POINTER(SACHParams), C.POINTER(SACCounters),
+                                        _i32, _vp]),
+    "tma_td3_param_offsets": (_i32, [_sd, C.POINTER(TD3Offsets)]),
+    "tma_td3_act": (_i32, [_vp, _sd, _vp, _i64, _i32, C.POINTER(TD3Noise), _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "tma_td3_workspace_bytes": (_i64, [_sd, _i64]),
+    "tma_td3_critic_grad": (_i32, [_vp, _vp, _vp, _sd, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tma_td3_actor_grad": (_i32, [_vp, _vp, _sd, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tma_td3_iterations_local": (_i32, [_vp, _vp, _vp, _vp, _vp, _sd, C.POINTER(Replay), C.POINTER(TD3Buffers), C.POINTER(TD3HParams), C.POINTER(TD3Counters),
                                         _i32, _vp]),
     "tma_ppo_persist_fallbacks": (_i32, [_vp, C.POINTER(_i64), _vp]),
     "tma_ppo_train_epoch_local": (_i32, [_vp, _pd, C.POINTER(Rollout), _u32, _u32, _i64, C.POINTER(PPOHParams), _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64,
