@@ -18,6 +18,8 @@
 //       blocks' (loss, Q taken, count) float64 partials in block order.
 // Order of one gradient element's sum: rows in order inside a tile (the MFMA's k order), a block's tiles in order, blocks in order: it depends on
 // (shape, n) alone, so equal inputs give equal bits.  The workspace is grid x (pi segment + 3 doubles), bounded by the grid cap whatever n.
+// The layer functions, mlp_trunk_tile (the two hidden layers of dqn_q_tile), TileStats, TILE_DISPATCH, tile_set_device and the native loop's
+// collect step and sample live in tma_dqn_tile.h, which tma_sac.hip and tma_td3.hip share; the target update runs tma_sac.hip's polyak kernel.
 #include "tma_dqn_tile.h"
 
 namespace tma {
@@ -31,10 +33,7 @@ constexpr uint32_t DQN_PICK_KEY = 0xE9517EEDu;  // tma_egreedy_actions' EGREEDY_
 template <int ACT, int NT>
 __device__ __forceinline__ void dqn_q_tile(const float *__restrict__ p, const PLayout &L, const float *X, float *h1, float *h2, float *q, int lane, int wave) {
     constexpr int H = 64 * NT, LD = H + 2;
-    dqn_dense<ACT, NT>(X, DQN_LDX, L.D, p + L.pW1t, p + L.pb1, H, h1, LD, lane, wave * 16 * NT);
-    __syncthreads();
-    dqn_dense<ACT, NT>(h1, LD, H, p + L.pW2t, p + L.pb2, H, h2, LD, lane, wave * 16 * NT);
-    __syncthreads();
+    mlp_trunk_tile<ACT, NT>(X, L.D, p, L.pW1t, L.pb1, L.pW2t, L.pb2, h1, h2, lane, wave);
     if (wave == 0) {
         f32x4 acc[1];
         dense_head<1>(h2, LD, H, p + L.pW3t, p + L.pb3, L.A, acc, lane);
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(256) void dqn_td_kernel(DqnTdArgs a) {
     float *slab = a.slabs + (int64_t)blockIdx.x * L.vW1t;
     const float nf = (float)a.n;
     const int64_t n_tiles = (a.n + 15) >> 4;
-    double loss_sum = 0.0, q_sum = 0.0, rows = 0.0;  // thread 0's
+    TileStats<2> stats;  // thread 0's: loss, Q taken
     bool first = true;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t row0 = tile << 4;
@@ -142,9 +141,7 @@ __global__ __launch_bounds__(256) void dqn_td_kernel(DqnTdArgs a) {
             }
         }
         __syncthreads();
-        if (tid == 0) {
-            for (int row = 0; row < 16 && row0 + row < a.n; row++) loss_sum += (double)rowstat[2 * row], q_sum += (double)rowstat[2 * row + 1], rows += 1.0;
-        }
+        if (tid == 0) stats.add_columns(row0, a.n, rowstat);
         dqn_wgrad(h2, LD, H, dz3, DQN_LDQ, A, slab + L.pW3t, first, lane, wave);
         dqn_bgrad(dz3, DQN_LDQ, A, slab + L.pb3, first, tid);
         __syncthreads();
@@ -160,10 +157,7 @@ __global__ __launch_bounds__(256) void dqn_td_kernel(DqnTdArgs a) {
         __syncthreads();  // (the next tile overwrites every buffer)
         first = false;
     }
-    if (tid == 0) {
-        double *p = a.parts + 3 * (int64_t)blockIdx.x;
-        p[0] = loss_sum, p[1] = q_sum, p[2] = rows;
-    }
+    if (tid == 0) stats.store<3>(a.parts);
 }
 
 __global__ __launch_bounds__(256) void dqn_reduce_kernel(const float *__restrict__ slabs, const double *__restrict__ parts, int nb, int n_pi, int P,
@@ -180,14 +174,6 @@ __global__ __launch_bounds__(256) void dqn_reduce_kernel(const float *__restrict
         double s0 = parts[0], s1 = parts[1], s2 = parts[2];
         for (int b = 1; b < nb; b++) s0 += parts[3 * b], s1 += parts[3 * b + 1], s2 += parts[3 * b + 2];
         stats[0] = s0, stats[1] = s1, stats[2] = s2;
-    }
-}
-
-// target <- tau * params + (1 - tau) * target in f32 (two products, one sum, nothing fused); tau == 1: a copy
-__global__ __launch_bounds__(256) void dqn_polyak_kernel(const float *__restrict__ params, float *__restrict__ target, int P, float tau, float omt, int copy) {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < P; e += gridDim.x * 256) {
-        const float p = params[e];
-        target[e] = copy ? p : tau * p + omt * target[e];
     }
 }
 
@@ -213,29 +199,7 @@ static int dqn_check(const tma_policy_dims *d, const char *who) {
     if (d->obs_dim < 1 || d->obs_dim > DQN_MAX_OBS) return fail(TMA_ERR_INVALID, "%s: obs_dim %d is outside [1, %d]", who, d->obs_dim, DQN_MAX_OBS);
     return TMA_OK;
 }
-static int dqn_set_device(const tma_policy_dims *d) {
-    if (d->device >= 0) {
-        int cur = -1;
-        TMA_HIP(hipGetDevice(&cur));
-        if (cur != d->device) TMA_HIP(hipSetDevice(d->device));
-    }
-    return TMA_OK;
-}
 static PLayout dqn_layout(const tma_policy_dims *d) { return make_layout(d->obs_dim, d->hidden, d->act_dim, 0, 0, d->activation); }
-
-// f(kernel template instance) for (activation, H)
-#define DQN_DISPATCH(KERNEL, L, CALL)                                             \
-    do {                                                                          \
-        if ((L).act == ACT_RELU) {                                                \
-            if ((L).H == 64) { auto k = KERNEL<ACT_RELU, 1>; CALL; }              \
-            else if ((L).H == 128) { auto k = KERNEL<ACT_RELU, 2>; CALL; }        \
-            else { auto k = KERNEL<ACT_RELU, 4>; CALL; }                          \
-        } else {                                                                  \
-            if ((L).H == 64) { auto k = KERNEL<ACT_TANH, 1>; CALL; }              \
-            else if ((L).H == 128) { auto k = KERNEL<ACT_TANH, 2>; CALL; }        \
-            else { auto k = KERNEL<ACT_TANH, 4>; CALL; }                          \
-        }                                                                         \
-    } while (0)
 
 extern "C" {
 
@@ -246,11 +210,11 @@ int tma_dqn_act(const float *params, const tma_policy_dims *d, const float *obs,
     if (!params || !obs || !actions_out) return fail(TMA_ERR_INVALID, "tma_dqn_act: null argument (params, obs or actions_out)");
     if (n < 1) return fail(TMA_ERR_INVALID, "tma_dqn_act: n must be at least 1 (got %lld)", (long long)n);
     if (!(eps >= 0.0 && eps <= 1.0)) return fail(TMA_ERR_INVALID, "tma_dqn_act: eps %g is outside [0, 1]", eps);
-    if ((rc = dqn_set_device(d))) return rc;
+    if ((rc = tile_set_device(d->device))) return rc;
     const PLayout L = dqn_layout(d);
     const int64_t tiles = (n + 15) >> 4;
     const dim3 grid((unsigned)(tiles < DQN_ACT_GRID_CAP ? tiles : DQN_ACT_GRID_CAP)), block(256);
-    DQN_DISPATCH(dqn_act_kernel, L, (k<<<grid, block, 0, (hipStream_t)stream>>>(params, L, obs, n, (float)eps, rng_seed, rng_step, env_offset, actions_out, q_out)));
+    TILE_DISPATCH(dqn_act_kernel, L, (k<<<grid, block, 0, (hipStream_t)stream>>>(params, L, obs, n, (float)eps, rng_seed, rng_step, env_offset, actions_out, q_out)));
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
@@ -278,14 +242,14 @@ int tma_dqn_td_grad(const float *params, const float *target_params, const tma_p
     if (!workspace || workspace_bytes < need)
         return fail(TMA_ERR_INVALID, "tma_dqn_td_grad: workspace of %lld bytes, tma_dqn_workspace_bytes reports %lld", (long long)(workspace ? workspace_bytes : 0),
                     (long long)need);
-    if ((rc = dqn_set_device(d))) return rc;
+    if ((rc = tile_set_device(d->device))) return rc;
     const PLayout L = dqn_layout(d);
     const int grid = dqn_td_grid(n);
     double *parts = static_cast<double *>(workspace);
     float *slabs = reinterpret_cast<float *>(static_cast<char *>(workspace) + dqn_parts_bytes(grid));
     const DqnTdArgs a{params, target_params, L, obs, next_obs, dones, rewards, discounts, actions, n, slabs, parts, q_out};
     hipStream_t s = (hipStream_t)stream;
-    DQN_DISPATCH(dqn_td_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
+    TILE_DISPATCH(dqn_td_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
     TMA_LAUNCH_CHECK();
     const int rb = (int)ceil_div(L.P, 256);
     dqn_reduce_kernel<<<dim3((unsigned)(rb < 256 ? rb : 256)), dim3(256), 0, s>>>(slabs, parts, grid, L.vW1t, L.P, grad_out, stats_out);
@@ -299,12 +263,8 @@ int tma_dqn_target_update(const float *params, float *target_params, const tma_p
     if (!params || !target_params) return fail(TMA_ERR_INVALID, "tma_dqn_target_update: null argument (params or target_params)");
     if (!(tau > 0.0 && tau <= 1.0)) return fail(TMA_ERR_INVALID, "tma_dqn_target_update: tau %g is outside (0, 1]", tau);
     if (params == target_params) return fail(TMA_ERR_INVALID, "tma_dqn_target_update: params and target_params are the same buffer");
-    if ((rc = dqn_set_device(d))) return rc;
-    const PLayout L = dqn_layout(d);
-    const int nb = (int)ceil_div(L.P, 256);
-    dqn_polyak_kernel<<<dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, (hipStream_t)stream>>>(params, target_params, L.P, (float)tau, (float)(1.0 - tau),
-                                                                                                   tau == 1.0 ? 1 : 0);
-    TMA_LAUNCH_CHECK();
+    if ((rc = tile_set_device(d->device))) return rc;
+    if ((rc = tma_polyak_update(params, target_params, dqn_layout(d).P, tau, stream))) return rc;
     return tma_policy_sync(target_params, d, stream);  // the derived copies the policy kernels read (the DQN kernels read none of the target's)
 }
 
@@ -341,23 +301,12 @@ int tma_dqn_iterations_local(tma_env *env, float *params, float *target_params, 
         for (int k = 0; k < hp->train_freq; k++) {
             const double eps = tma_dqn_epsilon(hp, c->num_timesteps);
             if ((rc = tma_dqn_act(params, d, b->last_obs, N, eps, hp->rng_seed, c->collect_step, hp->env_offset, b->actions, nullptr, stream))) return rc;
-            if ((rc = tma_env_step(env, b->actions, TMA_ACT_I32, 0, 0, 1, b->step_obs, b->rewards, b->term, b->trunc, b->term_obs, nullptr, nullptr, stream)))
-                return rc;
-            if ((rc = tma_replay_add(rb, c->pos, b->last_obs, b->actions, b->step_obs, b->rewards, b->term, b->trunc, b->term_obs, stream))) return rc;
-            c->collect_step += 1;
-            c->pos += 1;
-            if (c->pos == rb->capacity) c->pos = 0, c->full = 1;
-            c->num_timesteps += N;
-            c->n_calls += 1;
+            if ((rc = offpolicy_collect_step(env, rb, b, c, TMA_ACT_I32, stream))) return rc;
             if (c->n_calls % every == 0 && (rc = tma_dqn_target_update(params, target_params, d, hp->tau, stream))) return rc;
         }
         if (c->num_timesteps > hp->learning_starts) {
             for (int gs = 0; gs < grad_steps; gs++) {
-                const int size = c->full ? rb->capacity : (int)c->pos;
-                const int newest = (int)((c->pos + rb->capacity - 1) % rb->capacity);
-                if ((rc = tma_replay_sample(rb, size, newest, hp->n_step, hp->gamma, hp->sample_seed, c->draw, hp->batch_size, b->s_obs, b->s_actions, b->s_next_obs,
-                                            b->s_dones, b->s_rewards, b->s_discounts, nullptr, nullptr, stream)))
-                    return rc;
+                if ((rc = offpolicy_sample(rb, b, hp, c, stream))) return rc;
                 c->draw += 1;
                 if ((rc = tma_dqn_td_grad(params, target_params, d, b->s_obs, b->s_actions, b->s_next_obs, b->s_dones, b->s_rewards, b->s_discounts, hp->batch_size,
                                           b->grad, b->stats, nullptr, b->td_workspace, b->td_workspace_bytes, stream)))

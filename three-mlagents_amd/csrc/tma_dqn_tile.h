@@ -1,6 +1,10 @@
-// tma_dqn_tile.h -- the tile functions of the four-wave-per-16-row-tile MLP kernels, shared by csrc/tma_dqn.hip and csrc/tma_sac.hip (moved
-// here unchanged from tma_dqn.hip).  A workgroup of four waves owns a tile of 16 rows; a hidden layer's H output columns are split over the
-// waves (16 NT columns each, NT = H / 64); the tile's activations live in LDS; f32 MFMA (v_mfma_f32_16x16x4_f32) in k order.
+// tma_dqn_tile.h -- what the off-policy files (csrc/tma_dqn.hip, csrc/tma_sac.hip, csrc/tma_td3.hip) share.
+// Device: the tile functions of the four-wave-per-16-row-tile MLP kernels.  A workgroup of four waves owns a tile of 16 rows; a hidden layer's H
+// output columns are split over the waves (16 NT columns each, NT = H / 64); the tile's activations live in LDS; f32 MFMA
+// (v_mfma_f32_16x16x4_f32) in k order.  dqn_dense / dqn_bwd_input / dqn_wgrad / dqn_bgrad are one layer's pieces, mlp_trunk_tile the two hidden
+// layers every forward starts with, TileStats a block's float64 loss sums.
+// Host: tile_set_device, the (activation, H) dispatch TILE_DISPATCH, and the two halves of a native iteration that every algorithm issues alike,
+// offpolicy_collect_step and offpolicy_sample.
 #pragma once
 #include "tma_ppo_types.h"
 
@@ -103,6 +107,19 @@ __device__ __forceinline__ void dqn_bgrad(const float *dz, int ldz, int N, float
     }
 }
 
+// THE two hidden layers of every off-policy net: h1 = act(X[.][0 .. K) W1 + b1), h2 = act(h1 W2 + b2), a barrier behind each; oW1 .. ob2 are the
+// layers' offsets in the parameter buffer `p` (a layer's address is formed where the layer runs, as before the function existed: the compiler's
+// schedule follows it).  Every thread of the workgroup calls it; X must be complete (a barrier behind its load); on return h1, h2 are visible.
+template <int ACT, int NT>
+__device__ __forceinline__ void mlp_trunk_tile(const float *X, int K, const float *p, const int &oW1, const int &ob1, const int &oW2, const int &ob2,
+                                               float *h1, float *h2, int lane, int wave) {
+    constexpr int H = 64 * NT, LD = H + 2;
+    dqn_dense<ACT, NT>(X, DQN_LDX, K, p + oW1, p + ob1, H, h1, LD, lane, wave * 16 * NT);
+    __syncthreads();
+    dqn_dense<ACT, NT>(h1, LD, H, p + oW2, p + ob2, H, h2, LD, lane, wave * 16 * NT);
+    __syncthreads();
+}
+
 // rows [row0, row0 + 16) of src f32[n][D] into X[16][DQN_LDX]; rows behind n are zeros
 __device__ __forceinline__ void dqn_load_tile(const float *__restrict__ src, int64_t row0, int64_t n, int D, float *X, int tid) {
     for (int e = tid; e < 16 * D; e += 256) {
@@ -111,4 +128,85 @@ __device__ __forceinline__ void dqn_load_tile(const float *__restrict__ src, int
     }
 }
 
+// thread 0's float64 sums of a gradient kernel's block: NS statistics and the rows counted
+template <int NS>
+struct TileStats {
+    double s[NS] = {}, rows = 0.0;
+    // one tile: row_stats(row, v) gives the NS values of a row; the tile's valid rows are added in order
+    template <class F>
+    __device__ __forceinline__ void add(int64_t row0, int64_t n, F row_stats) {
+        for (int row = 0; row < 16 && row0 + row < n; row++) {
+            double v[NS];
+            row_stats(row, v);
+#pragma unroll
+            for (int k = 0; k < NS; k++) s[k] += v[k];
+            rows += 1.0;
+        }
+    }
+    // ... where a row's values are the columns of rowstat[16][NS]
+    __device__ __forceinline__ void add_columns(int64_t row0, int64_t n, const float *rowstat) {
+        add(row0, n, [rowstat](int row, double(&v)[NS]) {
+#pragma unroll
+            for (int k = 0; k < NS; k++) v[k] = (double)rowstat[NS * row + k];
+        });
+    }
+    // the block's W partials: the sums, the rows, zeros behind them
+    template <int W>
+    __device__ __forceinline__ void store(double *__restrict__ parts) const {
+        double *p = parts + W * (int64_t)blockIdx.x;
+#pragma unroll
+        for (int k = 0; k < NS; k++) p[k] = s[k];
+        p[NS] = rows;
+#pragma unroll
+        for (int k = NS + 1; k < W; k++) p[k] = 0.0;
+    }
+};
+
+static inline int tile_set_device(int device) {
+    if (device >= 0) {
+        int cur = -1;
+        TMA_HIP(hipGetDevice(&cur));
+        if (cur != device) TMA_HIP(hipSetDevice(device));
+    }
+    return TMA_OK;
+}
+
+// ONE vector step of a native iteration behind the algorithm's own act call: the envs step on b->actions, the transition goes into the ring at
+// c->pos, the counters move on.  (Buffers, Counters: tma_{dqn,sac,td3}_{buffers,counters}, whose field names agree.)
+template <class Buffers, class Counters>
+static inline int offpolicy_collect_step(tma_env *env, const tma_replay *rb, const Buffers *b, Counters *c, int action_kind, void *stream) {
+    int rc;
+    if ((rc = tma_env_step(env, b->actions, action_kind, 0, 0, 1, b->step_obs, b->rewards, b->term, b->trunc, b->term_obs, nullptr, nullptr, stream))) return rc;
+    if ((rc = tma_replay_add(rb, c->pos, b->last_obs, b->actions, b->step_obs, b->rewards, b->term, b->trunc, b->term_obs, stream))) return rc;
+    c->collect_step += 1;
+    c->pos += 1;
+    if (c->pos == rb->capacity) c->pos = 0, c->full = 1;
+    c->num_timesteps += rb->n_envs;
+    c->n_calls += 1;
+    return TMA_OK;
+}
+
+// the minibatch of one optimizer step, drawn with c->draw into the s_* buffers (c->draw is the caller's to bump)
+template <class Buffers, class HParams, class Counters>
+static inline int offpolicy_sample(const tma_replay *rb, const Buffers *b, const HParams *hp, const Counters *c, void *stream) {
+    const int size = c->full ? rb->capacity : (int)c->pos;
+    const int newest = (int)((c->pos + rb->capacity - 1) % rb->capacity);
+    return tma_replay_sample(rb, size, newest, hp->n_step, hp->gamma, hp->sample_seed, c->draw, hp->batch_size, b->s_obs, b->s_actions, b->s_next_obs, b->s_dones,
+                             b->s_rewards, b->s_discounts, nullptr, nullptr, stream);
+}
+
 }  // namespace tma
+
+// f(kernel template instance) for (activation, H)
+#define TILE_DISPATCH(KERNEL, L, CALL)                                            \
+    do {                                                                          \
+        if ((L).act == ACT_RELU) {                                                \
+            if ((L).H == 64) { auto k = KERNEL<ACT_RELU, 1>; CALL; }              \
+            else if ((L).H == 128) { auto k = KERNEL<ACT_RELU, 2>; CALL; }        \
+            else { auto k = KERNEL<ACT_RELU, 4>; CALL; }                          \
+        } else {                                                                  \
+            if ((L).H == 64) { auto k = KERNEL<ACT_TANH, 1>; CALL; }              \
+            else if ((L).H == 128) { auto k = KERNEL<ACT_TANH, 2>; CALL; }        \
+            else { auto k = KERNEL<ACT_TANH, 4>; CALL; }                          \
+        }                                                                         \
+    } while (0)

@@ -15,7 +15,10 @@
 // down to the action rows of W1 -> through the squash and logp into the head cotangent -> the actor's backward into the slab.  Launch 2 of
 // either (sac_reduce_kernel) folds the slabs and the float64 partials in block order.  No float atomics; a gradient element is summed over the
 // rows of a tile in row order, a block's tiles in order, the blocks in order: equal inputs give equal bits.
-// The layout, sac_bwd_input_t, sac_q_tile, sac_normal, the slab fold, the shape check and the dispatch live in tma_sac_tile.h (tma_td3.hip shares them).
+// The layout, sac_bwd_input_t, sac_q_tile, q_backward_tile (one critic's backward), q_action_grad_tile (the critics' input gradients down to dQ/da),
+// trunk_backward_tile (the actor's two hidden layers), sac_normal, the slab fold, the shape check and sac_grad_run (the frame of a gradient entry)
+// live in tma_sac_tile.h, which tma_td3.hip shares (all but the three backward functions: see its head); mlp_trunk_tile, TileStats, TILE_DISPATCH and the native loop's collect step and sample in
+// tma_dqn_tile.h, which tma_dqn.hip shares as well.
 #include "tma_sac_tile.h"
 
 namespace tma {
@@ -29,10 +32,7 @@ template <int ACT, int NT>
 __device__ __forceinline__ void sac_actor_tile(const float *__restrict__ p, const SacLayout &L, const float *X, float *h1, float *h2, float *head, int lane,
                                                int wave) {
     constexpr int H = 64 * NT, LD = H + 2;
-    dqn_dense<ACT, NT>(X, DQN_LDX, L.D, p + L.aW1, p + L.ab1, H, h1, LD, lane, wave * 16 * NT);
-    __syncthreads();
-    dqn_dense<ACT, NT>(h1, LD, H, p + L.aW2, p + L.ab2, H, h2, LD, lane, wave * 16 * NT);
-    __syncthreads();
+    mlp_trunk_tile<ACT, NT>(X, L.D, p, L.aW1, L.ab1, L.aW2, L.ab2, h1, h2, lane, wave);
     if (wave == 0) {
         const int r16 = lane & 15, g = lane >> 4, j = r16 & 7, A = L.A;
         const bool ok = j < A;
@@ -145,11 +145,11 @@ __global__ __launch_bounds__(256) void sac_critic_kernel(SacCriticArgs a) {
     __shared__ float X[16 * DQN_LDX], Xn[16 * DQN_LDX], h1[16 * LD], h2[16 * LD], head[16 * DQN_LDQ], qt[32], qv[16], yv[16], lp[16], dz3[16 * DQN_LDQ],
         rowstat[16 * 4];
     const SacLayout &L = a.L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, A = L.A, D = L.D, c0 = wave * 16 * NT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, A = L.A, D = L.D;
     float *slab = a.slabs + (int64_t)blockIdx.x * 2 * L.n_q;
     const float nf = (float)a.n, alpha = expf(a.log_alpha[0]);
     const int64_t n_tiles = (a.n + 15) >> 4;
-    double loss_sum = 0.0, q0_sum = 0.0, q1_sum = 0.0, rows = 0.0;  // thread 0's
+    TileStats<3> stats;  // thread 0's: critic loss, Q0, Q1
     bool first = true;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t row0 = tile << 4;
@@ -190,7 +190,6 @@ __global__ __launch_bounds__(256) void sac_critic_kernel(SacCriticArgs a) {
         __syncthreads();
         for (int i = 0; i < 2; i++) {
             const float *cp = a.critic + (int64_t)i * L.n_q;
-            float *sl = slab + (int64_t)i * L.n_q;
             sac_q_tile<ACT, NT>(cp, L, X, h1, h2, qv, lane, wave);
             if (tid < 16) {
                 const int64_t r = row0 + tid;
@@ -206,36 +205,14 @@ __global__ __launch_bounds__(256) void sac_critic_kernel(SacCriticArgs a) {
                 rowstat[4 * tid + 2 * i] = loss, rowstat[4 * tid + 2 * i + 1] = q;
             }
             __syncthreads();
-            dqn_wgrad(h2, LD, H, dz3, DQN_LDQ, 1, sl + L.qW3, first, lane, wave);
-            dqn_bgrad(dz3, DQN_LDQ, 1, sl + L.qb3, first, tid);
-            __syncthreads();
-            for (int e = tid; e < 16 * H; e += 256) {  // h2 := dz2 = dz3 W3^T act'(h2): one output column, so one product per element
-                const int row = e / H, k = e - row * H;
-                h2[row * LD + k] = act_bwd<ACT>(dz3[row * DQN_LDQ] * cp[L.qW3 + k], h2[row * LD + k]);
-            }
-            __syncthreads();
-            dqn_wgrad(h1, LD, H, h2, LD, H, sl + L.qW2, first, lane, wave);
-            dqn_bgrad(h2, LD, H, sl + L.qb2, first, tid);
-            __syncthreads();
-            sac_bwd_input_t<ACT, NT>(h2, LD, H, cp + L.qW2, h1, LD, lane, c0);  // h1 := dz1
-            __syncthreads();
-            dqn_wgrad(X, DQN_LDX, D + A, h1, LD, H, sl + L.qW1, first, lane, wave);
-            dqn_bgrad(h1, LD, H, sl + L.qb1, first, tid);
+            q_backward_tile<ACT, NT>(cp, L, X, h1, h2, dz3, slab + (int64_t)i * L.n_q, first, tid);
             __syncthreads();  // (the next critic / tile overwrites every buffer)
         }
-        if (tid == 0) {
-            for (int row = 0; row < 16 && row0 + row < a.n; row++) {
-                loss_sum += (double)rowstat[4 * row] + (double)rowstat[4 * row + 2];
-                q0_sum += (double)rowstat[4 * row + 1], q1_sum += (double)rowstat[4 * row + 3], rows += 1.0;
-            }
-        }
+        if (tid == 0) stats.add(row0, a.n, critic_row_stats(rowstat));
         __syncthreads();  // (rowstat is rewritten by the next tile)
         first = false;
     }
-    if (tid == 0) {
-        double *p = a.parts + 4 * (int64_t)blockIdx.x;
-        p[0] = loss_sum, p[1] = q0_sum, p[2] = q1_sum, p[3] = rows;
-    }
+    if (tid == 0) stats.store<4>(a.parts);
 }
 
 struct SacActorArgs {
@@ -255,11 +232,11 @@ __global__ __launch_bounds__(256) void sac_actor_kernel(SacActorArgs a) {
     __shared__ float X[16 * DQN_LDX], ha1[16 * LD], ha2[16 * LD], hq1[2][16 * LD], hq2[2][16 * LD], head[16 * DQN_LDQ], dzh[16 * DQN_LDQ], qv[32], dzq[32],
         zs[16 * SAC_MAX_A], ats[16 * SAC_MAX_A], sds[16 * SAC_MAX_A], dA[16 * SAC_MAX_A], rowstat[16 * 2];
     const SacLayout &L = a.L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, A = L.A, D = L.D, c0 = wave * 16 * NT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, A = L.A, D = L.D;
     float *slab = a.slabs + (int64_t)blockIdx.x * L.n_actor;
     const float nf = (float)a.n, alpha = expf(a.log_alpha[0]);
     const int64_t n_tiles = (a.n + 15) >> 4;
-    double loss_sum = 0.0, lp_sum = 0.0, rows = 0.0;  // thread 0's
+    TileStats<2> stats;  // thread 0's: actor loss, logp_pi
     bool first = true;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t row0 = tile << 4;
@@ -298,31 +275,8 @@ __global__ __launch_bounds__(256) void sac_actor_kernel(SacActorArgs a) {
             rowstat[2 * tid] = in ? alpha * rowstat[2 * tid + 1] - (second ? qv[16 + tid] : qv[tid]) : 0.0f;
         }
         __syncthreads();
-        if (tid == 0) {
-            for (int row = 0; row < 16 && row0 + row < a.n; row++) loss_sum += (double)rowstat[2 * row], lp_sum += (double)rowstat[2 * row + 1], rows += 1.0;
-        }
-        for (int i = 0; i < 2; i++) {  // hq2[i] := dz2 of critic i (its head has one column: one product per element)
-            const float *cp = a.critic + (int64_t)i * L.n_q;
-            for (int e = tid; e < 16 * H; e += 256) {
-                const int row = e / H, k = e - row * H;
-                hq2[i][row * LD + k] = act_bwd<ACT>(dzq[16 * i + row] * cp[L.qW3 + k], hq2[i][row * LD + k]);
-            }
-        }
-        __syncthreads();
-        for (int i = 0; i < 2; i++) sac_bwd_input_t<ACT, NT>(hq2[i], LD, H, a.critic + (int64_t)i * L.n_q + L.qW2, hq1[i], LD, lane, c0);  // hq1[i] := dz1
-        __syncthreads();
-        {  // dQ/da through the action rows of both W1 (no critic weight gradient is formed): thread (row, j), h in order, qf0 before qf1
-            const int row = tid >> 4, j = tid & 15;
-            if (j < A) {
-                float s = 0.0f;
-                for (int i = 0; i < 2; i++) {
-                    const float *w = a.critic + (int64_t)i * L.n_q + L.qW1 + (int64_t)(D + j) * H;
-                    for (int h = 0; h < H; h++) s += hq1[i][row * LD + h] * w[h];
-                }
-                dA[row * SAC_MAX_A + j] = s;
-            }
-        }
-        __syncthreads();
+        if (tid == 0) stats.add_columns(row0, a.n, rowstat);
+        q_action_grad_tile<ACT, NT, 2>(a.critic, L, dzq, hq1[0], hq2[0], dA, tid);  // both critics' input gradients down to the action rows of W1
         if (tid < 16) {  // through the squash and logp into the head cotangent
             const bool in = row0 + tid < a.n;
             const float an = alpha / nf;
@@ -351,20 +305,11 @@ __global__ __launch_bounds__(256) void sac_actor_kernel(SacActorArgs a) {
             ha2[row * LD + k] = act_bwd<ACT>(s, ha2[row * LD + k]);
         }
         __syncthreads();
-        dqn_wgrad(ha1, LD, H, ha2, LD, H, slab + L.aW2, first, lane, wave);
-        dqn_bgrad(ha2, LD, H, slab + L.ab2, first, tid);
-        __syncthreads();
-        sac_bwd_input_t<ACT, NT>(ha2, LD, H, a.actor + L.aW2, ha1, LD, lane, c0);  // ha1 := dz1
-        __syncthreads();
-        dqn_wgrad(X, DQN_LDX, D, ha1, LD, H, slab + L.aW1, first, lane, wave);
-        dqn_bgrad(ha1, LD, H, slab + L.ab1, first, tid);
+        trunk_backward_tile<ACT, NT>(a.actor, slab, L.aW1, L.ab1, L.aW2, L.ab2, X, D, ha1, ha2, first, tid);
         __syncthreads();  // (the next tile overwrites every buffer)
         first = false;
     }
-    if (tid == 0) {
-        double *p = a.parts + 4 * (int64_t)blockIdx.x;
-        p[0] = loss_sum, p[1] = lp_sum, p[2] = rows, p[3] = 0.0;
-    }
+    if (tid == 0) stats.store<4>(a.parts);
 }
 
 // d loss / d log_ent_coef of SB3's  -(log_ent_coef * (logp_pi + target_entropy).detach()).mean(), from the float64 sum of logp_pi
@@ -387,8 +332,8 @@ __global__ __launch_bounds__(256) void sac_adam_kernel(float *__restrict__ p, co
     }
 }
 
-// target <- tau * params + (1 - tau) * target in f32 (two products, one sum, nothing fused); tau == 1: a copy (dqn_polyak_kernel's arithmetic)
-__global__ __launch_bounds__(256) void sac_polyak_kernel(const float *__restrict__ params, float *__restrict__ target, int64_t n, float tau, float omt, int copy) {
+// target <- tau * params + (1 - tau) * target in f32 (two products, one sum, nothing fused); tau == 1: a copy.  THE target update: tma_dqn_target_update runs it too
+__global__ __launch_bounds__(256) void polyak_kernel(const float *__restrict__ params, float *__restrict__ target, int64_t n, float tau, float omt, int copy) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         const float p = params[e];
         target[e] = copy ? p : tau * p + omt * target[e];
@@ -425,7 +370,7 @@ int tma_sac_act(const float *actor, const tma_sac_dims *d, const float *obs, int
     if (mode == TMA_SAC_UNIFORM) {
         if (noise_in || logp_out || noise_out || head_out)
             return fail(TMA_ERR_INVALID, "tma_sac_act: the uniform mode reads no net and no noise: noise_in, logp_out, noise_out and head_out must be NULL");
-        if ((rc = sac_set_device(d))) return rc;
+        if ((rc = tile_set_device(d->device))) return rc;
         const int64_t nb = ceil_div(n * L.A, 256);
         sac_uniform_kernel<<<dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, (hipStream_t)stream>>>(n, L.A, seed, draw, row_offset, actions_out);
         TMA_LAUNCH_CHECK();
@@ -433,11 +378,11 @@ int tma_sac_act(const float *actor, const tma_sac_dims *d, const float *obs, int
     }
     if (!actor || !obs) return fail(TMA_ERR_INVALID, "tma_sac_act: null argument (actor or obs)");
     if (mode == TMA_SAC_DETERMINISTIC && noise_in) return fail(TMA_ERR_INVALID, "tma_sac_act: the deterministic mode takes no noise_in");
-    if ((rc = sac_set_device(d))) return rc;
+    if ((rc = tile_set_device(d->device))) return rc;
     const int64_t tiles = (n + 15) >> 4;
     const dim3 grid((unsigned)(tiles < SAC_ACT_GRID_CAP ? tiles : SAC_ACT_GRID_CAP)), block(256);
-    SAC_DISPATCH(sac_act_kernel, L, (k<<<grid, block, 0, (hipStream_t)stream>>>(actor, L, obs, n, mode == TMA_SAC_DETERMINISTIC ? 1 : 0, seed, draw, row_offset,
-                                                                                noise_in, actions_out, logp_out, noise_out, head_out)));
+    TILE_DISPATCH(sac_act_kernel, L, (k<<<grid, block, 0, (hipStream_t)stream>>>(actor, L, obs, n, mode == TMA_SAC_DETERMINISTIC ? 1 : 0, seed, draw, row_offset,
+                                                                                 noise_in, actions_out, logp_out, noise_out, head_out)));
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
@@ -448,10 +393,7 @@ int64_t tma_sac_workspace_bytes(const tma_sac_dims *d, int64_t n) {
         fail(TMA_ERR_INVALID, "tma_sac_workspace_bytes: n must be at least 1 (got %lld)", (long long)n);
         return 0;
     }
-    const SacLayout L = sac_layout_of(d);
-    const int grid = sac_grad_grid(n);
-    const int64_t widest = 2 * (int64_t)L.n_q > L.n_actor ? 2 * (int64_t)L.n_q : L.n_actor;
-    return sac_parts_bytes(grid) + (int64_t)grid * widest * 4;
+    return sac_workspace_bytes_of(sac_layout_of(d), n);
 }
 
 int tma_sac_critic_grad(const float *actor, const float *critic, const float *critic_target, const float *log_ent_coef, const tma_sac_dims *d, const float *obs,
@@ -464,24 +406,14 @@ int tma_sac_critic_grad(const float *actor, const float *critic, const float *cr
         return fail(TMA_ERR_INVALID,
                     "tma_sac_critic_grad: null argument (actor, critic, critic_target, log_ent_coef, obs, actions, next_obs, dones, rewards, discounts or grad_out)");
     if (n < 1) return fail(TMA_ERR_INVALID, "tma_sac_critic_grad: n must be at least 1 (got %lld)", (long long)n);
-    const int64_t need = tma_sac_workspace_bytes(d, n);
-    if (!workspace || workspace_bytes < need)
-        return fail(TMA_ERR_INVALID, "tma_sac_critic_grad: workspace of %lld bytes, tma_sac_workspace_bytes reports %lld", (long long)(workspace ? workspace_bytes : 0),
-                    (long long)need);
-    if ((rc = sac_set_device(d))) return rc;
     const SacLayout L = sac_layout_of(d);
-    const int grid = sac_grad_grid(n);
-    double *parts = static_cast<double *>(workspace);
-    float *slabs = reinterpret_cast<float *>(static_cast<char *>(workspace) + sac_parts_bytes(grid));
-    const SacCriticArgs a{actor, critic, critic_target, log_ent_coef, L, obs, actions, next_obs, dones, rewards, discounts, noise_in, n, seed, draw, slabs, parts,
-                          q_out, target_out, noise_out, head_out};
     hipStream_t s = (hipStream_t)stream;
-    SAC_DISPATCH(sac_critic_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
-    TMA_LAUNCH_CHECK();
-    const int P = 2 * L.n_q, rb = (int)ceil_div(P, 256);
-    sac_reduce_kernel<<<dim3((unsigned)(rb < 256 ? rb : 256)), dim3(256), 0, s>>>(slabs, parts, grid, P, 4, grad_out, stats_out);
-    TMA_LAUNCH_CHECK();
-    return TMA_OK;
+    return sac_grad_run("tma_sac_critic_grad", "tma_sac_workspace_bytes", d, L, n, workspace, workspace_bytes, 2 * L.n_q, 4, grad_out, stats_out, s,
+                        [&](int grid, float *slabs, double *parts) {
+                            const SacCriticArgs a{actor, critic, critic_target, log_ent_coef, L, obs, actions, next_obs, dones, rewards, discounts,
+                                                  noise_in, n, seed, draw, slabs, parts, q_out, target_out, noise_out, head_out};
+                            TILE_DISPATCH(sac_critic_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
+                        });
 }
 
 int tma_sac_actor_grad(const float *actor, const float *critic, const float *log_ent_coef, const tma_sac_dims *d, const float *obs, int64_t n, uint32_t seed,
@@ -492,23 +424,13 @@ int tma_sac_actor_grad(const float *actor, const float *critic, const float *log
     if (!actor || !critic || !log_ent_coef || !obs || !grad_out)
         return fail(TMA_ERR_INVALID, "tma_sac_actor_grad: null argument (actor, critic, log_ent_coef, obs or grad_out)");
     if (n < 1) return fail(TMA_ERR_INVALID, "tma_sac_actor_grad: n must be at least 1 (got %lld)", (long long)n);
-    const int64_t need = tma_sac_workspace_bytes(d, n);
-    if (!workspace || workspace_bytes < need)
-        return fail(TMA_ERR_INVALID, "tma_sac_actor_grad: workspace of %lld bytes, tma_sac_workspace_bytes reports %lld", (long long)(workspace ? workspace_bytes : 0),
-                    (long long)need);
-    if ((rc = sac_set_device(d))) return rc;
     const SacLayout L = sac_layout_of(d);
-    const int grid = sac_grad_grid(n);
-    double *parts = static_cast<double *>(workspace);
-    float *slabs = reinterpret_cast<float *>(static_cast<char *>(workspace) + sac_parts_bytes(grid));
-    const SacActorArgs a{actor, critic, log_ent_coef, L, obs, noise_in, n, seed, draw, slabs, parts, actions_out, logp_out, noise_out, head_out};
     hipStream_t s = (hipStream_t)stream;
-    SAC_DISPATCH(sac_actor_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
-    TMA_LAUNCH_CHECK();
-    const int rb = (int)ceil_div(L.n_actor, 256);
-    sac_reduce_kernel<<<dim3((unsigned)(rb < 256 ? rb : 256)), dim3(256), 0, s>>>(slabs, parts, grid, L.n_actor, 3, grad_out, stats_out);
-    TMA_LAUNCH_CHECK();
-    return TMA_OK;
+    return sac_grad_run("tma_sac_actor_grad", "tma_sac_workspace_bytes", d, L, n, workspace, workspace_bytes, L.n_actor, 3, grad_out, stats_out, s,
+                        [&](int grid, float *slabs, double *parts) {
+                            const SacActorArgs a{actor, critic, log_ent_coef, L, obs, noise_in, n, seed, draw, slabs, parts, actions_out, logp_out, noise_out, head_out};
+                            TILE_DISPATCH(sac_actor_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
+                        });
 }
 
 int tma_sac_ent_coef_grad(const double *actor_stats, double target_entropy, float *grad_out, void *stream) {
@@ -542,8 +464,7 @@ int tma_polyak_update(const float *params, float *target, int64_t n, double tau,
     if (!(tau > 0.0 && tau <= 1.0)) return fail(TMA_ERR_INVALID, "tma_polyak_update: tau %g is outside (0, 1]", tau);
     if (params == target) return fail(TMA_ERR_INVALID, "tma_polyak_update: params and target are the same buffer");
     const int64_t nb = ceil_div(n, 256);
-    sac_polyak_kernel<<<dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, (hipStream_t)stream>>>(params, target, n, (float)tau, (float)(1.0 - tau),
-                                                                                                      tau == 1.0 ? 1 : 0);
+    polyak_kernel<<<dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, (hipStream_t)stream>>>(params, target, n, (float)tau, (float)(1.0 - tau), tau == 1.0 ? 1 : 0);
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
@@ -575,22 +496,11 @@ int tma_sac_iterations_local(tma_env *env, float *actor, float *critic, float *c
             if ((rc = tma_sac_act(warm ? nullptr : actor, d, warm ? nullptr : b->last_obs, N, warm ? TMA_SAC_UNIFORM : TMA_SAC_SAMPLE, hp->rng_seed, c->collect_step,
                                   hp->env_offset, nullptr, b->actions, nullptr, nullptr, nullptr, stream)))
                 return rc;
-            if ((rc = tma_env_step(env, b->actions, TMA_ACT_F32, 0, 0, 1, b->step_obs, b->rewards, b->term, b->trunc, b->term_obs, nullptr, nullptr, stream)))
-                return rc;
-            if ((rc = tma_replay_add(rb, c->pos, b->last_obs, b->actions, b->step_obs, b->rewards, b->term, b->trunc, b->term_obs, stream))) return rc;
-            c->collect_step += 1;
-            c->pos += 1;
-            if (c->pos == rb->capacity) c->pos = 0, c->full = 1;
-            c->num_timesteps += N;
-            c->n_calls += 1;
+            if ((rc = offpolicy_collect_step(env, rb, b, c, TMA_ACT_F32, stream))) return rc;
         }
         if (c->num_timesteps > hp->learning_starts) {
             for (int gs = 0; gs < grad_steps; gs++) {
-                const int size = c->full ? rb->capacity : (int)c->pos;
-                const int newest = (int)((c->pos + rb->capacity - 1) % rb->capacity);
-                if ((rc = tma_replay_sample(rb, size, newest, hp->n_step, hp->gamma, hp->sample_seed, c->draw, B, b->s_obs, b->s_actions, b->s_next_obs, b->s_dones,
-                                            b->s_rewards, b->s_discounts, nullptr, nullptr, stream)))
-                    return rc;
+                if ((rc = offpolicy_sample(rb, b, hp, c, stream))) return rc;
                 const int64_t t = c->adam_step + 1;
                 if ((rc = tma_sac_critic_grad(actor, critic, critic_target, log_ent_coef, d, b->s_obs, b->s_actions, b->s_next_obs, b->s_dones, b->s_rewards,
                                               b->s_discounts, B, hp->rng_seed, c->draw, nullptr, b->critic_grad, b->critic_stats, nullptr, nullptr, nullptr, nullptr,

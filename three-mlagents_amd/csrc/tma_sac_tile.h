@@ -1,6 +1,10 @@
-// tma_sac_tile.h -- what csrc/tma_sac.hip and csrc/tma_td3.hip share (moved here unchanged from tma_sac.hip): the flat [in][out] layout of an
-// actor and of a critic pair, the transposed input gradient of a hidden layer, one critic's forward on a 16-row tile, the Box-Muller noise, the
-// slab fold of a gradient launch, the shape check of tma_sac_dims and the (activation, H) dispatch.
+// tma_sac_tile.h -- what csrc/tma_sac.hip and csrc/tma_td3.hip share beyond tma_dqn_tile.h: the flat [in][out] layout of an actor and of a critic
+// pair; on a 16-row tile the transposed input gradient of a hidden layer (sac_bwd_input_t), one critic's forward (sac_q_tile), the backward of
+// the two hidden layers of an actor or a critic (trunk_backward_tile), one critic's whole backward (q_backward_tile) and the critics' gradient
+// with respect to the action (q_action_grad_tile); the Box-Muller noise; the slab fold of a gradient launch; the shape check of tma_sac_dims,
+// the workspace size and the frame of a gradient entry (sac_grad_run).  The three backward functions are SAC's two gradient kernels'; TD3's
+// kernels spell the same chains out (tma_td3.hip's head says why).  Offsets reach the tile functions by reference: a layout field is then read
+// where the layer that needs it runs, as in the text the functions replaced, and the compiler's schedule stays close to that text's.
 #pragma once
 #include "tma_dqn_tile.h"
 
@@ -76,10 +80,7 @@ __device__ __forceinline__ void sac_bwd_input_t(const float *dz, int ldz, int N,
 template <int ACT, int NT>
 __device__ __forceinline__ void sac_q_tile(const float *__restrict__ p, const SacLayout &L, const float *X, float *h1, float *h2, float *q, int lane, int wave) {
     constexpr int H = 64 * NT, LD = H + 2;
-    dqn_dense<ACT, NT>(X, DQN_LDX, L.D + L.A, p + L.qW1, p + L.qb1, H, h1, LD, lane, wave * 16 * NT);
-    __syncthreads();
-    dqn_dense<ACT, NT>(h1, LD, H, p + L.qW2, p + L.qb2, H, h2, LD, lane, wave * 16 * NT);
-    __syncthreads();
+    mlp_trunk_tile<ACT, NT>(X, L.D + L.A, p, L.qW1, L.qb1, L.qW2, L.qb2, h1, h2, lane, wave);
     if (wave == 0) {
         f32x4 acc[1];
         dense_head<1>(h2, LD, H, p + L.qW3, p + L.qb3, 1, acc, lane);
@@ -88,6 +89,77 @@ __device__ __forceinline__ void sac_q_tile(const float *__restrict__ p, const Sa
 #pragma unroll
             for (int r = 0; r < 4; r++) q[g * 4 + r] = acc[0][r];
         }
+    }
+    __syncthreads();
+}
+
+// THE backward of a net's two hidden layers, from h2 already holding dz2 (a barrier behind its forming): dW2 / db2, h1 := dz1, dW1 / db1 into the
+// block's slab.  oW1 .. ob2 are the layers' offsets, the same in the parameter buffer `p` and in `slab`; X[.][0 .. K) is the net's input.  Every
+// thread of the workgroup calls it (it holds barriers); the caller's next barrier stands before any reuse of X, h1, h2.
+template <int ACT, int NT>
+__device__ __forceinline__ void trunk_backward_tile(const float *p, float *slab, const int &oW1, const int &ob1, const int &oW2, const int &ob2, const float *X,
+                                                    int K, float *h1, float *h2, bool first, int tid) {
+    constexpr int H = 64 * NT, LD = H + 2;
+    const int lane = tid & 63, wave = tid >> 6;
+    dqn_wgrad(h1, LD, H, h2, LD, H, slab + oW2, first, lane, wave);
+    dqn_bgrad(h2, LD, H, slab + ob2, first, tid);
+    __syncthreads();
+    sac_bwd_input_t<ACT, NT>(h2, LD, H, p + oW2, h1, LD, lane, wave * 16 * NT);  // h1 := dz1
+    __syncthreads();
+    dqn_wgrad(X, DQN_LDX, K, h1, LD, H, slab + oW1, first, lane, wave);
+    dqn_bgrad(h1, LD, H, slab + ob1, first, tid);
+}
+
+// h2 := dz2 = dz3 W3^T act'(h2) of ONE critic, whose head has one column: one product per element.  dz[row * ldz] is the row's head cotangent.
+template <int ACT, int NT>
+__device__ __forceinline__ void q_head_backward_tile(const float *dz, int ldz, const float *cp, const int &oW3, float *h2, int tid) {
+    constexpr int H = 64 * NT, LD = H + 2;
+    for (int e = tid; e < 16 * H; e += 256) {
+        const int row = e / H, k = e - row * H;
+        h2[row * LD + k] = act_bwd<ACT>(dz[row * ldz] * cp[oW3 + k], h2[row * LD + k]);
+    }
+}
+
+// ONE critic's backward from dz3 (column 0: the head cotangent, visible to every thread) into its slab `sl`: dW3 / db3, h2 := dz2, then
+// trunk_backward_tile.  cp is the critic's parameters, X its input tile (obs | action); barriers as trunk_backward_tile.
+template <int ACT, int NT>
+__device__ __forceinline__ void q_backward_tile(const float *cp, const SacLayout &L, const float *X, float *h1, float *h2, const float *dz3, float *sl, bool first,
+                                                int tid) {
+    constexpr int H = 64 * NT, LD = H + 2;
+    dqn_wgrad(h2, LD, H, dz3, DQN_LDQ, 1, sl + L.qW3, first, tid & 63, tid >> 6);
+    dqn_bgrad(dz3, DQN_LDQ, 1, sl + L.qb3, first, tid);
+    __syncthreads();
+    q_head_backward_tile<ACT, NT>(dz3, DQN_LDQ, cp, L.qW3, h2, tid);
+    __syncthreads();
+    trunk_backward_tile<ACT, NT>(cp, sl, L.qW1, L.qb1, L.qW2, L.qb2, X, L.D + L.A, h1, h2, first, tid);
+}
+
+// a critic kernel's rowstat[16][4] = (loss0, Q0, loss1, Q1) as a row's three statistics for TileStats<3>::add: loss0 + loss1, Q0, Q1
+__device__ __forceinline__ auto critic_row_stats(const float *rowstat) {
+    return [rowstat](int row, double(&v)[3]) {
+        v[0] = (double)rowstat[4 * row] + (double)rowstat[4 * row + 2], v[1] = (double)rowstat[4 * row + 1], v[2] = (double)rowstat[4 * row + 3];
+    };
+}
+
+// dQ/da of the first NQ critics of `critic`, summed into dA[16][SAC_MAX_A] (no critic weight gradient is formed).  dzq[16 i + row] is critic i's
+// head cotangent; hq1 + i 16 LD, hq2 + i 16 LD hold its hidden activations and become dz1, dz2; then thread (row, j) walks the action rows of the
+// W1s, h in order, qf0 before qf1.  Every thread of the workgroup calls it; dzq must be visible; on return dA is.
+template <int ACT, int NT, int NQ>
+__device__ __forceinline__ void q_action_grad_tile(const float *critic, const SacLayout &L, const float *dzq, float *hq1, float *hq2, float *dA, int tid) {
+    constexpr int H = 64 * NT, LD = H + 2;
+    for (int i = 0; i < NQ; i++) q_head_backward_tile<ACT, NT>(dzq + 16 * i, 1, critic + (int64_t)i * L.n_q, L.qW3, hq2 + i * 16 * LD, tid);
+    __syncthreads();
+    for (int i = 0; i < NQ; i++)
+        sac_bwd_input_t<ACT, NT>(hq2 + i * 16 * LD, LD, H, critic + (int64_t)i * L.n_q + L.qW2, hq1 + i * 16 * LD, LD, tid & 63, (tid >> 6) * 16 * NT);
+    __syncthreads();
+    const int row = tid >> 4, j = tid & 15;
+    if (j < L.A) {
+        float s = 0.0f;
+        for (int i = 0; i < NQ; i++) {
+            const float *w = critic + (int64_t)i * L.n_q + L.qW1 + (int64_t)(L.D + j) * H;
+            for (int h = 0; h < H; h++) s += hq1[i * 16 * LD + row * LD + h] * w[h];
+        }
+        dA[row * SAC_MAX_A + j] = s;
     }
     __syncthreads();
 }
@@ -135,28 +207,34 @@ static inline int sac_check(const tma_sac_dims *d, const char *who) {
         return fail(TMA_ERR_INVALID, "%s: activation %d is neither TMA_ACT_TANH (0) nor TMA_ACT_RELU (1)", who, d->activation);
     return TMA_OK;
 }
-static inline int sac_set_device(const tma_sac_dims *d) {
-    if (d->device >= 0) {
-        int cur = -1;
-        TMA_HIP(hipGetDevice(&cur));
-        if (cur != d->device) TMA_HIP(hipSetDevice(d->device));
-    }
-    return TMA_OK;
-}
 static inline SacLayout sac_layout_of(const tma_sac_dims *d) { return sac_layout(d->obs_dim, d->act_dim, d->hidden, d->activation); }
 
-}  // namespace tma
+// the workspace of either gradient launch on n rows of layout L (SAC's or TD3's): the blocks' partials, then the wider of the two slab sets
+static inline int64_t sac_workspace_bytes_of(const SacLayout &L, int64_t n) {
+    const int grid = sac_grad_grid(n);
+    const int64_t widest = 2 * (int64_t)L.n_q > L.n_actor ? 2 * (int64_t)L.n_q : L.n_actor;
+    return sac_parts_bytes(grid) + (int64_t)grid * widest * 4;
+}
 
-// f(kernel template instance) for (activation, H)
-#define SAC_DISPATCH(KERNEL, L, CALL)                                             \
-    do {                                                                          \
-        if ((L).act == ACT_RELU) {                                                \
-            if ((L).H == 64) { auto k = KERNEL<ACT_RELU, 1>; CALL; }              \
-            else if ((L).H == 128) { auto k = KERNEL<ACT_RELU, 2>; CALL; }        \
-            else { auto k = KERNEL<ACT_RELU, 4>; CALL; }                          \
-        } else {                                                                  \
-            if ((L).H == 64) { auto k = KERNEL<ACT_TANH, 1>; CALL; }              \
-            else if ((L).H == 128) { auto k = KERNEL<ACT_TANH, 2>; CALL; }        \
-            else { auto k = KERNEL<ACT_TANH, 4>; CALL; }                          \
-        }                                                                         \
-    } while (0)
+// what a gradient entry `who` does around its kernel: refuse a workspace below what `ws_fn` reports, select the device, carve parts and slabs,
+// launch(grid, slabs, parts), then fold the slabs of P floats and the first n_stats partials (sac_reduce_kernel)
+template <class Launch>
+static inline int sac_grad_run(const char *who, const char *ws_fn, const tma_sac_dims *d, const SacLayout &L, int64_t n, void *workspace, int64_t workspace_bytes,
+                               int P, int n_stats, float *grad_out, double *stats_out, hipStream_t s, Launch launch) {
+    const int64_t need = sac_workspace_bytes_of(L, n);
+    if (!workspace || workspace_bytes < need)
+        return fail(TMA_ERR_INVALID, "%s: workspace of %lld bytes, %s reports %lld", who, (long long)(workspace ? workspace_bytes : 0), ws_fn, (long long)need);
+    const int rc = tile_set_device(d->device);
+    if (rc) return rc;
+    const int grid = sac_grad_grid(n);
+    double *parts = static_cast<double *>(workspace);
+    float *slabs = reinterpret_cast<float *>(static_cast<char *>(workspace) + sac_parts_bytes(grid));
+    launch(grid, slabs, parts);
+    TMA_LAUNCH_CHECK();
+    const int rb = (int)ceil_div(P, 256);
+    sac_reduce_kernel<<<dim3((unsigned)(rb < 256 ? rb : 256)), dim3(256), 0, s>>>(slabs, parts, grid, P, n_stats, grad_out, stats_out);
+    TMA_LAUNCH_CHECK();
+    return TMA_OK;
+}
+
+}  // namespace tma

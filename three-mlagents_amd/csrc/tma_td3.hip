@@ -14,6 +14,11 @@
 // its W1 -> through the tanh -> the actor's backward into the slab.  Launch 2 of either (sac_reduce_kernel) folds the slabs and the float64
 // partials in block order.  No float atomics; a gradient element is summed over the rows of a tile in row order, a block's tiles in order, the
 // blocks in order: equal inputs give equal bits.
+// Shared: sac_q_tile, critic_row_stats and a gradient entry's frame sac_grad_run (tma_sac_tile.h); mlp_trunk_tile, TileStats, TILE_DISPATCH and
+// the loop's collect step and sample (tma_dqn_tile.h).  NOT shared, on a measurement: the two gradient kernels spell out the backward chains that
+// tma_sac_tile.h holds as q_backward_tile, q_action_grad_tile and trunk_backward_tile.  Through those functions the same operations compiled to
+// a different register allocation, and at H = 256 the kernels ran 0.3 - 0.6 % slower than written out (SAC's did not); the text here and there
+// must be kept in step by hand.
 #include "tma_sac_tile.h"
 
 namespace tma {
@@ -34,10 +39,7 @@ template <int ACT, int NT>
 __device__ __forceinline__ void td3_actor_tile(const float *__restrict__ p, const SacLayout &L, const float *X, float *h1, float *h2, float *head, int lane,
                                                int wave) {
     constexpr int H = 64 * NT, LD = H + 2;
-    dqn_dense<ACT, NT>(X, DQN_LDX, L.D, p + L.aW1, p + L.ab1, H, h1, LD, lane, wave * 16 * NT);
-    __syncthreads();
-    dqn_dense<ACT, NT>(h1, LD, H, p + L.aW2, p + L.ab2, H, h2, LD, lane, wave * 16 * NT);
-    __syncthreads();
+    mlp_trunk_tile<ACT, NT>(X, L.D, p, L.aW1, L.ab1, L.aW2, L.ab2, h1, h2, lane, wave);
     if (wave == 0) {
         const int r16 = lane & 15, g = lane >> 4, A = L.A;
         const bool ok = r16 < A;
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256) void td3_critic_kernel(Td3CriticArgs a) {
     float *slab = a.slabs + (int64_t)blockIdx.x * 2 * L.n_q;
     const float nf = (float)a.n;
     const int64_t n_tiles = (a.n + 15) >> 4;
-    double loss_sum = 0.0, q0_sum = 0.0, q1_sum = 0.0, rows = 0.0;  // thread 0's
+    TileStats<3> stats;  // thread 0's: critic loss, Q0, Q1
     bool first = true;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t row0 = tile << 4;
@@ -180,6 +182,7 @@ __global__ __launch_bounds__(256) void td3_critic_kernel(Td3CriticArgs a) {
                 rowstat[4 * tid + 2 * i] = loss, rowstat[4 * tid + 2 * i + 1] = q;
             }
             __syncthreads();
+            // (tma_sac_tile.h's q_backward_tile written out: through the function these kernels measured 0.3 - 0.6 % slower at H = 256)
             dqn_wgrad(h2, LD, H, dz3, DQN_LDQ, 1, sl + L.qW3, first, lane, wave);
             dqn_bgrad(dz3, DQN_LDQ, 1, sl + L.qb3, first, tid);
             __syncthreads();
@@ -197,19 +200,11 @@ __global__ __launch_bounds__(256) void td3_critic_kernel(Td3CriticArgs a) {
             dqn_bgrad(h1, LD, H, sl + L.qb1, first, tid);
             __syncthreads();  // (the next critic / tile overwrites every buffer)
         }
-        if (tid == 0) {
-            for (int row = 0; row < 16 && row0 + row < a.n; row++) {
-                loss_sum += (double)rowstat[4 * row] + (double)rowstat[4 * row + 2];
-                q0_sum += (double)rowstat[4 * row + 1], q1_sum += (double)rowstat[4 * row + 3], rows += 1.0;
-            }
-        }
+        if (tid == 0) stats.add(row0, a.n, critic_row_stats(rowstat));
         __syncthreads();  // (rowstat is rewritten by the next tile)
         first = false;
     }
-    if (tid == 0) {
-        double *p = a.parts + 4 * (int64_t)blockIdx.x;
-        p[0] = loss_sum, p[1] = q0_sum, p[2] = q1_sum, p[3] = rows;
-    }
+    if (tid == 0) stats.store<4>(a.parts);
 }
 
 struct Td3ActorArgs {
@@ -232,7 +227,7 @@ __global__ __launch_bounds__(256) void td3_actor_kernel(Td3ActorArgs a) {
     float *slab = a.slabs + (int64_t)blockIdx.x * L.n_actor;
     const float nf = (float)a.n;
     const int64_t n_tiles = (a.n + 15) >> 4;
-    double loss_sum = 0.0, rows = 0.0;  // thread 0's
+    TileStats<1> stats;  // thread 0's: the sum of -Q0
     bool first = true;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t row0 = tile << 4;
@@ -256,10 +251,9 @@ __global__ __launch_bounds__(256) void td3_actor_kernel(Td3ActorArgs a) {
         __syncthreads();
         sac_q_tile<ACT, NT>(a.critic, L, X, hq1, hq2, qv, lane, wave);  // qf0 alone (SB3: critic.q1_forward)
         if (tid < 16) dzq[tid] = row0 + tid < a.n ? -1.0f / nf : 0.0f;
-        if (tid == 0) {
-            for (int row = 0; row < 16 && row0 + row < a.n; row++) loss_sum += -(double)qv[row], rows += 1.0;
-        }
+        if (tid == 0) stats.add(row0, a.n, [&](int row, double(&v)[1]) { v[0] = -(double)qv[row]; });
         __syncthreads();
+        // (tma_sac_tile.h's q_action_grad_tile<.., 1> and, below, trunk_backward_tile written out: see td3_critic_kernel)
         for (int e = tid; e < 16 * H; e += 256) {  // hq2 := dz2 of qf0 (its head has one column: one product per element)
             const int row = e / H, k = e - row * H;
             hq2[row * LD + k] = act_bwd<ACT>(dzq[row] * a.critic[L.qW3 + k], hq2[row * LD + k]);
@@ -306,10 +300,7 @@ __global__ __launch_bounds__(256) void td3_actor_kernel(Td3ActorArgs a) {
         __syncthreads();  // (the next tile overwrites every buffer)
         first = false;
     }
-    if (tid == 0) {
-        double *p = a.parts + 4 * (int64_t)blockIdx.x;
-        p[0] = loss_sum, p[1] = rows, p[2] = 0.0, p[3] = 0.0;
-    }
+    if (tid == 0) stats.store<4>(a.parts);
 }
 
 static SacLayout td3_layout_of(const tma_sac_dims *d) { return td3_layout(d->obs_dim, d->act_dim, d->hidden, d->activation); }
@@ -357,12 +348,12 @@ int tma_td3_act(const float *actor, const tma_sac_dims *d, const float *obs, int
             an.mean[j] = m, an.sigma[j] = s;
         }
     }
-    if ((rc = sac_set_device(d))) return rc;
+    if ((rc = tile_set_device(d->device))) return rc;
     const SacLayout L = td3_layout_of(d);
     const int64_t tiles = (n + 15) >> 4;
     const dim3 grid((unsigned)(tiles < SAC_ACT_GRID_CAP ? tiles : SAC_ACT_GRID_CAP)), block(256);
-    SAC_DISPATCH(td3_act_kernel, L, (k<<<grid, block, 0, (hipStream_t)stream>>>(actor, L, obs, n, mode == TMA_TD3_NOISY ? 1 : 0, an, seed, draw, row_offset, noise_in,
-                                                                                actions_out, noise_out, head_out)));
+    TILE_DISPATCH(td3_act_kernel, L, (k<<<grid, block, 0, (hipStream_t)stream>>>(actor, L, obs, n, mode == TMA_TD3_NOISY ? 1 : 0, an, seed, draw, row_offset, noise_in,
+                                                                                 actions_out, noise_out, head_out)));
     TMA_LAUNCH_CHECK();
     return TMA_OK;
 }
@@ -373,10 +364,7 @@ int64_t tma_td3_workspace_bytes(const tma_sac_dims *d, int64_t n) {
         fail(TMA_ERR_INVALID, "tma_td3_workspace_bytes: n must be at least 1 (got %lld)", (long long)n);
         return 0;
     }
-    const SacLayout L = td3_layout_of(d);
-    const int grid = sac_grad_grid(n);
-    const int64_t widest = 2 * (int64_t)L.n_q > L.n_actor ? 2 * (int64_t)L.n_q : L.n_actor;
-    return sac_parts_bytes(grid) + (int64_t)grid * widest * 4;
+    return sac_workspace_bytes_of(td3_layout_of(d), n);
 }
 
 int tma_td3_critic_grad(const float *actor_target, const float *critic, const float *critic_target, const tma_sac_dims *d, const float *obs, const float *actions,
@@ -392,24 +380,14 @@ int tma_td3_critic_grad(const float *actor_target, const float *critic, const fl
     if (!(target_policy_noise >= 0.0) || !(target_noise_clip >= 0.0))
         return fail(TMA_ERR_INVALID, "tma_td3_critic_grad: target_policy_noise %g and target_noise_clip %g must be at least 0", target_policy_noise,
                     target_noise_clip);
-    const int64_t need = tma_td3_workspace_bytes(d, n);
-    if (!workspace || workspace_bytes < need)
-        return fail(TMA_ERR_INVALID, "tma_td3_critic_grad: workspace of %lld bytes, tma_td3_workspace_bytes reports %lld", (long long)(workspace ? workspace_bytes : 0),
-                    (long long)need);
-    if ((rc = sac_set_device(d))) return rc;
     const SacLayout L = td3_layout_of(d);
-    const int grid = sac_grad_grid(n);
-    double *parts = static_cast<double *>(workspace);
-    float *slabs = reinterpret_cast<float *>(static_cast<char *>(workspace) + sac_parts_bytes(grid));
-    const Td3CriticArgs a{actor_target, critic, critic_target, L, obs, actions, next_obs, dones, rewards, discounts, noise_in, n, seed, draw,
-                          (float)target_policy_noise, (float)target_noise_clip, slabs, parts, q_out, target_out, noise_out, head_out};
     hipStream_t s = (hipStream_t)stream;
-    SAC_DISPATCH(td3_critic_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
-    TMA_LAUNCH_CHECK();
-    const int P = 2 * L.n_q, rb = (int)ceil_div(P, 256);
-    sac_reduce_kernel<<<dim3((unsigned)(rb < 256 ? rb : 256)), dim3(256), 0, s>>>(slabs, parts, grid, P, 4, grad_out, stats_out);
-    TMA_LAUNCH_CHECK();
-    return TMA_OK;
+    return sac_grad_run("tma_td3_critic_grad", "tma_td3_workspace_bytes", d, L, n, workspace, workspace_bytes, 2 * L.n_q, 4, grad_out, stats_out, s,
+                        [&](int grid, float *slabs, double *parts) {
+                            const Td3CriticArgs a{actor_target, critic, critic_target, L, obs, actions, next_obs, dones, rewards, discounts, noise_in, n, seed, draw,
+                                                  (float)target_policy_noise, (float)target_noise_clip, slabs, parts, q_out, target_out, noise_out, head_out};
+                            TILE_DISPATCH(td3_critic_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
+                        });
 }
 
 int tma_td3_actor_grad(const float *actor, const float *critic, const tma_sac_dims *d, const float *obs, int64_t n, float *grad_out, double *stats_out,
@@ -418,23 +396,13 @@ int tma_td3_actor_grad(const float *actor, const float *critic, const tma_sac_di
     if (rc) return rc;
     if (!actor || !critic || !obs || !grad_out) return fail(TMA_ERR_INVALID, "tma_td3_actor_grad: null argument (actor, critic, obs or grad_out)");
     if (n < 1) return fail(TMA_ERR_INVALID, "tma_td3_actor_grad: n must be at least 1 (got %lld)", (long long)n);
-    const int64_t need = tma_td3_workspace_bytes(d, n);
-    if (!workspace || workspace_bytes < need)
-        return fail(TMA_ERR_INVALID, "tma_td3_actor_grad: workspace of %lld bytes, tma_td3_workspace_bytes reports %lld", (long long)(workspace ? workspace_bytes : 0),
-                    (long long)need);
-    if ((rc = sac_set_device(d))) return rc;
     const SacLayout L = td3_layout_of(d);
-    const int grid = sac_grad_grid(n);
-    double *parts = static_cast<double *>(workspace);
-    float *slabs = reinterpret_cast<float *>(static_cast<char *>(workspace) + sac_parts_bytes(grid));
-    const Td3ActorArgs a{actor, critic, L, obs, n, slabs, parts, actions_out, head_out};
     hipStream_t s = (hipStream_t)stream;
-    SAC_DISPATCH(td3_actor_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
-    TMA_LAUNCH_CHECK();
-    const int rb = (int)ceil_div(L.n_actor, 256);
-    sac_reduce_kernel<<<dim3((unsigned)(rb < 256 ? rb : 256)), dim3(256), 0, s>>>(slabs, parts, grid, L.n_actor, 2, grad_out, stats_out);
-    TMA_LAUNCH_CHECK();
-    return TMA_OK;
+    return sac_grad_run("tma_td3_actor_grad", "tma_td3_workspace_bytes", d, L, n, workspace, workspace_bytes, L.n_actor, 2, grad_out, stats_out, s,
+                        [&](int grid, float *slabs, double *parts) {
+                            const Td3ActorArgs a{actor, critic, L, obs, n, slabs, parts, actions_out, head_out};
+                            TILE_DISPATCH(td3_actor_kernel, L, (k<<<dim3((unsigned)grid), dim3(256), 0, s>>>(a)));
+                        });
 }
 
 int tma_td3_iterations_local(tma_env *env, float *actor, float *actor_target, float *critic, float *critic_target, const tma_sac_dims *d, const tma_replay *rb,
@@ -468,23 +436,12 @@ int tma_td3_iterations_local(tma_env *env, float *actor, float *actor_target, fl
             if ((rc = tma_td3_act(warm ? nullptr : actor, d, warm ? nullptr : b->last_obs, N, mode, &hp->action_noise, hp->rng_seed, c->collect_step, hp->env_offset,
                                   nullptr, b->actions, nullptr, nullptr, stream)))
                 return rc;
-            if ((rc = tma_env_step(env, b->actions, TMA_ACT_F32, 0, 0, 1, b->step_obs, b->rewards, b->term, b->trunc, b->term_obs, nullptr, nullptr, stream)))
-                return rc;
-            if ((rc = tma_replay_add(rb, c->pos, b->last_obs, b->actions, b->step_obs, b->rewards, b->term, b->trunc, b->term_obs, stream))) return rc;
-            c->collect_step += 1;
-            c->pos += 1;
-            if (c->pos == rb->capacity) c->pos = 0, c->full = 1;
-            c->num_timesteps += N;
-            c->n_calls += 1;
+            if ((rc = offpolicy_collect_step(env, rb, b, c, TMA_ACT_F32, stream))) return rc;
         }
         if (c->num_timesteps > hp->learning_starts) {
             for (int gs = 0; gs < grad_steps; gs++) {
                 c->n_updates += 1;  // SB3 counts before it decides: the actor steps where n_updates % policy_delay == 0
-                const int size = c->full ? rb->capacity : (int)c->pos;
-                const int newest = (int)((c->pos + rb->capacity - 1) % rb->capacity);
-                if ((rc = tma_replay_sample(rb, size, newest, hp->n_step, hp->gamma, hp->sample_seed, c->draw, B, b->s_obs, b->s_actions, b->s_next_obs, b->s_dones,
-                                            b->s_rewards, b->s_discounts, nullptr, nullptr, stream)))
-                    return rc;
+                if ((rc = offpolicy_sample(rb, b, hp, c, stream))) return rc;
                 if ((rc = tma_td3_critic_grad(actor_target, critic, critic_target, d, b->s_obs, b->s_actions, b->s_next_obs, b->s_dones, b->s_rewards, b->s_discounts, B,
                                               hp->target_policy_noise, hp->target_noise_clip, hp->rng_seed, c->draw, nullptr, b->critic_grad, b->critic_stats, nullptr,
                                               nullptr, nullptr, nullptr, b->workspace, b->workspace_bytes, stream)))

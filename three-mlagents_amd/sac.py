@@ -25,13 +25,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dqn import DQN, pol_space
-from .ppo import PPO
+from .off_policy import ADAM_EPS, NATIVE_ITERATIONS, OffPolicyAlgorithm, pol_space  # noqa: F401  (the names this module has always had)
 from .replay_buffer import ReplayBuffer
 from .vec_env import HipVecEnv
 
-ADAM_EPS = 1e-8          # torch.optim.Adam's default, which SB3's SAC policies use
-NATIVE_ITERATIONS = 256  # iterations per tma_sac_iterations_local call of a learn() without a callback (the episode log is popped in between)
 ACTIVATIONS = {"tanh": 0, "relu": 1}
 
 
@@ -166,8 +163,9 @@ class _OptState:
         self.grad, self.exp_avg, self.exp_avg_sq = (torch.zeros(n, dtype=torch.float32, device=device) for _ in range(3))
 
 
-class SAC(PPO):
-    """SB3-shaped SAC whose compute is libtma_hip.so.  Constructor / learn / train / predict / save / load keep SB3's names and defaults."""
+class SAC(OffPolicyAlgorithm):
+    """SB3-shaped SAC whose compute is libtma_hip.so.  Constructor / learn / train / predict / save / load keep SB3's names and defaults; learn(),
+    the frame of the native loop and the replay-buffer files are OffPolicyAlgorithm's."""
 
     ALGORITHM = "sac"
 
@@ -177,30 +175,10 @@ class SAC(PPO):
                  use_sde: bool = False, sde_sample_freq: int = -1, use_sde_at_warmup: bool = False, stats_window_size: int = 100,
                  tensorboard_log: str | None = None, policy_kwargs: dict | None = None, verbose: int = 0, seed: int | None = None, device="auto",
                  _init_setup_model: bool = True):
-        import collections
-
-        from . import dist as _dist
-
-        if policy not in ("MlpPolicy", "MultiInputPolicy"):
-            raise ValueError(f"three-mlagents_amd SAC supports MlpPolicy (vector observations), got '{policy}'")
-        if callable(learning_rate):
-            raise ValueError("schedules are not supported: pass a constant learning_rate (the reference does)")
         if use_sde:
             raise ValueError("use_sde=True is not built (generalised state-dependent exploration has no kernel)")
         if action_noise is not None:
             raise ValueError("action_noise is not built: SAC explores through its own policy noise")
-        if isinstance(train_freq, (tuple, list)):
-            if len(train_freq) != 2 or str(train_freq[1]) != "step":
-                raise ValueError(f"train_freq per episode is not supported: pass a number of steps (got {train_freq!r})")
-            train_freq = train_freq[0]
-        if optimize_memory_usage:
-            raise ValueError("optimize_memory_usage=True is not built (next_observations is a plane of its own)")
-        if int(train_freq) < 1 or int(batch_size) < 1 or int(target_update_interval) < 1 or int(buffer_size) < 1 or int(learning_starts) < 0:
-            raise ValueError("train_freq, batch_size, target_update_interval and buffer_size must be at least 1, learning_starts at least 0")
-        if int(gradient_steps) == 0 or int(gradient_steps) < -1:
-            raise ValueError(f"gradient_steps must be at least 1, or -1 for as many as the vector steps collected (got {gradient_steps})")
-        if not 0.0 < float(tau) <= 1.0:
-            raise ValueError(f"tau must be in (0, 1] (got {tau})")
         pk = dict(policy_kwargs or {})
         if int(pk.get("n_critics", 2)) != 2:
             raise ValueError(f"n_critics must be 2 (got {pk.get('n_critics')})")
@@ -221,27 +199,9 @@ class SAC(PPO):
         if isinstance(target_entropy, str) and target_entropy != "auto":
             raise ValueError(f"target_entropy must be 'auto' or a number (got {target_entropy!r})")
         self.target_entropy = target_entropy
-        self.policy_class, self.env = policy, env
-        self.stats_window_size = int(stats_window_size) if stats_window_size else 0
-        self._ep_info_r = collections.deque(maxlen=max(self.stats_window_size, 1))
-        self._ep_info_l = collections.deque(maxlen=max(self.stats_window_size, 1))
-        self.learning_rate, self.buffer_size, self.learning_starts, self.batch_size = float(learning_rate), int(buffer_size), int(learning_starts), int(batch_size)
-        self.tau, self.gamma, self.train_freq, self.gradient_steps, self.n_steps = float(tau), float(gamma), int(train_freq), int(gradient_steps), int(n_steps)
-        self.optimize_memory_usage, self.action_noise, self.use_sde = False, None, False
-        self.target_update_interval = int(target_update_interval)
-        self.policy_kwargs = pk
-        self.tensorboard_log, self.verbose = tensorboard_log, int(verbose)
-        self.seed = 0 if seed is None else int(seed)
-        self.num_timesteps = self._n_updates = self._adam_step = self._n_calls = 0
-        self._total_timesteps = 0
-        self.logger_values: dict[str, float] = {}
-        self.policy: HipSACPolicy | None = None
-        self.replay_buffer: ReplayBuffer | None = None
-        self._last_obs_valid = False
-        self._native_comm = None
-        self.world_size, self.rank = _dist.world_size(), _dist.rank()
-        if env is not None and _init_setup_model:
-            self._setup_model()
+        self.action_noise, self.use_sde = None, False
+        super().__init__(policy, env, learning_rate, buffer_size, learning_starts, batch_size, tau, gamma, train_freq, gradient_steps, optimize_memory_usage,
+                         n_steps, target_update_interval, stats_window_size, tensorboard_log, pk, verbose, seed, _init_setup_model)
 
     # ------------------------------------------------------------------------------------
     @staticmethod
@@ -344,20 +304,11 @@ class SAC(PPO):
         return _lib.SACCounters(self.num_timesteps, self._n_calls, rb.pos, 1 if rb.full else 0, rb._draw & 0xFFFFFFFF, rb._collect_step & 0xFFFFFFFF,
                                 self._adam_step, self._n_updates)
 
-    _take_counters = DQN._take_counters
-
-    def _run_iterations(self, n_iters: int) -> None:
+    def _native_iterations(self, hp, c, n_iters: int) -> int:
         pol = self.policy
-        if not self._last_obs_valid:
-            self.replay_buffer.start(self.env.reset_device())
-            self._last_obs_valid = True
-        c, hp = self._counters(), self._hparams()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().tma_sac_iterations_local(self.env.engine._h, _lib.ptr(pol.actor), _lib.ptr(pol.critic), _lib.ptr(pol.critic_target),
-                                                           _lib.ptr(pol.log_ent_coef), C.byref(pol.dims), C.byref(self.replay_buffer._view),
-                                                           C.byref(self._buffers), C.byref(hp), C.byref(c), int(n_iters), self._stream()))
-        self._take_counters(c)
-        self._mark_update_done()
+        return _lib.lib().tma_sac_iterations_local(self.env.engine._h, _lib.ptr(pol.actor), _lib.ptr(pol.critic), _lib.ptr(pol.critic_target),
+                                                   _lib.ptr(pol.log_ent_coef), C.byref(pol.dims), C.byref(self.replay_buffer._view), C.byref(self._buffers),
+                                                   C.byref(hp), C.byref(c), n_iters, self._stream())
 
     # -- update ---------------------------------------------------------------------------
     def train(self, gradient_steps: int = 1, batch_size: int | None = None) -> None:
@@ -405,78 +356,6 @@ class SAC(PPO):
             # the pre-step value of log_ent_coef is not kept: the loss is reported with the post-step one (they differ by at most one lr-sized step)
             out["train/ent_coef_loss"] = log_alpha * g
         return out
-
-    # -- learn ----------------------------------------------------------------------------
-    def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "SAC", reset_num_timesteps: bool = True,
-              progress_bar: bool = False):
-        """SB3's learn.  Without a callback the iterations run in native calls of up to NATIVE_ITERATIONS; after each call the episode log is
-        popped and a log row is dumped once at least `log_interval` episodes have finished since the last row (SB3 dumps at that episode).  With a
-        callback: one iteration per native call, its train_freq vector steps reported through callbacks.BaseCallback.on_steps afterwards."""
-        from .callbacks import as_callback
-
-        cb = as_callback(callback)
-        if reset_num_timesteps:
-            self.num_timesteps = 0
-        else:
-            total_timesteps = int(total_timesteps) + self.num_timesteps
-        self._total_timesteps = int(total_timesteps)
-        eng, N = self.env.engine, self.n_envs
-        per_iter = self.train_freq * N
-        if getattr(eng, "_log_cap", 0) == 0:
-            eng.episode_log(max(4096, 2 * NATIVE_ITERATIONS * per_iter))
-        cb.init_callback(self)
-        cb.on_training_start(locals(), globals())
-        t0 = t_prev = time.time()
-        episodes = since_row = 0
-        first_timestep = self.num_timesteps
-        try:
-            while self.num_timesteps < total_timesteps:
-                remaining = -(-(total_timesteps - self.num_timesteps) // per_iter)
-                n = 1 if callback is not None else min(remaining, NATIVE_ITERATIONS)
-                cb.on_rollout_start()
-                start = self.num_timesteps
-                self._run_iterations(n)
-                keep_going = True
-                if callback is not None:
-                    end, self.num_timesteps = self.num_timesteps, start
-                    _, keep_going = cb.on_steps(self.train_freq, N)
-                    self.num_timesteps = end
-                cb.on_rollout_end()
-                cb.on_update_queued()
-                r, l, e, seen = eng.pop_episode_log()
-                s_ret, s_len, cnt = float(np.sum(r)), float(np.sum(l)), len(r)
-                window = self._episode_window(r, l, s_ret, s_len, cnt)
-                episodes += seen
-                since_row += seen
-                now = time.time()
-                self._write_monitor(s_ret, s_len, cnt, t_prev - t0, now - t0, t0, log=(r, l, e, seen))
-                t_prev = now
-                if log_interval and since_row >= log_interval:
-                    since_row = 0
-                    stats = {"rollout/ep_rew_mean": window[0], "rollout/ep_len_mean": window[1], "train/n_updates": self._n_updates,
-                             "train/learning_rate": self.learning_rate, "time/episodes": episodes,
-                             "time/fps": (self.num_timesteps - first_timestep) / max(now - t0, 1e-9), "time/time_elapsed": now - t0,
-                             "time/total_timesteps": self.num_timesteps}
-                    if self._n_updates > 0:
-                        stats.update(self.pop_train_stats())
-                    self.logger_values = stats
-                    self._write_progress(stats, self.num_timesteps)
-                    if self.verbose >= 1:
-                        print(json.dumps({k: (round(v, 6) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
-                if not keep_going:
-                    break
-        except BaseException:
-            self._join_monitor_writer(reraise=False)
-            flush = getattr(cb, "flush", None)
-            if callable(flush):
-                try:
-                    flush()
-                except Exception:  # noqa: BLE001 -- never mask the exception that is unwinding
-                    pass
-            raise
-        self._join_monitor_writer()
-        cb.on_training_end()
-        return self
 
     # -- inference ------------------------------------------------------------------------
     def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
@@ -559,9 +438,6 @@ class SAC(PPO):
                                                                                       self.learning_rate, eps=ADAM_EPS)))
             z.writestr("pytorch_variables.pth", _pth({"log_ent_coef": pol.log_ent_coef.detach().cpu()}))
             z.writestr("_stable_baselines3_version", "2.9.0+three-mlagents_amd")
-
-    save_replay_buffer = DQN.save_replay_buffer
-    load_replay_buffer = DQN.load_replay_buffer
 
     @classmethod
     def load(cls, path, env=None, device="auto", **kwargs) -> "SAC":

@@ -25,9 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dqn import pol_space
+from .off_policy import ADAM_EPS, OffPolicyAlgorithm, pol_space
 from .replay_buffer import ReplayBuffer
-from .sac import ADAM_EPS, SAC, _OptState, critic_tensors, flat_from_named, named_from_flat, sac_dims
+from .sac import SAC, _OptState, critic_tensors, flat_from_named, named_from_flat, sac_dims
 from .vec_env import HipVecEnv
 
 SUPPORTED_WIDTHS = (64, 128, 256)
@@ -166,38 +166,20 @@ class HipTD3Policy:
 
 class TD3(SAC):
     """SB3-shaped TD3 whose compute is libtma_hip.so.  Constructor / learn / train / predict / save / load keep SB3's names and defaults, except the
-    default net_arch ([256, 256]).  learn(), the episode log and the replay-buffer files are SAC's."""
+    default net_arch ([256, 256]).  learn(), the frame of the native loop and the replay-buffer files are OffPolicyAlgorithm's; the SB3 attribute
+    names of the parts, the actor / critic optimizer states and the saved action space are SAC's."""
 
     ALGORITHM = "td3"
+    ADAM_COUNTERS = {"_adam_step": "critic_adam_step", "_actor_adam_step": "actor_adam_step"}  # (_adam_step: the critic's)
 
     def __init__(self, policy: str = "MlpPolicy", env=None, learning_rate: float = 1e-3, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq=1, gradient_steps: int = 1, action_noise=None,
                  optimize_memory_usage: bool = False, n_steps: int = 1, policy_delay: int = 2, target_policy_noise: float = 0.2,
                  target_noise_clip: float = 0.5, stats_window_size: int = 100, tensorboard_log: str | None = None, policy_kwargs: dict | None = None,
                  verbose: int = 0, seed: int | None = None, device="auto", _init_setup_model: bool = True):
-        import collections
-
-        from . import dist as _dist
-
-        if policy not in ("MlpPolicy", "MultiInputPolicy"):
-            raise ValueError(f"three-mlagents_amd TD3 supports MlpPolicy (vector observations), got '{policy}'")
-        if callable(learning_rate):
-            raise ValueError("schedules are not supported: pass a constant learning_rate (the reference does)")
         if action_noise is not None and not isinstance(action_noise, NormalActionNoise):
             raise ValueError(f"action_noise must be None or a three_mlagents_amd NormalActionNoise (got {type(action_noise).__name__}): "
                              "Ornstein-Uhlenbeck and other noises are not built")
-        if isinstance(train_freq, (tuple, list)):
-            if len(train_freq) != 2 or str(train_freq[1]) != "step":
-                raise ValueError(f"train_freq per episode is not supported: pass a number of steps (got {train_freq!r})")
-            train_freq = train_freq[0]
-        if optimize_memory_usage:
-            raise ValueError("optimize_memory_usage=True is not built (next_observations is a plane of its own)")
-        if int(train_freq) < 1 or int(batch_size) < 1 or int(buffer_size) < 1 or int(learning_starts) < 0:
-            raise ValueError("train_freq, batch_size and buffer_size must be at least 1, learning_starts at least 0")
-        if int(gradient_steps) == 0 or int(gradient_steps) < -1:
-            raise ValueError(f"gradient_steps must be at least 1, or -1 for as many as the vector steps collected (got {gradient_steps})")
-        if not 0.0 < float(tau) <= 1.0:
-            raise ValueError(f"tau must be in (0, 1] (got {tau})")
         if int(policy_delay) < 1:
             raise ValueError(f"policy_delay must be at least 1 (got {policy_delay})")
         if not float(target_policy_noise) >= 0.0:
@@ -208,27 +190,10 @@ class TD3(SAC):
         if int(pk.get("n_critics", 2)) != 2:
             raise ValueError(f"n_critics must be 2 (got {pk.get('n_critics')})")
         self._arch(pk)  # (an unsupported net_arch is refused here, before any env is looked at)
-        self.policy_class, self.env = policy, env
-        self.stats_window_size = int(stats_window_size) if stats_window_size else 0
-        self._ep_info_r = collections.deque(maxlen=max(self.stats_window_size, 1))
-        self._ep_info_l = collections.deque(maxlen=max(self.stats_window_size, 1))
-        self.learning_rate, self.buffer_size, self.learning_starts, self.batch_size = float(learning_rate), int(buffer_size), int(learning_starts), int(batch_size)
-        self.tau, self.gamma, self.train_freq, self.gradient_steps, self.n_steps = float(tau), float(gamma), int(train_freq), int(gradient_steps), int(n_steps)
         self.policy_delay, self.target_policy_noise, self.target_noise_clip = int(policy_delay), float(target_policy_noise), float(target_noise_clip)
-        self.optimize_memory_usage, self.action_noise, self.use_sde = False, action_noise, False
-        self.policy_kwargs = pk
-        self.tensorboard_log, self.verbose = tensorboard_log, int(verbose)
-        self.seed = 0 if seed is None else int(seed)
-        self.num_timesteps = self._n_updates = self._adam_step = self._actor_adam_step = self._n_calls = 0  # (_adam_step: the critic's)
-        self._total_timesteps = 0
-        self.logger_values: dict[str, float] = {}
-        self.policy: HipTD3Policy | None = None
-        self.replay_buffer: ReplayBuffer | None = None
-        self._last_obs_valid = False
-        self._native_comm = None
-        self.world_size, self.rank = _dist.world_size(), _dist.rank()
-        if env is not None and _init_setup_model:
-            self._setup_model()
+        self.action_noise, self.use_sde = action_noise, False
+        OffPolicyAlgorithm.__init__(self, policy, env, learning_rate, buffer_size, learning_starts, batch_size, tau, gamma, train_freq, gradient_steps,
+                                    optimize_memory_usage, n_steps, None, stats_window_size, tensorboard_log, pk, verbose, seed, _init_setup_model)
 
     # ------------------------------------------------------------------------------------
     @staticmethod
@@ -320,26 +285,11 @@ class TD3(SAC):
         return _lib.TD3Counters(self.num_timesteps, self._n_calls, rb.pos, 1 if rb.full else 0, rb._draw & 0xFFFFFFFF, rb._collect_step & 0xFFFFFFFF,
                                 self._adam_step, self._actor_adam_step, self._n_updates)
 
-    def _take_counters(self, c) -> None:
-        rb = self.replay_buffer
-        self.num_timesteps, self._n_calls, self._n_updates = int(c.num_timesteps), int(c.n_calls), int(c.n_updates)
-        self._adam_step, self._actor_adam_step = int(c.critic_adam_step), int(c.actor_adam_step)
-        rb.pos, rb.full = int(c.pos), bool(c.full)
-        rb._draw += (int(c.draw) - rb._draw) & 0xFFFFFFFF            # (the 32-bit counters wrap; the host ones do not)
-        rb._collect_step += (int(c.collect_step) - rb._collect_step) & 0xFFFFFFFF
-
-    def _run_iterations(self, n_iters: int) -> None:
+    def _native_iterations(self, hp, c, n_iters: int) -> int:
         pol = self.policy
-        if not self._last_obs_valid:
-            self.replay_buffer.start(self.env.reset_device())
-            self._last_obs_valid = True
-        c, hp = self._counters(), self._hparams()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().tma_td3_iterations_local(self.env.engine._h, _lib.ptr(pol.actor), _lib.ptr(pol.actor_target), _lib.ptr(pol.critic),
-                                                           _lib.ptr(pol.critic_target), C.byref(pol.dims), C.byref(self.replay_buffer._view),
-                                                           C.byref(self._buffers), C.byref(hp), C.byref(c), int(n_iters), self._stream()))
-        self._take_counters(c)
-        self._mark_update_done()
+        return _lib.lib().tma_td3_iterations_local(self.env.engine._h, _lib.ptr(pol.actor), _lib.ptr(pol.actor_target), _lib.ptr(pol.critic),
+                                                   _lib.ptr(pol.critic_target), C.byref(pol.dims), C.byref(self.replay_buffer._view), C.byref(self._buffers),
+                                                   C.byref(hp), C.byref(c), n_iters, self._stream())
 
     # -- update ---------------------------------------------------------------------------
     def train(self, gradient_steps: int = 1, batch_size: int | None = None) -> None:
@@ -384,12 +334,6 @@ class TD3(SAC):
         if self._actor_adam_step > 0 and as_[1]:
             out["train/actor_loss"] = as_[0] / as_[1]
         return out
-
-    def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "TD3", reset_num_timesteps: bool = True,
-              progress_bar: bool = False):
-        """SB3's learn, run as SAC.learn runs it: native calls of whole iterations, the episode log popped in between."""
-        return super().learn(total_timesteps, callback=callback, log_interval=log_interval, tb_log_name=tb_log_name,
-                             reset_num_timesteps=reset_num_timesteps, progress_bar=progress_bar)
 
     # -- inference ------------------------------------------------------------------------
     def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
