@@ -17,6 +17,12 @@ static __device__ unsigned long long g_h64_tail_ticks;  // diagnostic build: the
 // last barrier in front of the loop).  Slots 8..15: loop-end clock of wave w minus wave 0's (two's complement).  The prologue stamps stay
 // in registers until the loop starts: a stamp is one s_memtime, not a global read-add-write.
 static __device__ unsigned long long g_h64_edge_ticks[2][16];
+// ... and how the two waves of a SIMD (w and w + 4) share their loop, block pair 0, every wave (tma_debug_h64_pair_ticks), sums over launches:
+// [0] loop length, [1] the partner's completed tiles when this wave left, [2] / [3] cycles and tiles from the loop's start to the last tile
+// top at which the partner was still in its loop, [4] / [5] cycles and tiles from the first tile top that found the partner gone to the
+// loop's end (the tile in between is of both kinds and of neither sum), [6] tiles run, [7] loop start minus wave 0's.  The bookkeeping is
+// two LDS words a wave and registers: lane 0 writes the wave's tile count at every tile top, a departing wave reads its partner's once.
+static __device__ unsigned long long g_h64_pair_ticks[2][8][8];
 #ifndef TMA_H64_TICK_PAIR
 #define TMA_H64_TICK_PAIR 0  // the stamped block pair (pair 0 also writes the next optimizer state: -DTMA_H64_TICK_PAIR=1 shows a pair that does not)
 #endif
@@ -500,18 +506,21 @@ struct AdamImageFold {
     }
 };
 
-template <bool IS_PI, int DT, bool DIRECT = false, int AT = 0, int FOLD = FOLD_BOTH>  // AT > 0: compile-time head width of the policy net, 0: runtime L.A; FOLD: h64t_tile's
+// BAL (eight-wave kernel): the two waves of a SIMD hold each other's pace through the issue priority (pair_progress below)
+template <bool IS_PI, int DT, bool DIRECT = false, int AT = 0, int FOLD = FOLD_BOTH, bool BAL = false>  // AT > 0: compile-time head width of the policy net, 0: runtime L.A; FOLD: h64t_tile's
 __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params, const PLayout &L, const Rollout &rb, const Minibatch &mb,
                                                const HParams &hp, const double *__restrict__ adv_part, int n_part, float *__restrict__ slab,
                                                double *__restrict__ stat_slot, float *smem, int n_blocks_net, int block_net, const AdamFold &fold,
                                                const PrepNext &next) {
 #ifdef TMA_H64_TICKS
     const unsigned long long kern_t0 = __builtin_amdgcn_s_memtime();
+    constexpr bool PAIR_TICKS = !DIRECT;  // diagnostic build: the pace of the two waves of a SIMD (g_h64_pair_ticks)
+#else
+    constexpr bool PAIR_TICKS = false;
 #endif
     __shared__ float adv_ms[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const int r16 = lane & 15, g = lane >> 4;  // r16: the tile's sample this lane works for (and the A operand's row); g: lane group
-    (void)0;
     const int D = DT > 0 ? DT : L.D, A = AT > 0 ? AT : L.A;
     constexpr int KS1C = DT > 0 ? (DT + 3) / 4 : 4;  // layer-1 k-steps held in registers (runtime D: up to 16 features)
     const int KS1 = (D + 3) >> 2;
@@ -643,6 +652,15 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
         af.finish(fold, wimg, block_net, fold_coef, pt);
         H64_PRO_STAMP(pt, 3);
     }
+    // Tiles each wave has completed, written by its lane 0 at every tile top and read there by the wave that shares its SIMD (wave ^ 4).
+    // The hardware issues oldest first: left alone, the older wave of a SIMD leaves the loop about two tiles ahead and the younger one runs
+    // the rest with nothing beside it.  Nobody waits on these words: a stale one mis-sets a priority for one tile.
+    [[maybe_unused]] __shared__ int pair_progress[8];
+    if constexpr (BAL || PAIR_TICKS) pair_progress[lane & 7] = 0;  // (every lane, the same word eight times over: no branch near the loads in flight)
+#ifdef TMA_H64_TICKS
+    __shared__ int pair_left[8];  // diagnostic build: wave w is out of its loop
+    pair_left[lane & 7] = 0;
+#endif
     lds_barrier();  // the image (and, without a folded step, the advantage statistics)
     H64_PRO_STAMP(pt, 4);
     const float amean = (IS_PI && hp.normalize_advantage) ? adv_ms[0] : 0.0f;
@@ -657,7 +675,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
     // the two waves a SIMD hosts (w and w + 4) run the same program: started together they tend to stay in lockstep -- both in their
     // MFMA-dense phases, then both in their VALU phases -- so the second half of the block starts a fraction of a tile later
     if (wave >= 4)
-        for (int q = 0; q < hp.debug; q++) __builtin_amdgcn_s_sleep(100);
+        for (int q = 0; q < (hp.debug & 0xffff); q++) __builtin_amdgcn_s_sleep(100);
 #ifdef TMA_H64_TICKS
     const bool tick_on = block_net == TMA_H64_TICK_PAIR && wave == 0;
     tk.on = tick_on, tk.prev = __builtin_amdgcn_s_memtime();
@@ -666,9 +684,41 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
         g_h64_ticks[IS_PI ? 0 : 1][12] += loop_t0 - kern_t0;
         for (int i = 0; i < 5; i++) g_h64_edge_ticks[IS_PI ? 0 : 1][i] += pt.t[i] - kern_t0;
     }
-    __shared__ unsigned long long wave_end[8];
+    __shared__ unsigned long long wave_end[8], wave_beg[8];
+    unsigned long long paired_c = 0, solo_t = 0;
+    int paired_n = 0, solo_n = -1;
 #endif
+    [[maybe_unused]] int done = 0;  // tiles this wave has completed
     for (int64_t tile = (int64_t)block_net * wpb + wave; tile < n_tiles; tile += tile_stride) {
+        if constexpr (BAL || PAIR_TICKS) {
+            // (relaxed atomics: one ds_write_b32 / ds_read_b32 that the compiler neither caches nor hoists, and no wait beyond the read's own)
+            if (lane == 0) __hip_atomic_store(&pair_progress[wave], done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if constexpr (BAL) {
+                // behind the partner: priority 1, ahead of it: 0, level: the younger wave (the one that loses the arbitration) takes 1.
+                // One uniform word decides, so the branch around the immediate is a scalar one.
+                const int lead = __hip_atomic_load(&pair_progress[wave ^ 4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - done;  // (> 0: the partner leads)
+#ifdef TMA_H64_TICKS  // diagnostic build: the variants that were measured (TMA_H64_PAIR_PRIO = 2 / 3: a wider gap; TMA_H64_PAIR_LEAD: only beyond one tile)
+                const int bal_hi = (hp.debug >> 16) & 3;
+                const bool raise = ((hp.debug >> 18) & 1) ? lead > 1 : (lead > 0 || (lead == 0 && wave >= 4));
+                if (__builtin_amdgcn_readfirstlane((int)raise)) {
+                    if (bal_hi == 3) __builtin_amdgcn_s_setprio(3);
+                    else if (bal_hi == 2) __builtin_amdgcn_s_setprio(2);
+                    else __builtin_amdgcn_s_setprio(1);
+                } else __builtin_amdgcn_s_setprio(0);
+#else
+                if (__builtin_amdgcn_readfirstlane((int)(lead > 0 || (lead == 0 && wave >= 4)))) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+#endif
+            }
+        }
+#ifdef TMA_H64_TICKS
+        if constexpr (PAIR_TICKS) {
+            const unsigned long long top = __builtin_amdgcn_s_memtime();
+            if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&pair_left[wave ^ 4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) paired_c = top - loop_t0, paired_n = done;
+            else if (solo_n < 0) solo_t = top, solo_n = done;
+        }
+#endif
+        done++;
         H64_TICK(15);
         // ---- commit the prefetched tile ----
         const bool valid = ((tile << 4) + r16) < mb.count;
@@ -680,18 +730,32 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
         fetch(tile + tile_stride);
         h64t_tile<IS_PI, KS1C, AT, FOLD>(wimg, slotA, slotB, slotC, dz3t, Xt, xb, m0, m1, act, valid, KS1, A, invB, amean, astd, hp, acc, st, tk, lane);
     }
+    if constexpr (BAL) __builtin_amdgcn_s_setprio(0);
 #ifdef TMA_H64_TICKS
     const unsigned long long loop_t1 = __builtin_amdgcn_s_memtime();
+    [[maybe_unused]] int partner_done = 0;
+    if constexpr (PAIR_TICKS) {
+        if (lane == 0) __hip_atomic_store(&pair_left[wave], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        partner_done = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&pair_progress[wave ^ 4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    }
     if (tick_on && lane == 0) {
         g_h64_ticks[IS_PI ? 0 : 1][10] += loop_t1 - loop_t0;
         g_h64_ticks[IS_PI ? 0 : 1][11] += __builtin_amdgcn_s_memrealtime() - loop_r0;
     }
 #endif
 #ifdef TMA_H64_TICKS
-    if (lane == 0) wave_end[wave] = loop_t1;
+    if (lane == 0) wave_end[wave] = loop_t1, wave_beg[wave] = loop_t0;
 #endif
     __syncthreads();
 #ifdef TMA_H64_TICKS
+    if constexpr (PAIR_TICKS) {
+        if (block_net == TMA_H64_TICK_PAIR && lane == 0) {  // (one writer per slot)
+            unsigned long long *p = g_h64_pair_ticks[IS_PI ? 0 : 1][wave];
+            p[0] += loop_t1 - loop_t0, p[1] += partner_done, p[2] += paired_c, p[3] += paired_n;
+            if (solo_n >= 0) p[4] += loop_t1 - solo_t, p[5] += done - solo_n;
+            p[6] += done, p[7] += loop_t0 - wave_beg[0];
+        }
+    }
     if (tick_on && lane == 0) g_h64_ticks[IS_PI ? 0 : 1][14] += __builtin_amdgcn_s_memtime() - loop_t1;  // waiting for the block's slowest wave
     if (block_net == TMA_H64_TICK_PAIR && lane == 0) g_h64_edge_ticks[IS_PI ? 0 : 1][8 + wave] += loop_t1 - wave_end[0];  // (one writer per slot)
 #endif
@@ -740,7 +804,7 @@ __device__ __forceinline__ void grad_h64t_body(const float *__restrict__ params,
     }
 }
 
-template <int DT, int VER, int AT = 0, int FOLD = FOLD_BOTH>  // FOLD: h64t_tile's order of the small weight gradients; AT > 0 (VER 2): compile-time head width -- <4, 2, 5> is the headline shape (GridWorld: 4 observations, 5 actions)
+template <int DT, int VER, int AT = 0, int FOLD = FOLD_BOTH, bool BAL = false>  // BAL: grad_h64t_body's pair balance; FOLD: h64t_tile's order of the small weight gradients; AT > 0 (VER 2): compile-time head width -- <4, 2, 5> is the headline shape (GridWorld: 4 observations, 5 actions)
 __global__ __launch_bounds__(512, 2) void ppo_grad_h64_kernel(const float *__restrict__ params, PLayout L, Rollout rb, Minibatch mb, HParams hp,
                                                               const double *__restrict__ adv_part, int n_part, float *__restrict__ slabs,
                                                               double *__restrict__ stat_slots, AdamFold fold, PrepNext next) {
@@ -755,8 +819,8 @@ __global__ __launch_bounds__(512, 2) void ppo_grad_h64_kernel(const float *__res
         if (pi_block) grad_h64_body<true, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair);
         else grad_h64_body<false, DT>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair);
     } else {
-        if (pi_block) grad_h64t_body<true, DT, false, AT, FOLD>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
-        else grad_h64t_body<false, DT, false, 0, FOLD>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
+        if (pi_block) grad_h64t_body<true, DT, false, AT, FOLD, BAL>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
+        else grad_h64t_body<false, DT, false, 0, FOLD, BAL>(params, L, rb, mb, hp, adv_part, n_part, slab, slot, smem, n_pairs, pair, fold, next);
     }
 }
 
@@ -816,7 +880,14 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
     static const bool runtime_a = getenv("TMA_H64_RUNTIME_A") != nullptr;  // (A/B and test switch: the runtime-head-width kernel at every shape)
     const int small_fold = tma_h64_small_fold();
     HParams hps = hpar;
-    hps.debug = stagger;
+    hps.debug = stagger & 0xffff;
+    // A/B and test switch, read per call: TMA_H64_NO_PAIR_BALANCE=1 launches the eight-wave kernel without the pair balance
+    const char *nb = getenv("TMA_H64_NO_PAIR_BALANCE");
+    const bool balance = !(nb && nb[0] == '1');
+#ifdef TMA_H64_TICKS
+    if (const char *e = getenv("TMA_H64_PAIR_PRIO")) hps.debug |= (atoi(e) & 3) << 16;
+    if (getenv("TMA_H64_PAIR_LEAD")) hps.debug |= 1 << 18;
+#endif
     const int64_t tiles = ceil_div(M.count, 16);
     if (ver == 2 && tiles <= H64_BLOCKS) {  // up to 2048 samples: one tile per wave, 4-wave blocks (a 256-sample minibatch: 4 + 4 blocks, 4 slabs)
         const int64_t blocks = ceil_div(tiles, 4);
@@ -847,10 +918,10 @@ int tma_launch_grad_h64(const float *params, const PLayout &L, const Rollout &R,
     int rc;
     if (ver == 1) rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 1>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 1>) : launch(ppo_grad_h64_kernel<0, 1>));
     else if (L.D == 4 && L.A == 5 && !runtime_a) {  // the headline shape: head width folded as well
-        rc = small_fold == FOLD_BOTH ? launch(ppo_grad_h64_kernel<4, 2, 5>)
+        rc = small_fold == FOLD_BOTH ? (balance ? launch(ppo_grad_h64_kernel<4, 2, 5, FOLD_BOTH, true>) : launch(ppo_grad_h64_kernel<4, 2, 5>))
              : (small_fold == FOLD_W1 ? launch(ppo_grad_h64_kernel<4, 2, 5, FOLD_W1>)
                                       : (small_fold == FOLD_W3 ? launch(ppo_grad_h64_kernel<4, 2, 5, FOLD_W3>) : launch(ppo_grad_h64_kernel<4, 2, 5, 0>)));
-    } else if (small_fold == FOLD_BOTH) {
+    } else if (small_fold == FOLD_BOTH) {  // (no pair balance at runtime widths: with the counter these kernels spill 11 / 16 / 31 VGPRs where they spill 9 / 15 / 19)
         rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 2>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 2>) : launch(ppo_grad_h64_kernel<0, 2>));
     } else {
         rc = L.D == 4 ? launch(ppo_grad_h64_kernel<4, 2, 0, 0>) : (L.D == 6 ? launch(ppo_grad_h64_kernel<6, 2, 0, 0>) : launch(ppo_grad_h64_kernel<0, 2, 0, 0>));
@@ -869,6 +940,15 @@ extern "C" int tma_debug_h64_tail_ticks(unsigned long long *out, int reset) {
     if (reset) {
         unsigned long long z = 0;
         TMA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_h64_tail_ticks), &z, sizeof(z)));
+    }
+    return TMA_OK;
+}
+extern "C" int tma_debug_h64_pair_ticks(unsigned long long *out128, int reset) {  // out128: [net][wave][8] (g_h64_pair_ticks)
+    TMA_HIP(hipDeviceSynchronize());
+    if (out128) TMA_HIP(hipMemcpyFromSymbol(out128, HIP_SYMBOL(g_h64_pair_ticks), sizeof(unsigned long long) * 128));
+    if (reset) {
+        unsigned long long z[128] = {};
+        TMA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_h64_pair_ticks), z, sizeof(z)));
     }
     return TMA_OK;
 }

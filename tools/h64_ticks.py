@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Per-phase cycle breakdown of the H = 64 gradient kernel's tile chain (diagnostic build libtma_hip_ticks.so, wave 0 of block pair 0).
+"""Per-phase cycle breakdown of the H = 64 gradient kernel's tile chain (diagnostic build libtma_hip_ticks.so, wave 0 of block pair 0), and
+how the two waves of each SIMD of that block pair share the loop (TMA_H64_NO_PAIR_BALANCE=1: without the pair balance; TMA_H64_PAIR_PRIO=2 / 3
+and TMA_H64_PAIR_LEAD=1: the variants of it that only this build has).  A second argument `loop` stops behind the tile loop's figures.
 Run: make -C three-mlagents_amd/csrc libtma_hip_ticks.so && TMA_LIB_PATH=three-mlagents_amd/csrc/libtma_hip_ticks.so python tools/h64_ticks.py"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +24,9 @@ for _ in range(3):
 out = (C.c_ulonglong * 64)()  # [0..31]: the tile phases and launch sums of both nets; [32..63]: the launch edges (g_h64_edge_ticks)
 L.tma_debug_h64_ticks.argtypes = [C.c_void_p, C.c_int]
 L.tma_debug_h64_ticks(None, 1)
+if hasattr(L, "tma_debug_h64_pair_ticks"):
+    L.tma_debug_h64_pair_ticks.argtypes = [C.c_void_p, C.c_int]
+    L.tma_debug_h64_pair_ticks(None, 1)
 def edges(n):
     """The prologue split at its waits and barriers (cumulative, wave 0) and each wave's loop-end clock against wave 0's: block pair 0, per launch."""
     for net, o in (("pi", 32), ("vf", 48)):
@@ -53,6 +58,30 @@ for net, o in (("pi", 0), ("vf", 16)):
     print("    of the epilogue,", round(out[o + 14] / reps), "cycles are the wait for the block's slowest wave")
     print("    per launch: loop", round(loop_c), "cycles =", round(loop_rt / 100, 1), "us (100 MHz counter) -> clock", round(loop_c / max(loop_rt, 1) * 0.1, 2),
           "GHz; prologue", round(pro), "cycles, epilogue", round(epi), "cycles")
+
+def pairs(pt, n):
+    """How the two waves of a SIMD (w and w + 4) of block pair 0 share their loop, per launch: (a) the loop clock at which the one that left
+    first did, (b) its partner's completed tiles at that moment, (c) the partner's cycles per tile up to its last tile top with company,
+    (d) its cycles per tile from its first tile top alone to its loop's end.  SIMD 0 hosts the stamped wave 0: read the other three."""
+    for net, o in (("pi", 0), ("vf", 64)):
+        w = [[pt[o + 8 * k + i] for i in range(8)] for k in range(8)]
+        print("   ", net, "loop end of waves 0..7 since wave 0's loop start:", [round((C.c_longlong(w[k][7]).value + w[k][0]) / n) for k in range(8)],
+              "tiles a wave and launch:", [round(w[k][6] / n, 2) for k in range(8)])
+        for k in range(4):
+            first, last = (k, k + 4) if w[k][0] + C.c_longlong(w[k][7]).value <= w[k + 4][0] + C.c_longlong(w[k + 4][7]).value else (k + 4, k)
+            f, l = w[first], w[last]
+            print("   ", net, "waves", (k, k + 4), "-- (a) wave", first, "left at", round(f[0] / n), "of its loop, (b) wave", last, "had completed", round(f[1] / n, 2),
+                  "tiles, (c) wave", last, "with company:", round(l[2] / max(l[3], 1)), "cycles a tile over", round(l[3] / n, 2), "tiles, (d) alone:",
+                  round(l[4] / max(l[5], 1)), "cycles a tile over", round(l[5] / n, 2), "tiles; it left at", round(l[0] / n),
+                  "-- wave", first, "itself:", round(f[2] / max(f[3], 1)), "cycles a tile")
+if hasattr(L, "tma_debug_h64_pair_ticks"):
+    pt = (C.c_ulonglong * 128)()
+    L.tma_debug_h64_pair_ticks(pt, 1)
+    print("pair balance", "off (TMA_H64_NO_PAIR_BALANCE)" if os.environ.get("TMA_H64_NO_PAIR_BALANCE", "")[:1] == "1" else
+          "on, priority %s%s" % (os.environ.get("TMA_H64_PAIR_PRIO", "1"), " beyond one tile's lead" if os.environ.get("TMA_H64_PAIR_LEAD") else ""))
+    pairs(pt, reps)
+if sys.argv[2:3] == ["loop"]:  # (python tools/h64_ticks.py 131072 loop: the tile loop alone)
+    sys.exit(0)
 
 # ---- the value blocks' tail phase (the next minibatch's advantage pre-pass, carried by the launch): two epochs of two minibatches of B rows
 # through tma_ppo_train_epochs_local -- four gradient launches a call, three of them carrying a pre-pass
