@@ -20,6 +20,9 @@ LP_TOL = dict(rtol=1e-5, atol=5e-5)  # log-probability and entropy (same test, t
 
 CONFIGS = [(4, 64, 5, False), (6, 256, 5, False), (21, 64, 3, False), (172, 256, 20, True), (4, 128, 5, False),  # tests/test_ppo_gpu.py CONFIGS
            (105, 256, 8, True), (45, 256, 3, False)]
+# the H = 64 image path beyond 4 observations: DT = 6 (Ball3D), a runtime width with one zero-padded column (Bicycle) and four full k-steps (Glider)
+H64_MORE = [(6, 64, 5, False), (7, 64, 3, False), (16, 64, 5, False)]
+CONFIGS += H64_MORE
 
 # (D, H, A, continuous, mfma_dtype, TMA_DISPATCH_FWD_* family the shape runs in)
 FAMILIES = [
@@ -28,14 +31,14 @@ FAMILIES = [
     (6, 256, 5, False, "bf16", "FWD_BF16_NTW4_DISCRETE"), (105, 256, 8, True, "bf16", "FWD_BF16_NTW4_BOX"),
     (4, 320, 3, False, "f32", "FWD_GENERIC"), (6, 64, 4, True, "f32", "FWD_GENERIC"),
     (6, 256, 5, False, "bf16x3", "FWD_F32_NTW4_DISCRETE"),  # mfma_dtype 2: the exact-f32 kernels, as `act`
-]
+] + [(*c, "f32", "FWD_H64") for c in H64_MORE]
 # one run per family above its grid cap (wide: 4096 groups of 32 rows; generic: 8192 blocks of 4 tiles of 16 rows; H = 64: 2048 blocks)
 CAPPED = [
     (4, 64, 5, False, "f32", 131072 + 17, "FWD_H64"),
     (6, 128, 3, True, "f32", 32 * 4096 + 17, "FWD_F32_NTW2_BOX|GRID_CAPPED"), (6, 256, 5, False, "f32", 32 * 4096 + 17, "FWD_F32_NTW4_DISCRETE|GRID_CAPPED"),
     (6, 256, 5, False, "bf16", 32 * 4096 + 17, "FWD_BF16_NTW4_DISCRETE|GRID_CAPPED"),
     (4, 64, 2, True, "f32", 16 * 4 * 8192 + 17, "FWD_GENERIC_W4|GRID_CAPPED"), (21, 64, 3, False, "f32", 16 * 4 * 8192 + 17, "FWD_GENERIC_W4|GRID_CAPPED"),
-]
+] + [(*c, "f32", 131072 + 17, "FWD_H64") for c in H64_MORE]
 
 
 def _policy(D, H, A, cont, seed=5, mfma="f32"):
@@ -163,7 +166,8 @@ def test_same_bits_as_act_above_the_grid_caps(D, H, A, cont, mfma, n, dispatch):
     _check_same_bits_as_act(pol, cont, obs_d, dispatch)
 
 
-@pytest.mark.parametrize("D,H,A,mfma", [(4, 64, 5, "f32"), (4, 64, 16, "f32"), (6, 256, 5, "f32"), (6, 256, 5, "bf16"), (4, 320, 3, "f32"), (21, 64, 2, "f32")])
+@pytest.mark.parametrize("D,H,A,mfma", [(4, 64, 5, "f32"), (4, 64, 16, "f32"), (6, 256, 5, "f32"), (6, 256, 5, "bf16"), (4, 320, 3, "f32"), (21, 64, 2, "f32")]
+                         + [(*c[:3], "f32") for c in H64_MORE])
 def test_out_of_range_discrete_actions_give_nan_and_touch_nothing_else(D, H, A, mfma):
     pol, _ = _policy(D, H, A, False, mfma=mfma)
     n = 203

@@ -1,10 +1,15 @@
 """The dispatch-record table of tests/test_policy_dispatch_gpu.py stays complete: every branch id include/tma.h declares has at least one
 case that is meant to reach it (so a new specialisation cannot ship without a float64 reference test), and every case names ids that
 exist; and the host-only query tma_debug_plan_dispatch -- the pure plan functions of csrc/tma_policy_plan.h behind every launch -- gives every
-case the id the table expects and refuses what the real calls refuse.  None of this touches a GPU."""
+case the id the table expects and refuses what the real calls refuse.  Where one id stands for several compile-time variants the table is checked
+one level down: every bf16 gradient leaf at every width and head, and every variant of the H = 64 image kernels (observation-width class, head
+width, either kernel) together with every task shape that trains on them; the inputs of the H = 64 rows are checked from the references alone
+(the comparator must see their last row tile go).  None of this touches a GPU."""
 import os
 import re
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -134,6 +139,114 @@ def test_every_bf16_gradient_leaf_has_a_case_at_every_width_and_head_it_takes():
     assert want <= have, sorted(want - have)
     # every bf16 gradient row is compared (the dropped-tile rejection included): none of them is a dispatch-only entry
     assert all(e.endswith("_bf16") for e, D, H, A, cont, B, ident in t.CASES if ident.startswith("GRAD_BF16_"))
+
+
+def h64_grad_class(D, A, B):
+    """The compile-time variant tma_launch_grad_h64 (csrc/tma_h64.hip) launches for a Discrete D x 64 x A policy and a minibatch of B samples,
+    restated from its code: (kernel, DT, AT, KS1, padded columns).  Up to 128 row tiles of 16 the four-wave small kernel (one tile per wave, no
+    compile-time head), beyond them the eight-wave persistent kernel; DT = D for 4 and 6 observations, 0 (runtime width) otherwise; AT = 5 on
+    the eight-wave kernel at 4 x 64 x 5 alone.  KS1 = (D + 3) >> 2 layer-1 k-steps of four columns; the runtime-width kernels zero-pad the
+    columns D .. 4 KS1 - 1, so KS1 and the padding belong to the class for DT = 0 only (None for the compile-time widths)."""
+    assert 1 <= D <= 16 and 1 <= A <= 16 and B >= 241, (D, A, B)  # (the family: csrc/tma_mlp.h `fast`, plan_grad's tiles >= 16)
+    kernel = "small" if -(-B // 16) <= 128 else "wave8"
+    DT = D if D in (4, 6) else 0
+    AT = 5 if (kernel == "wave8" and D == 4 and A == 5) else 0
+    ks1 = (D + 3) >> 2
+    return (kernel, DT, AT, ks1 if DT == 0 else None, 4 * ks1 - D if DT == 0 else None)
+
+
+def head_row_class(A):
+    """the head's rows in groups of four: A up to 4, 5 .. 8, 9 .. 12, 13 .. 16"""
+    return (A + 3) >> 2
+
+
+def test_every_h64_gradient_variant_has_a_float64_row_on_both_kernels():
+    """GRAD_H64_SMALL and GRAD_H64 are one id each for every DT and AT, so test_every_dispatch_id_has_a_reference_case is satisfied by 4 x 64 x 5
+    alone: this is the same check one level down, on the variant h64_grad_class derives for every f32 `grad` row of the family."""
+    import torch
+
+    import test_policy_dispatch_gpu as t
+
+    rows = [c for c in t.CASES if c[0] == "grad" and c[6] in ("GRAD_H64_SMALL", "GRAD_H64")]
+    for entry, D, H, A, cont, B, ident in rows:  # the restatement, the table and the plan agree on the kernel
+        assert H == 64 and not cont and ident == {"small": "GRAD_H64_SMALL", "wave8": "GRAD_H64"}[h64_grad_class(D, A, B)[0]], (D, A, B, ident)
+        rc, got = t.planned(_case_dims(entry, D, H, A, cont), "grad", B)[:2]
+        assert rc == 0 and got == t.expected_value(ident), (D, A, B, t._name(got))
+    classes = [h64_grad_class(D, A, B) for entry, D, H, A, cont, B, ident in rows]
+    # every (kernel, DT, AT) some shape of the family reaches: every D and A at the first size of either kernel
+    reachable = {h64_grad_class(D, A, B)[:3] for D in range(1, 17) for A in range(1, 17) for B in (241, 2049)}
+    assert reachable == {("small", 4, 0), ("small", 6, 0), ("small", 0, 0), ("wave8", 4, 5), ("wave8", 4, 0), ("wave8", 6, 0), ("wave8", 0, 0)}
+    have = {c[:3] for c in classes}
+    assert reachable <= have, sorted(reachable - have)
+    for kernel in ("small", "wave8"):
+        on = [(c, A) for c, (entry, D, H, A, cont, B, ident) in zip(classes, rows) if c[0] == kernel]
+        assert {1, 2, 3, 4} <= {c[3] for c, A in on}, kernel  # every KS1, at a runtime width
+        assert {0, 1, 3} <= {c[4] for c, A in on}, kernel  # no padded column, one (Bicycle), three
+        assert {1, 2, 3, 4} <= {head_row_class(A) for c, A in on}, kernel
+        assert {(ks1, 3) for ks1 in (1, 2, 3, 4)} <= {(c[3], c[4]) for c, A in on}, kernel  # the most padding at every KS1
+    assert not torch.cuda.is_initialized()
+
+
+def _image_path_tasks():
+    """(task, D, A) of every Discrete task with at most 16 observations and 16 actions, from the package's task and space tables"""
+    from three_mlagents_amd.spaces import Discrete, task_spaces
+    from three_mlagents_amd.tasks import ENGINE_TASKS
+
+    out = []
+    for task in ENGINE_TASKS.values():
+        obs_space, act_space = task_spaces(task.kernel)
+        if isinstance(act_space, Discrete) and obs_space.shape[0] <= 16 and act_space.n <= 16:
+            out.append((task.id, obs_space.shape[0], act_space.n))
+    return out
+
+
+def test_every_task_that_trains_on_the_h64_path_has_its_shape_in_the_table():
+    """Every task whose 64-wide policy runs the LDS-image kernels has, at its own (D, A), a float64 gradient row on the small kernel and on the
+    eight-wave kernel, a forward row and an optimizer row."""
+    import torch
+
+    import test_policy_dispatch_gpu as t
+
+    tasks = _image_path_tasks()
+    assert tasks, "no task of the package's tables has a shape of the H = 64 image family"
+    have = {(entry, D, A, ident) for entry, D, H, A, cont, B, ident in t.CASES if H == 64 and not cont}
+    for name, D, A in tasks:
+        for need in (("grad", D, A, "GRAD_H64_SMALL"), ("grad", D, A, "GRAD_H64"), ("fwd", D, A, "FWD_H64"), ("opt", D, A, "OPT_SCATTER_H64")):
+            assert need in have, (name, need)
+    assert not torch.cuda.is_initialized()
+
+
+def _h64_class_grad_rows():
+    import test_policy_dispatch_gpu as t
+
+    return [pytest.param(*c, id=t._case_id(c)) for c in t.H64_CLASS_CASES if c[0].startswith("grad")]
+
+
+@pytest.mark.parametrize("entry,D,H,A,cont,B,ident", _h64_class_grad_rows())
+def test_comparator_sees_the_last_row_tile_of_every_h64_class_row_dropped(entry, D, H, A, cont, B, ident, record_property):
+    """A condition on the rows' inputs, computed from grad_case_inputs and _grads alone, no kernel: the float64 gradient of the minibatch without
+    its last row tile overshoots the K, F budget at least fourfold (the floor of tests/test_split3_ref_cpu.py), so the rejection each GPU row
+    asserts has room.  A row that falls below moves by a tile; the constants stay."""
+    import torch
+
+    import test_policy_dispatch_gpu as t
+
+    assert t.entry_dtype_kind(entry)[0] == "f32" and H == 64 and not cont
+    sd = t.case_state_dict(D, H, A, cont)
+    c = t.grad_case_inputs(entry, D, A, cont, B, sd)  # (_rollout asserts the clip margin)
+    rows, idx, hp, drop = c["rows"], c["idx"], c["hp"], c["drop"]
+    assert len(idx) == B and drop == (B % 16 or 16)
+    g64, s64 = t._grads(sd, rows, idx, torch.float64, hp)
+    g32, _ = t._grads(sd, rows, idx, torch.float32, hp)
+    gdrop, _ = t._grads(sd, rows, idx[:B - drop], torch.float64, hp)
+    assert 0.05 < s64["clip_fraction"] < 0.95  # both branches of the clipped surrogate
+    errs_drop = t._segment_errors(gdrop, g64, g32)
+    over = max(t.budget_use(*v, t.K, t.F) for v in errs_drop.values())
+    record_property("drop_overshoot", over)
+    print(f"{t._case_id((entry, D, H, A, cont, B, ident))}: drop of {drop} rows overshoots {over:.1f}-fold")
+    assert t._rejects(errs_drop, t.K, t.F)
+    assert over >= 4.0, (over, errs_drop)
+    assert not torch.cuda.is_initialized()
 
 
 def test_plan_query_refuses_what_the_real_calls_refuse():

@@ -20,7 +20,7 @@ import torch
 import _policy_head_ref as ref
 from test_bf16_gpu import _emulated_forward
 from test_evaluate_actions_gpu import CAPPED, FAMILIES, _dispatch_value, _last_fwd_dispatch
-from test_policy_vjp_gpu import LP_TOL, NS, SHAPES, V_TOL, _batch, _bits, _dev, _flat, _policy, _vjp, _within
+from test_policy_vjp_gpu import H64_MORE, LP_TOL, NS, SHAPES, V_TOL, _batch, _bits, _dev, _flat, _policy, _vjp, _within
 
 pytestmark = pytest.mark.gpu
 
@@ -137,7 +137,7 @@ def test_same_bits_above_the_grid_caps(D, H, A, cont, mfma, n, dispatch):
 
 
 # ---- 3
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True), (6, 256, 5, False), (105, 256, 8, True)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True), (6, 256, 5, False), (105, 256, 8, True)] + H64_MORE)
 def test_distribution_is_consistent_with_evaluate_actions(D, H, A, cont):
     from three_mlagents_amd.distributions import CategoricalDistribution, DiagGaussianDistribution
 
@@ -177,7 +177,7 @@ def test_backward_of_a_bf16x3_policy_runs_the_exact_f32_code():
     assert _bits(grad, _head_vjp(pol0, obs, g_head, g_values))
 
 
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True), (6, 256, 5, False)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True), (6, 256, 5, False)] + H64_MORE)
 def test_null_cotangents_are_zeros(D, H, A, cont):
     pol, sd = _policy(D, H, A, cont)
     n = 77
@@ -194,7 +194,7 @@ def test_null_cotangents_are_zeros(D, H, A, cont):
     assert _bits(joint[:v0], only_head[:v0]) and _bits(joint[v0:], only_values[v0:])
 
 
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False), (6, 64, 4, True)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False), (6, 64, 4, True)] + H64_MORE)
 def test_chunk_boundaries(D, H, A, cont, monkeypatch):
     """n = 69 at 32-row chunks: two full chunks and a ragged one, added to the gradient chunk after chunk"""
     pol, sd = _policy(D, H, A, cont)
@@ -210,7 +210,7 @@ def test_chunk_boundaries(D, H, A, cont, monkeypatch):
     _within(one_chunk, want, "one chunk")
 
 
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False)] + H64_MORE)
 def test_reproducible(D, H, A, cont):
     pol, _ = _policy(D, H, A, cont)
     obs = _obs(1000, D, 0)
@@ -220,7 +220,7 @@ def test_reproducible(D, H, A, cont):
 
 
 # ---- 5
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False), (6, 64, 4, True), (105, 256, 8, True)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False), (6, 64, 4, True), (105, 256, 8, True)] + H64_MORE)
 def test_implied_head_cotangent_reproduces_the_evaluate_actions_vjp(D, H, A, cont):
     pol, sd = _policy(D, H, A, cont)
     obs, actions, (g_v, g_lp, g_ent) = _batch(sd, D, A, cont, 77)
@@ -240,7 +240,7 @@ def test_head_is_plain_without_parameters():
     assert not dist.distribution.logits.requires_grad
 
 
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True)] + H64_MORE)
 def test_kl_between_two_policies_backpropagates_to_the_leaf(D, H, A, cont):
     student, s_sd = _policy(D, H, A, cont)
     teacher, t_sd = _policy(D, H, A, cont, seed=11)
@@ -278,7 +278,7 @@ def test_kl_between_two_policies_backpropagates_to_the_leaf(D, H, A, cont):
     assert not student.head(obs_d)[0].requires_grad
 
 
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False), (6, 64, 4, True)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False), (6, 64, 4, True)] + H64_MORE)
 def test_head_follows_a_torch_optimizer_step(D, H, A, cont):
     pol, sd = _policy(D, H, A, cont)
     obs = _obs(77, D, 0)

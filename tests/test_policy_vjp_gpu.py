@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from oracle import sb3_ref
+from test_evaluate_actions_gpu import H64_MORE
 
 pytestmark = pytest.mark.gpu
 
@@ -26,6 +27,7 @@ LP_TOL = dict(rtol=1e-5, atol=5e-5)
 # (D, H, A, Box?): H = 64 image family, generic, column-parallel 128 / 256, generic 320, two-pass Box shapes, and the head edges
 SHAPES = [(4, 64, 5, False), (21, 64, 3, False), (6, 64, 4, True), (4, 128, 5, False), (6, 256, 5, False), (105, 256, 8, True), (4, 320, 3, False),
           (172, 256, 20, True), (4, 64, 2, False), (4, 64, 16, False), (6, 64, 32, True)]
+SHAPES += H64_MORE  # (and every shorter list below that holds (4, 64, 5): the image path at 6, 7 and 16 observations)
 NS = [1, 15, 16, 17, 77]
 
 
@@ -133,7 +135,7 @@ def test_vjp_of_a_bf16x3_policy_runs_the_exact_f32_code():
 
 
 # ---- 2
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False), (6, 64, 4, True)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False), (6, 64, 4, True)] + H64_MORE)
 def test_chunk_boundaries(D, H, A, cont, monkeypatch):
     """n = 69 at 32-row chunks: two full chunks and a ragged one, added to the gradient chunk after chunk"""
     pol, sd = _policy(D, H, A, cont)
@@ -149,7 +151,7 @@ def test_chunk_boundaries(D, H, A, cont, monkeypatch):
 
 
 # ---- 3
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True), (6, 256, 5, False)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True), (6, 256, 5, False)] + H64_MORE)
 def test_null_cotangents_are_zeros(D, H, A, cont):
     pol, sd = _policy(D, H, A, cont)
     n = 77
@@ -168,7 +170,7 @@ def test_null_cotangents_are_zeros(D, H, A, cont):
 
 
 # ---- 4
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 256, 5, False)] + H64_MORE)
 def test_reproducible(D, H, A, cont):
     pol, sd = _policy(D, H, A, cont)
     obs, actions, cots = _batch(sd, D, A, cont, 1000)
@@ -200,7 +202,7 @@ def _rollout(pol, sd, D, A, cont, T, N, seed=0):
     return obs, actions, old_lp.reshape(T, N), torch.randn(T, N, generator=g), torch.randn(T, N, generator=g)
 
 
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True)] + H64_MORE)
 def test_ppo_cotangents_reproduce_the_trained_gradient_kernel(D, H, A, cont):
     from three_mlagents_amd import _lib
 
@@ -245,7 +247,7 @@ def test_out_of_range_action_never_matters_where_its_cotangent_is_zero():
 
 
 # ---- 7
-@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True), (6, 256, 5, False)])
+@pytest.mark.parametrize("D,H,A,cont", [(4, 64, 5, False), (6, 64, 4, True), (6, 256, 5, False)] + H64_MORE)
 def test_autograd_binding(D, H, A, cont):
     pol, sd = _policy(D, H, A, cont)
     n = 77
@@ -288,7 +290,7 @@ def test_parameters_of_a_bf16_policy_are_refused():
 
 
 # ---- 8
-@pytest.mark.parametrize("D,H,A", [(4, 64, 5), (6, 256, 5)])
+@pytest.mark.parametrize("D,H,A", [(4, 64, 5), (6, 256, 5)] + [c[:3] for c in H64_MORE])
 def test_derived_copies_follow_a_torch_optimizer_step(D, H, A):
     pol, sd = _policy(D, H, A, False)
     obs, actions, _ = _batch(sd, D, A, False, 77)
